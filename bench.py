@@ -13,10 +13,16 @@ items for the V-step, RCCL all-gathers in between): "scaling": "strong".
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` for the dominant kernel (als_row_solve's k_row_tasks, timed with
-events on its stream) and `cpu_baseline` (the numpy oracle - a port of the
-reference's CPU path - on a bounded row sample, rank 0, N=1 only).
+Prints ONE JSON line on rank 0, with `roofline` for the dominant kernel
+(als_row_solve's k_row_tasks, timed with events on its stream during the
+timed steps).  A plain run does only that: inputs, set-up, warm-up, the timed
+steps, the line.  `--full` adds what takes runs of its own: `cpu_baseline`
+(the numpy oracle - a port of the reference's CPU path - on a bounded row
+sample, rank 0, N=1 only) and `secondary` (cfg4 in float64, cfg5-small, cfg3).
+
+`--dump-outputs DIR` writes what the fit hands its caller after the last timed
+step (ALS.U / V / b_u / b_i / mu / W / history, see `dump_outputs`) as
+DIR/<name>.npy; inputs are seeded, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -354,6 +360,51 @@ def run_case(size, inputs, dev, *, steps, warmup, dist_on=False, gs_mode=None, g
             "hist": eng.hist[: n_total].cpu().numpy()}
 
 
+DUMP_FACTOR_BYTES = 28 << 20    # per factor matrix (U, V); the whole dump stays under 64 MB
+
+
+def _row_sample(nrows, row_bytes, seed):
+    """Row ids to dump of a side with `nrows` rows: all of them when they fit DUMP_FACTOR_BYTES, otherwise a fixed
+    seeded uniform sample (sorted) of as many rows as fit."""
+    cap = max(1, DUMP_FACTOR_BYTES // row_bytes)
+    if nrows <= cap:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(nrows, size=cap, replace=False))
+
+
+def dump_outputs(eng, out_dir):
+    """What `ALS` exports to its caller after the last iteration (_Engine.export: U, V, b_u, b_i, mu, W per
+    feature, the per-iteration history) as out_dir/<name>.npy in the engine's float32 / float64.  U / b_u and
+    V / b_i share one row sample per side when a side is larger than DUMP_FACTOR_BYTES (`_row_sample`).
+    Returns ({name: shape}, {side: how its rows were sampled})."""
+    os.makedirs(out_dir, exist_ok=True)
+    k = eng.k
+    out, rows = {}, {}
+    for side, F, b, nrows, seed in (("U", eng.U, eng.b_u, eng.m, 5001), ("V", eng.V, eng.b_i, eng.n, 5002)):
+        idx = _row_sample(nrows, k * F.element_size(), seed)
+        if idx is None:
+            out[side], out["b_u" if side == "U" else "b_i"] = F[:nrows, :k], b[:nrows]
+        else:
+            it = torch.from_numpy(idx).to(F.device)
+            out[side], out["b_u" if side == "U" else "b_i"] = F[it, :k], b[it]
+            rows[side] = f"{idx.size} of {nrows} rows, np.random.default_rng({seed}).choice(replace=False), sorted"
+    out["mu"] = eng.mu.reshape(1)
+    for f in eng.feat_names:
+        out["W_" + f] = eng.W64[f]
+    out["history"] = eng.hist[: eng.iters_run, :5]     # train_rmse, U_norm, V_norm, bu_norm, bi_norm
+    shapes, total = {}, 0
+    for name, t in out.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        a = np.ascontiguousarray(a)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    assert total <= 64_000_000, f"dump of {total} bytes is over 64 MB"
+    return shapes, rows
+
+
 def frac_iter_of(size, nnz, elapsed_per_step):
     """[2 (4k+12) N + (m+n)(4k+12)] / t_iter as a fraction of 8 TB/s."""
     m, n, _, k = SIZES[size]
@@ -370,8 +421,14 @@ def main(argv=None, *, backend=None, device=None):
     ap.add_argument("--size", default="cfg4", choices=sorted(SIZES))
     ap.add_argument("--gs-mode", default=None, choices=[None, "exact", "block", "levels"],
                     help="Laplacian sweep with several ranks: exact (default; shards in rank order), block, levels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary cases (N = 1, cfg4 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline and the secondary cases (N = 1, "
+                         "cfg4 only); a plain run times the headline workload and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary cases")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the fit returns (U, V, b_u, b_i, mu, W, history; seeded "
+                         "row samples of sides over 28 MiB) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
     ap.add_argument("--no-graph", action="store_true", help="debug only; not a valid headline run")
     ap.add_argument("--hip-graph", action="store_true",
                     help="replay iterations as captured HIP graphs (no per-phase timing; for launch-bound sizes)")
@@ -426,6 +483,7 @@ def main(argv=None, *, backend=None, device=None):
     res = run_case(args.size, inputs, dev, steps=args.steps, warmup=args.warmup, dist_on=dist_on, gs_mode=args.gs_mode,
                    gram=args.gram, hip_graph=args.hip_graph, solve_dtype=args.solve_dtype, backend=backend)
     eng, elapsed, phase, hist, t_setup = res["eng"], res["elapsed"], res["phase"], res["hist"], res["setup_s"]
+    dumped = dump_outputs(eng, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
@@ -521,11 +579,13 @@ def main(argv=None, *, backend=None, device=None):
             else:
                 out["config"]["scaling_cap"] = {"mode": "exact", "note": "the sweep's dependency chain does not shrink "
                                                 "with N; see the N = 1 line for the bound"}
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped[0], "sampled_rows": dumped[1]}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(eng)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        if (world == 1 and not dist_on and args.size == "cfg4" and not args.no_secondary and not args.hip_graph
-                and args.solve_dtype == "auto" and backend is None):
+        if (args.full and world == 1 and not dist_on and args.size == "cfg4" and not args.no_secondary
+                and not args.hip_graph and args.solve_dtype == "auto" and backend is None):
             # other shapes / the reference's arithmetic type, in the driver's record as well (each a few seconds):
             # same code path, fewer steps; ms_per_step and the SURVEY 8(d) iteration fraction
             del res, eng
