@@ -20,7 +20,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_row_solve", "als_factor_scale", "als_gs_sweep", "als_gs_sweep_levels", "als_gs_sweep_dataflow", "als_residual_stats", "als_w_normal_equations", "als_spd_solve_workspace_bytes", "als_spd_solve_f64", "als_item_stats", "als_item_stats_f64", "als_sum_pairs", "als_sumsq_partials",
            "als_sumsq", "als_history_row", "als_compose_z", "als_predict_at", "als_predict_dense",
            "als_topk_similarity", "als_graph_classify", "als_normalize_features", "als_impute_col_median",
-           "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule")
+           "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
+           "als_recommend_workspace_bytes", "als_recommend_topk")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -116,6 +117,9 @@ def load():
     lib.als_predict_at.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_predict_dense.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_topk_similarity.argtypes = [_i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
+    lib.als_recommend_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
+    lib.als_recommend_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]
@@ -123,8 +127,10 @@ def load():
     lib.als_host_row_tasks.argtypes = [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
     lib.als_host_level_schedule.argtypes = [_i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
     for name in EXPORTS:
-        if name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64", "als_spd_solve_workspace_bytes"):
+        if name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64", "als_spd_solve_workspace_bytes",
+                        "als_recommend_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     lib.als_spd_solve_workspace_bytes.restype = C.c_size_t
+    lib.als_recommend_workspace_bytes.restype = C.c_size_t
     _lib = lib
     return lib

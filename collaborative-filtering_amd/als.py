@@ -31,6 +31,7 @@ from .als_config import ALSConfig
 
 SCALE_FACTOR = 0.1      # scripts/als.py:93
 EPS = 1e-10             # scripts/als.py:94
+RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
 W_F64_BELOW = 1e-2      # solve_dtype="auto": fp64 V-step by-products when some lambda_w (+ 1e-10) is below this
 
 logger = logging.getLogger(__name__)
@@ -420,6 +421,39 @@ class ALS:
         features = self._check_predict(features)
         with _on(self._eng.dev):
             return self._eng.predict_at(np.asarray(flat_idx, dtype=np.int64), features)
+
+    def recommend(self, users=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                  exclude_seen: bool = True):
+        """Top-N items per user: returns (items int64 [B, N], scores float64 [B, N]), each row ordered by score
+        descending, ties to the lower item index.
+
+        `users`: None = all m users in id order, else a 1-D array-like of user ids in [0, m) (order and duplicates
+        kept).  `features` is handled as in `predict`.  With `exclude_seen` the items rated in the ratings of the
+        last fit are never returned (under sweep.SweepDriver: the fold's training ratings).  Slots beyond the
+        number of candidate items hold item -1 and score -inf.  NaN scores are never returned.
+
+        Contract: scores[b, j] == predict(features)[users[b], items[b, j]] exactly, and no item outside the
+        returned list scores higher (or equal with a lower index) than items[b, N - 1], seen items aside.
+        Nothing m x n is formed: one fused kernel scores and selects (als_recommend_topk).  On a sharded fit the
+        call is local to the calling rank (no collective)."""
+        features = self._check_predict(features)
+        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= N <= RECOMMEND_MAX_N:
+            raise ValueError(f"N must be an integer in [1, {RECOMMEND_MAX_N}], got {N!r}")
+        N = int(N)
+        m = self.U.shape[0]
+        if users is None:
+            u = np.arange(m, dtype=np.int64)
+        else:
+            u = np.asarray(users)
+            if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
+                raise ValueError("users must be a 1-D array-like of integer user ids")
+            if u.size and (u.min() < 0 or u.max() >= m):
+                raise IndexError(f"user ids must lie in [0, {m})")
+        if u.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
+            return self._eng.recommend(us, N, features, exclude_seen)
 
 
 class _Engine:
@@ -1149,6 +1183,33 @@ class _Engine:
         us = torch.from_numpy(u.astype(np.int32)).to(self.dev)
         is_ = torch.from_numpy(i.astype(np.int32)).to(self.dev)
         return self.predict_pairs(us, is_, features).cpu().numpy().astype(np.float64)
+
+    REC_BATCH = 1 << 16     # users per als_recommend_topk call: bounds the outputs and the item-slice workspace
+
+    def recommend(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool):
+        """Top-N items of the users in `users_t` (int32, device): (items int64 [B, N], scores float64 [B, N]),
+        unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit.
+        Local to the calling rank: after the all-gathers every rank holds the full U, Z, biases and training CSR,
+        so no collective is issued."""
+        Z = self._compose_for(features)
+        seen_ptr = seen_idx = None
+        if exclude_seen and self.nnz > 0:
+            seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
+        B = users_t.numel()
+        items = np.empty((B, N), dtype=np.int64)
+        scores = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            us = users_t[b0: b0 + self.REC_BATCH]
+            nb = us.numel()
+            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.recommend_topk(k=self.k, ld=self.ld, users=us, n=self.n, U=self.U, Z=Z, b_u=self.b_u,
+                                   b_i=self.b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
+                                   top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
+            items[b0: b0 + nb] = top_idx.cpu().numpy()
+            scores[b0: b0 + nb] = top_val.cpu().numpy()
+        return items, scores
 
     def predict_pairs(self, us: torch.Tensor, is_: torch.Tensor, features, features_of_fit: bool = False) -> torch.Tensor:
         """Predictions at (user, item) index tensors already on the device (int32); fp32 device tensor."""

@@ -47,6 +47,7 @@ class HipBackend:
                                            device=device)
         self._stats_partials: Optional[torch.Tensor] = None
         self._spd_ws: Optional[torch.Tensor] = None
+        self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -284,3 +285,24 @@ class HipBackend:
     def predict_dense(self, *, k, ld, m, n, U, Z, b_u, b_i, mu, out):
         self._check(self.lib.als_predict_dense(k, ld, m, n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu),
                                                _p(out), self._stream()), "als_predict_dense")
+
+    @staticmethod
+    def recommend_slices() -> int:
+        # item slices of als_recommend_topk: 0 = automatic; ALS_RECOMMEND_SLICES forces a count (tests: the result
+        # must not depend on it)
+        return int(os.environ.get("ALS_RECOMMEND_SLICES", "0"))
+
+    def recommend_topk(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx,
+                       top_cnt):
+        """Top-`topn` items of every user in `users` (int32), seen items (CSR by user id; None = none) left out:
+        als_recommend_topk.  The item-slice workspace is owned here and grows as needed."""
+        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
+            seen_ptr = seen_idx = None
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_recommend_workspace_bytes(users.numel(), n, topn, nsl))
+        if need > 0 and (self._rec_ws is None or self._rec_ws.numel() < need):
+            self._rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_recommend_topk(k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i),
+                                                _p(mu), _p(seen_ptr), _p(seen_idx), topn, nsl, _p(top_val),
+                                                _p(top_idx), _p(top_cnt), _p(self._rec_ws) if need > 0 else None, need,
+                                                self._stream()), "als_recommend_topk")

@@ -20,60 +20,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "als_hip.h"
+#include "topk_common.hpp"
 
 namespace {
+
+using topk::enc_f32;
+using topk::dec_f32;
+using topk::sort256_desc;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TK_MAX = ALS_TOPK_MAX;      // longest list
 constexpr int TK_BUF = 128;               // survivors buffered per row between compactions
 constexpr int TK_CAP = TK_MAX + TK_BUF;   // 256 keys of 8 bytes per row: 32 KB per wave
-
-__device__ __forceinline__ unsigned enc_f32(float s) {
-    const unsigned b = __float_as_uint(s + 0.0f);                 // -0.0 -> +0.0
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
-    const unsigned lo = __shfl_xor((unsigned)v, m, 64), hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// 256 keys, 4 per lane (element i = lane + 64 v), sorted DESCENDING by a bitonic network
-__device__ __forceinline__ void sort256_desc(unsigned long long (&k)[4], int lane) {
-#pragma unroll
-    for (int size = 2; size <= 256; size <<= 1) {
-#pragma unroll
-        for (int j = size >> 1; j >= 1; j >>= 1) {
-            if (j >= 64) {
-                const int dv = j >> 6;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    if ((v & dv) == 0) {
-                        const int i = lane + 64 * v;
-                        const bool desc = (i & size) == 0;
-                        const unsigned long long a = k[v], b = k[v | dv];
-                        const bool sw = desc ? (a < b) : (a > b);
-                        k[v] = sw ? b : a;
-                        k[v | dv] = sw ? a : b;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int i = lane + 64 * v;
-                    const bool desc = (i & size) == 0;
-                    const bool lower = (i & j) == 0;                       // this element is the lower index of the pair
-                    const unsigned long long o = shfl_xor_u64(k[v], j);
-                    const bool take_max = (lower == desc);
-                    k[v] = take_max ? (k[v] > o ? k[v] : o) : (k[v] < o ? k[v] : o);
-                }
-            }
-        }
-    }
-}
 
 template <int NS>
 __global__ __launch_bounds__(64)

@@ -1,0 +1,355 @@
+// K8: top-N recommendation - score(u, i) = U_u.Z_i + mu + b_u + b_i over all items, the user's seen items left
+// out, the N best kept per user - without forming the m x n completion.
+//
+// k_recommend: one workgroup serves NW * 16 users (one 16-user tile per wave) over the items [lo, hi) of one slice.
+// The items are walked in chunks of 32: the workgroup stages the chunk's Z rows in LDS once (global loads of the
+// next chunk are in flight while the current one is scored), and every wave forms its two 16 x 16 score tiles with
+// the SAME v_mfma_f32_16x16x4_f32 chain and epilogue as k_predict_dense (lane (c, q) holds k = 4KB q + e of user
+// row c and item row c in step e; ((acc + mu) + b_u) + b_i), so every score is bitwise the value
+// als_predict_dense writes.  Z is therefore read from L2 / MALL once per NW * 16 users.
+//
+// Selection is k_topk_sim's (topk_common.hpp): each candidate is a 64-bit key ordered by (score desc, item asc);
+// a candidate above its row's threshold (the current N-th key) is appended - ballot + prefix popcount - to the
+// row's survivor buffer in LDS, and a row whose buffer could overflow is compacted by a bitonic sort of
+// (list + buffer).  Seen items never reach a buffer: each row keeps a cursor into its ascending seen list and the
+// next seen item; only a chunk that reaches that item builds a 16-bit seen mask for the block (one coalesced load
+// of the next 16 seen entries by the row's 16 lanes and an OR-reduction).
+//
+// Item split: with few users (a batch of 1 ... 1000 fills a fraction of the CUs) the item range is cut into
+// nslices slices (grid.y); each workgroup writes its per-(slice, user) list as raw keys to the workspace, and
+// k_recommend_merge merges the lists of every user with the same 256-key sort.  The order is total, so the
+// result does not depend on the slice count.
+#include "als_device.hpp"
+#include "als_hip.h"
+#include "topk_common.hpp"
+
+namespace {
+
+using topk::key_index;
+using topk::key_score;
+using topk::make_key;
+
+constexpr int RC_CHUNK = 32;        // items per staged chunk: two 16-item score tiles per wave
+constexpr int RC_WIDE = 64;         // users per workgroup, topn > 32: 4 waves, 256 keys per user (list 128)
+constexpr int RC_NARROW = 128;      // users per workgroup, topn <= 32: 8 waves, 128 keys per user (list 32)
+constexpr int RC_MIN_SLICE = 2048;  // automatic slicing keeps at least this many items per slice
+
+__device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
+
+// CAP keys per user: list [0, L) + survivor buffer [L, CAP)
+template <int KB, int NW, int CAP>
+__global__ __launch_bounds__(NW * 64)
+void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t n, int64_t slice,
+                 const float* __restrict__ U, const float* __restrict__ Z, const float* __restrict__ b_u,
+                 const float* __restrict__ b_i, const double* __restrict__ mu_p,
+                 const int64_t* __restrict__ seen_ptr, const int32_t* __restrict__ seen_idx, int topn,
+                 float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt,
+                 unsigned long long* __restrict__ part) {
+    constexpr int E = 4 * KB, LD = 16 * KB, ZS = LD + 4;        // LDS row stride: +16 B spreads lanes c over the banks
+    constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
+    constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
+    static_assert(L >= 32 && BUF >= 64, "a chunk appends up to 32 keys per row");
+    __shared__ unsigned long long keys[NW * 16][CAP];
+    __shared__ __attribute__((aligned(16))) float zs[RC_CHUNK][ZS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, q = lane >> 4;
+    const float mu = (float)(*mu_p);
+    const int64_t b0 = ((int64_t)blockIdx.x * NW + wave) * 16;            // first batch row of this wave
+    const int64_t lo = (int64_t)blockIdx.y * slice, hi = min(n, lo + slice);
+    unsigned long long (*kw)[CAP] = keys + wave * 16;
+
+    float ua[E];
+    load_frow<E>(U + (size_t)users[min(b0 + c, nusers - 1)] * ld + E * q, ua);
+    float bu[4];
+    bool valid[4];
+    int64_t cur[4], end[4];
+    int nxt[4];                                                          // next seen item of rows 4q + r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t rb = b0 + 4 * q + r;
+        valid[r] = rb < nusers;
+        const int u = users[min(rb, nusers - 1)];
+        bu[r] = b_u[u];
+        cur[r] = end[r] = 0;
+        if (seen_ptr && valid[r]) {
+            int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
+            end[r] = e;
+            while (a < e) {                                              // first seen item >= lo
+                const int64_t mid = a + ((e - a) >> 1);
+                if (seen_idx[mid] < lo) a = mid + 1; else e = mid;
+            }
+            cur[r] = a;
+        }
+        nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+    }
+    unsigned long long thr[4] = {0ull, 0ull, 0ull, 0ull};    // key of the current topn-th entry (0: list not full)
+    int cnt[4] = {0, 0, 0, 0};                                // buffered survivors (same in the 16 lanes of a q group)
+    int nlist[4] = {0, 0, 0, 0};                              // valid entries of the sorted list
+
+    auto compact = [&](int r) {        // wave-uniform r: list + buffer of row r -> sorted list, new threshold
+        const int rq = r >> 2, re = r & 3;
+        int rc = 0, rn = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { rc = (re == e) ? cnt[e] : rc; rn = (re == e) ? nlist[e] : rn; }
+        rc = readlane_i(rc, 16 * rq);
+        rn = readlane_i(rn, 16 * rq);
+        unsigned long long k[CAP / 64];
+#pragma unroll
+        for (int v = 0; v < CAP / 64; ++v) {
+            const int i = lane + 64 * v;
+            const bool live = (i < rn) || (i >= L && i < L + rc);
+            k[v] = live ? kw[r][i] : 0ull;
+        }
+        topk::sort_desc<CAP / 64>(k, lane);
+#pragma unroll
+        for (int v = 0; v < CAP / 64; ++v)
+            if (lane + 64 * v < L) kw[r][lane + 64 * v] = k[v];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const int nn = min(topn, rn + rc);
+        const unsigned long long t = (nn == topn) ? kw[r][topn - 1] : 0ull;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (q == rq && e == re) { thr[e] = t; cnt[e] = 0; nlist[e] = nn; }
+    };
+
+    // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold test, append
+    auto select = [&](const f32x4& acc, int64_t cb) {
+        unsigned msk[4] = {0u, 0u, 0u, 0u};
+        bool near = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) near = near || nxt[r] < cb + 16;
+        if (__ballot(near)) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                bool more = nxt[r] < cb + 16;                            // same in the 16 lanes of the q group
+                const bool touched = more;
+                while (__ballot(more)) {
+                    int s = INT32_MAX;
+                    if (more) {
+                        const int64_t p = cur[r] + c;
+                        s = p < end[r] ? seen_idx[p] : INT32_MAX;
+                    }
+                    const bool below = more && s < cb + 16;
+                    unsigned bit = (below && s >= cb) ? 1u << (int)(s - cb) : 0u;
+                    bit |= __shfl_xor(bit, 1, 64);
+                    bit |= __shfl_xor(bit, 2, 64);
+                    bit |= __shfl_xor(bit, 4, 64);
+                    bit |= __shfl_xor(bit, 8, 64);
+                    msk[r] |= bit;
+                    const int adv = __popc((unsigned)(__ballot(below) >> (16 * q)) & 0xFFFFu);
+                    cur[r] += adv;
+                    more = more && adv == 16;                            // 16 consumed: there may be more in the block
+                }
+                if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+            }
+        }
+        const int64_t col = cb + c;
+        const float bi = b_i[min(col, n - 1)];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float score = acc[r] + mu + bu[r] + bi;
+            const unsigned long long key = make_key(score, (unsigned)col);
+            const bool pass = col < hi && valid[r] && !((msk[r] >> c) & 1u) && score == score && key > thr[r];
+            const unsigned long long m = __ballot(pass);
+            const unsigned sub = (unsigned)(m >> (16 * q)) & 0xFFFFu;
+            if (pass) kw[4 * q + r][L + cnt[r] + __popc(sub & ((1u << c) - 1u))] = key;
+            cnt[r] += __popc(sub);
+        }
+    };
+
+    f32x4 pf[PF];
+    auto fetch = [&](int64_t it0) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const int v = tid + p * NT;
+            if (v < NV) {
+                const int i = v / (LD / 4), d = v - i * (LD / 4);
+                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
+            }
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const int v = tid + p * NT;
+            if (v < NV) {
+                const int i = v / (LD / 4), d = v - i * (LD / 4);
+                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
+            }
+        }
+    };
+
+    const int64_t nch = hi > lo ? (hi - lo + RC_CHUNK - 1) / RC_CHUNK : 0;
+    if (nch > 0) fetch(lo);
+    for (int64_t ch = 0; ch < nch; ++ch) {
+        const int64_t it0 = lo + ch * RC_CHUNK;
+        __syncthreads();                                 // every wave is done with the previous chunk
+        stage();
+        __syncthreads();
+        if (ch + 1 < nch) fetch(it0 + RC_CHUNK);
+        float z0[E], z1[E];
+        load_frow<E>(&zs[c][E * q], z0);
+        load_frow<E>(&zs[16 + c][E * q], z1);
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
+        }
+        select(acc0, it0);
+        select(acc1, it0 + 16);
+        bool full = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) full = full || cnt[r] > BUF - RC_CHUNK;
+        if (__ballot(full)) {                            // some row's buffer could overflow in the next chunk
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            for (int r = 0; r < 16; ++r) {
+                int rc = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
+                rc = readlane_i(rc, 16 * (r >> 2));
+                if (rc > BUF - RC_CHUNK) compact(r);
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    for (int r = 0; r < 16; ++r) {
+        int rc = 0, rn = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
+        rc = readlane_i(rc, 16 * (r >> 2));
+        if (rc > 0) compact(r);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rn = ((r & 3) == e) ? nlist[e] : rn;
+        rn = readlane_i(rn, 16 * (r >> 2));
+        const int64_t rb = b0 + r;
+        if (rb >= nusers) continue;
+        if (part) {                                      // sliced: raw keys of (slice, user), 0 = empty
+            unsigned long long* dst = part + ((int64_t)blockIdx.y * nusers + rb) * topn;
+            for (int t = lane; t < topn; t += 64) dst[t] = t < rn ? kw[r][t] : 0ull;
+        } else {
+            for (int t = lane; t < topn; t += 64) {
+                const bool ok = t < rn;
+                const unsigned long long key = ok ? kw[r][t] : 0ull;
+                top_val[rb * topn + t] = ok ? key_score(key) : -INFINITY;
+                top_idx[rb * topn + t] = ok ? key_index(key) : -1;
+            }
+            if (lane == 0) top_cnt[rb] = rn;
+        }
+    }
+}
+
+// one wave per user: the nslices lists of (at most topn <= 128) keys folded into one by 256-key sorts
+__global__ __launch_bounds__(256)
+void k_recommend_merge(int64_t nusers, int nslices, int topn, const unsigned long long* __restrict__ part,
+                       float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= nusers) return;                             // wave-uniform
+    unsigned long long k[4];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const int i = lane + 64 * v;
+        k[v] = i < topn ? part[b * topn + i] : 0ull;
+    }
+    for (int s = 1; s < nslices; ++s) {
+        const unsigned long long* src = part + ((int64_t)s * nusers + b) * topn;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            const int i = lane + 64 * v;
+            k[2 + v] = i < topn ? src[i] : 0ull;
+        }
+        topk::sort256_desc(k, lane);                     // elements 0 ... 127 (k[0], k[1]) hold the best 128
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const int i = lane + 64 * v;
+        const bool ok = i < topn && k[v] != 0ull;
+        cnt += __popcll(__ballot(ok));
+        if (i < topn) {
+            top_val[b * topn + i] = ok ? key_score(k[v]) : -INFINITY;
+            top_idx[b * topn + i] = ok ? key_index(k[v]) : -1;
+        }
+    }
+    if (lane == 0) top_cnt[b] = cnt;
+}
+
+int rec_slices(int64_t nusers, int64_t n, int topn, int nslices) {
+    const int64_t ub = topn <= 32 ? RC_NARROW : RC_WIDE;
+    const int64_t ublocks = (nusers + ub - 1) / ub;
+    int64_t s = nslices;
+    if (s == 0) {                                        // aim at two workgroups per CU, >= RC_MIN_SLICE items each
+        s = (512 + ublocks - 1) / ublocks;
+        s = min(s, (n + RC_MIN_SLICE - 1) / RC_MIN_SLICE);
+    }
+    s = min(s, (int64_t)ALS_RECOMMEND_MAX_SLICES);
+    s = min(s, (n + RC_CHUNK - 1) / RC_CHUNK);            // every slice at least one chunk
+    return (int)max(s, (int64_t)1);
+}
+
+template <int KB>
+int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
+                     const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
+                     const int32_t* seen_idx, int topn, float* tv, int32_t* ti, int32_t* tc,
+                     unsigned long long* part, hipStream_t st) {
+    // slice length: a whole number of chunks, so every slice but the last is full
+    const int64_t nchunks = (n + RC_CHUNK - 1) / RC_CHUNK;
+    const int64_t slice = (nchunks + nsl - 1) / nsl * RC_CHUNK;
+    if (topn <= 32) {
+        const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
+        hipLaunchKernelGGL((k_recommend<KB, RC_NARROW / 16, 128>), grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users,
+                           n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part);
+    } else {
+        const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
+        hipLaunchKernelGGL((k_recommend<KB, RC_WIDE / 16, 256>), grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users,
+                           n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" size_t als_recommend_workspace_bytes(int64_t nusers, int64_t n, int topn, int nslices) {
+    if (nusers <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
+    const int s = rec_slices(nusers, n, topn, nslices);
+    return s > 1 ? (size_t)s * (size_t)nusers * (size_t)topn * sizeof(unsigned long long) : 0;
+}
+
+extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                                  const float* Z, const float* b_u, const float* b_i, const double* mu,
+                                  const int64_t* seen_ptr, const int32_t* seen_idx, int topn, int nslices,
+                                  float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    const int kp = als_padded_k(k);
+    if (kp < 0) return ALS_E_BADK;
+    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
+        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES)
+        return ALS_E_BADARG;
+    if (nusers == 0) return 0;
+    if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx))
+        return ALS_E_BADARG;
+    const int nsl = rec_slices(nusers, n, topn, nslices);
+    const size_t need = als_recommend_workspace_bytes(nusers, n, topn, nslices);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
+    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+#define ALS_RC_CASE(KB) \
+    case KB: rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, \
+                                       top_val, top_idx, top_cnt, part, st); break;
+    switch (ld / 16) {
+        ALS_RC_CASE(1) ALS_RC_CASE(2) ALS_RC_CASE(3) ALS_RC_CASE(4) ALS_RC_CASE(5)
+        ALS_RC_CASE(6) ALS_RC_CASE(7) ALS_RC_CASE(8) ALS_RC_CASE(9) ALS_RC_CASE(10)
+        default: return ALS_E_BADK;
+    }
+#undef ALS_RC_CASE
+    if (rc != 0 || nsl == 1) return rc;
+    hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
+                       top_val, top_idx, top_cnt);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}

@@ -12,6 +12,7 @@ schema, so that results can be compared file by file:
   split        train_valid_split                                        create_folds.py:152-208
   metrics      rmse_at, popularity_bins, split_by_popularity            tune_params.py:147-167,
                                                                         evaluate_models.py:131-191
+               ranking_at_k (recall@K / NDCG@K of ALS.recommend)        new: the reference has RMSE only
   statistics   aggregate_convergence, aggregate_bins_mean,              evaluate_models.py:279-379
                sign_test_paired, fdr_bh
   variants     variant_grid                                             evaluate_models.py:382-455
@@ -116,6 +117,43 @@ def rmse_at(y_true: np.ndarray, y_pred: np.ndarray) -> float:
     if np.size(y_true) == 0:
         return float("nan")
     return float(np.sqrt(np.mean((np.asarray(y_true) - np.asarray(y_pred)) ** 2)))
+
+
+def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
+                 features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+    """recall@K and NDCG@K of `model.recommend` on held-out (user, item) pairs (new: the reference evaluates RMSE
+    only).  For every user u of the held-out set:
+
+      rel(u)       = {i : (u, i) held out, and vals >= min_rating unless min_rating is None}
+      top(u)       = model.recommend([u], K, features=features) - the training items of the fit excluded
+      recall@K(u)  = |top(u) & rel(u)| / |rel(u)|
+      DCG@K(u)     = sum over ranks r = 1 .. K of [top_r(u) in rel(u)] / log2(r + 1)     (binary gains)
+      NDCG@K(u)    = DCG@K(u) / IDCG@K(u),  IDCG@K(u) = sum over r = 1 .. min(K, |rel(u)|) of 1 / log2(r + 1)
+
+    Users with an empty rel(u) are left out; the result holds the means over the others:
+    {"users": their number, "recall@K": mean recall, "ndcg@K": mean NDCG} (NaN means when no user is left)."""
+    rows = np.asarray(rows, dtype=np.int64).ravel()
+    cols = np.asarray(cols, dtype=np.int64).ravel()
+    if rows.shape != cols.shape:
+        raise ValueError("rows and cols must have the same length")
+    if min_rating is not None:
+        if vals is None:
+            raise ValueError("min_rating needs the held-out ratings (vals)")
+        keep = np.asarray(vals, dtype=np.float64).ravel() >= min_rating
+        rows, cols = rows[keep], cols[keep]
+    users, ub = np.unique(rows, return_inverse=True)
+    if users.size == 0:
+        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan")}
+    n = int(max(model.V.shape[0], cols.max() + 1))
+    rel = np.unique(ub * n + cols)                                      # (user position, item), duplicates merged
+    nrel = np.bincount(rel // n, minlength=users.size)
+    items, _ = model.recommend(users, K, features=features)
+    hit = (items >= 0) & np.isin(np.arange(users.size)[:, None] * n + items, rel)
+    disc = 1.0 / np.log2(np.arange(2, K + 2, dtype=np.float64))         # rank r = 1 .. K
+    dcg = (hit * disc).sum(axis=1)
+    idcg = np.cumsum(disc)[np.minimum(nrel, K) - 1]
+    return {"users": int(users.size), "recall@K": float(np.mean(hit.sum(axis=1) / nrel)),
+            "ndcg@K": float(np.mean(dcg / idcg))}
 
 
 def popularity_bins(item_counts: np.ndarray, n_bins: int = N_POP_BINS,

@@ -388,6 +388,28 @@ int als_graph_classify(int64_t n, int topk, const float* top_val, const int32_t*
                        const int32_t* top_cnt, uint8_t* own, uint8_t* mirror, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Top-N recommendation.  For every batch row b (user u = users[b], in [0, m); duplicates allowed):
+ *   score(u, i) = U_u.Z_i + mu + b_u + b_i - bitwise the fp32 value als_predict_dense writes at (u, i) -
+ *   over all items i < n that are not in u's seen row (seen_ptr [m+1] / seen_idx: a CSR indexed by USER ID,
+ *   column indices ascending within each row; both NULL = exclude nothing).  NaN scores are never returned.
+ *   top_val / top_idx [nusers][topn], ordered by (score descending, item ascending) - among equal scores the
+ *   LOWEST item indices win; unused slots: top_idx -1, top_val -inf; top_cnt [nusers] = number of valid slots.
+ *   1 <= topn <= ALS_TOPK_MAX, n < 2^31; nusers == 0 is a no-op.
+ * nslices: 0 = automatic, otherwise the number of item slices (<= ALS_RECOMMEND_MAX_SLICES, at most one per 32
+ *   items) the item range is cut into, each slice's lists merged by a second launch; the result does not depend on
+ *   it (an override for tests and measurements).
+ * workspace: als_recommend_workspace_bytes(nusers, n, topn, nslices) bytes of device memory (0: may be NULL);
+ *   the call allocates nothing.
+ * ------------------------------------------------------------------------- */
+#define ALS_RECOMMEND_MAX_SLICES 64
+size_t als_recommend_workspace_bytes(int64_t nusers, int64_t n, int topn, int nslices);
+int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                       const float* Z, const float* b_u, const float* b_i, const double* mu,
+                       const int64_t* seen_ptr, const int32_t* seen_idx, int topn, int nslices,
+                       float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
