@@ -145,6 +145,50 @@ def _validate_graph(ptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, n: 
                          "symmetrise with max(S, S^T) as the reference does")
 
 
+def fold_in_csr(R_new, n: int):
+    """Ratings of users outside the fit -> host CSR (indptr int64 [B+1], indices int32, vals float32), every row's
+    columns ascending (values carried along).  `R_new`: a dense (B, n) array with NaN for missing ratings, or a CSR
+    triple (indptr, indices, vals) in any column order.  Raises ValueError for a wrong dense width, a malformed
+    triple, a duplicate column in a row or a non-finite rating, IndexError for a column outside [0, n)."""
+    if isinstance(R_new, (tuple, list)) and len(R_new) == 3 and not np.isscalar(R_new[0]) and np.ndim(R_new[0]) == 1:
+        indptr = np.asarray(R_new[0])
+        indices = np.asarray(R_new[1])
+        vals = np.asarray(R_new[2])
+        if (indptr.ndim != 1 or indptr.size < 1 or indices.ndim != 1 or vals.ndim != 1
+                or (indptr.size and not np.issubdtype(indptr.dtype, np.integer))
+                or (indices.size and not np.issubdtype(indices.dtype, np.integer))):
+            raise ValueError("R_new as CSR must be 1-D (indptr, indices, vals) with integer indptr / indices")
+        indptr = indptr.astype(np.int64)
+        if (indptr[0] != 0 or (np.diff(indptr) < 0).any() or indptr[-1] != indices.size
+                or indices.size != vals.size):
+            raise ValueError("R_new: indptr must start at 0, not decrease, and end at len(indices) == len(vals)")
+        indices = indices.astype(np.int64)
+        if indices.size and (indices.min() < 0 or indices.max() >= n):
+            raise IndexError(f"R_new: column indices must lie in [0, {n})")
+        vals = vals.astype(np.float64)
+    else:
+        R = np.asarray(R_new, dtype=np.float64)
+        if R.ndim != 2 or R.shape[1] != n:
+            raise ValueError(f"R_new must be a dense (B, {n}) array (NaN = missing) or a CSR triple, "
+                             f"got shape {R.shape}")
+        mask = ~np.isnan(R)
+        indptr = np.zeros(R.shape[0] + 1, dtype=np.int64)
+        np.cumsum(mask.sum(axis=1), out=indptr[1:])
+        indices = np.nonzero(mask)[1].astype(np.int64)
+        vals = R[mask]
+    with np.errstate(over="ignore"):
+        vals32 = vals.astype(np.float32)
+    if not np.isfinite(vals32).all():
+        raise ValueError("R_new contains non-finite ratings (or ones beyond the float32 range)")
+    B = indptr.size - 1
+    row = np.repeat(np.arange(B, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((indices, row))
+    indices, vals32 = indices[order], vals32[order]
+    if indices.size > 1 and ((np.diff(indices) == 0) & (np.diff(row) == 0)).any():
+        raise ValueError("R_new has a duplicate column within a row")
+    return indptr, indices.astype(np.int32), vals32
+
+
 def _on(device):
     """Make `device` the current HIP device for the enclosed calls: the C-ABI library launches on the current
     device (and sizes its persistent grids from that device's occupancy), torch only hands it a stream."""
@@ -454,6 +498,51 @@ class ALS:
         with _on(self._eng.dev):
             us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
             return self._eng.recommend(us, N, features, exclude_seen)
+
+    @staticmethod
+    def _check_sweeps(n_sweeps) -> int:
+        if n_sweeps is None:
+            return 0
+        if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, (int, np.integer)) or not 1 <= n_sweeps < 2 ** 31:
+            raise ValueError(f"n_sweeps must be None (fixed point) or an integer >= 1, got {n_sweeps!r}")
+        return int(n_sweeps)
+
+    def fold_in(self, R_new, *, features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None):
+        """Factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed: returns
+        (U_new float64 [B, k], b_u_new float64 [B]), the fp32 values of the device tables (as `U` after a fit).
+
+        `R_new`: a dense (B, n) array with NaN for missing ratings (the format of `fit`), or a CSR triple
+        (indptr, indices, vals) - columns in any order within a row, no duplicates.  `features` is handled as in
+        `predict` (it decides Z).  `n_sweeps` = T: the fit's user half-step (scripts/als.py:411-433) T times from
+        b_u = 0; None: its fixed point, the joint minimiser of the user's ridge objective.  A user without ratings
+        gets zero factors and bias.  Each row's result depends only on that row's ratings, bitwise.  Local to the
+        calling rank."""
+        features = self._check_predict(features)
+        T = self._check_sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        k, B = self.V.shape[1], indptr.size - 1
+        if B == 0:
+            return np.empty((0, k), dtype=np.float64), np.empty(0, dtype=np.float64)
+        with _on(self._eng.dev):
+            U, b = self._eng.fold_in(indptr, indices, vals, features, T)
+            return U[:, :k].to(torch.float64).cpu().numpy(), b.to(torch.float64).cpu().numpy()
+
+    def recommend_new(self, R_new, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                      n_sweeps: Optional[int] = None, exclude_seen: bool = True):
+        """Top-N items for users outside the fit: `fold_in(R_new, features=features, n_sweeps=n_sweeps)`, then
+        the contract of `recommend` on the folded factors - (items int64 [B, N], scores float64 [B, N]), every
+        score bitwise the predict epilogue U_b.Z_i + mu + b_b + b_i of the folded row; with `exclude_seen` the
+        items rated in R_new are never returned.  The folded factors stay on the device."""
+        features = self._check_predict(features)
+        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= N <= RECOMMEND_MAX_N:
+            raise ValueError(f"N must be an integer in [1, {RECOMMEND_MAX_N}], got {N!r}")
+        N = int(N)
+        T = self._check_sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        if indptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen)
 
 
 class _Engine:
@@ -1207,6 +1296,57 @@ class _Engine:
             self.be.recommend_topk(k=self.k, ld=self.ld, users=us, n=self.n, U=self.U, Z=Z, b_u=self.b_u,
                                    b_i=self.b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
                                    top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
+            items[b0: b0 + nb] = top_idx.cpu().numpy()
+            scores[b0: b0 + nb] = top_val.cpu().numpy()
+        return items, scores
+
+    def _fold_in_dev(self, indptr: np.ndarray, indices: np.ndarray, vals: np.ndarray, Z, n_sweeps: int):
+        """Folded factors (fp32 [B, ld], zero padding columns) and biases (fp32 [B]) on the device, with the
+        device CSR they were computed from (one als_fold_in launch)."""
+        md = self.model
+        B = indptr.size - 1
+        ptr_d = torch.from_numpy(indptr).to(self.dev)
+        # a one-element buffer when no row has ratings: the library wants valid pointers
+        idx_d = torch.from_numpy(indices if indices.size else np.zeros(1, np.int32)).to(self.dev)
+        val_d = torch.from_numpy(vals if vals.size else np.zeros(1, np.float32)).to(self.dev)
+        U = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
+        b = torch.empty(B, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.be.fold_in(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, n=self.n, Z=Z, b_i=self.b_i,
+                        mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu, n_sweeps=n_sweeps, U_out=U, b_u_out=b,
+                        status=status)
+        bad = int(status.item())
+        if bad:
+            raise np.linalg.LinAlgError(f"fold-in normal equations of row {bad - 1} are not positive definite")
+        return U, b, ptr_d, idx_d
+
+    def fold_in(self, indptr, indices, vals, features, n_sweeps: int):
+        """Factors / biases of new users (host CSR, rows sorted) against this fit's item side: device fp32
+        ([B, ld], [B]).  Z is composed as in `predict`.  Local to the calling rank, like `recommend`."""
+        U, b, _, _ = self._fold_in_dev(indptr, indices, vals, self._compose_for(features), n_sweeps)
+        return U, b
+
+    def recommend_new(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool):
+        """Fold in, then als_recommend_topk on the folded table (batch row b = user b, the given ratings as the
+        seen CSR), in REC_BATCH chunks: (items int64 [B, N], scores float64 [B, N])."""
+        Z = self._compose_for(features)
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        B = indptr.size - 1
+        items = np.empty((B, N), dtype=np.int64)
+        scores = np.empty((B, N), dtype=np.float64)
+        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            seen_ptr = seen_idx = None
+            if exclude_seen and indptr[b0 + nb] > indptr[b0]:
+                # views: row b of the chunk reads ptr_d[b0 + b]; the offsets stay absolute into idx_d
+                seen_ptr, seen_idx = ptr_d[b0: b0 + nb + 1], idx_d
+            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.recommend_topk(k=self.k, ld=self.ld, users=users[:nb], n=self.n, U=U[b0:], Z=Z,
+                                   b_u=b[b0:], b_i=self.b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                                   topn=N, top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
             items[b0: b0 + nb] = top_idx.cpu().numpy()
             scores[b0: b0 + nb] = top_val.cpu().numpy()
         return items, scores

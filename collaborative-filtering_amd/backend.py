@@ -306,3 +306,16 @@ class HipBackend:
                                                 _p(mu), _p(seen_ptr), _p(seen_idx), topn, nsl, _p(top_val),
                                                 _p(top_idx), _p(top_cnt), _p(self._rec_ws) if need > 0 else None, need,
                                                 self._stream()), "als_recommend_topk")
+
+    # -- K9 --------------------------------------------------------------------
+    def fold_in(self, *, k, ld, indptr, indices, vals, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, U_out, b_u_out,
+                status):
+        """Factors / biases of the rows of a CSR (device: int64 indptr, int32 indices, fp32 vals) against the fixed
+        item side: als_fold_in.  n_sweeps 0 = fixed point."""
+        p = _hip.FoldInParams()
+        p.k, p.ld, p.nrows, p.n_sweeps = k, ld, indptr.numel() - 1, int(n_sweeps)
+        p.indptr, p.indices, p.vals = _p(indptr), _p(indices), _p(vals)
+        p.n, p.Z, p.b_i, p.mu = int(n), _p(Z), _p(b_i), _p(mu)
+        p.lambda_u, p.lambda_bu = float(lam_u), float(lam_bu)
+        p.U_out, p.b_u_out, p.status = _p(U_out), _p(b_u_out), _p(status)
+        self._check(self.lib.als_fold_in(C.byref(p), self._stream()), "als_fold_in")

@@ -22,147 +22,11 @@
 // als_partial_slot_bytes_f64(k) bytes), k_sum_slots_f64 folds them in slot order, k_row_long_f64 finishes.
 #include "als_device.hpp"
 #include "als_hip.h"
+#include "row_f64_common.hpp"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ constexpr int blk64(int I, int K) { return I * (I + 1) / 2 + K; }
-
-template <int KB>
-struct F64Cfg {
-    static constexpr int KP = 16 * KB;
-    static constexpr int NACC = KB * (KB + 1) / 2;
-    static constexpr int NR = (KP + 63) / 64;
-    static constexpr int IMG = NACC * 256;                 // doubles: lower 16x16 blocks, row-major inside a block
-    static constexpr int SLOT = IMG + 2 * KP + 2;          // doubles of one partial slot: image, rhs, colsum, sumr, sumr2
-    static constexpr int MAXB = 28;                        // accumulator blocks per Gram pass (8 registers each)
-    // last block row (exclusive) of the pass that starts at block row I0
-    static constexpr int pass_end(int I0) {
-        int n = 0, I = I0;
-        while (I < KB && (n + I + 1 <= MAXB || I == I0)) { n += I + 1; ++I; }
-        return I;
-    }
-};
-
-__device__ __forceinline__ double readlane_d(double v, int src) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double bperm_d(double v, int src) {
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// one Gram pass: block rows [I0, I1) of the lower triangle, all ratings of the task
-// ---------------------------------------------------------------------------------------------------------
-template <int KB, int I0, int I1, bool FIRST>
-__device__ __forceinline__ void gram_pass_f64(const als_row_solve_params& P, int64_t beg, int len, double mu,
-                                              double bself, double* __restrict__ img, double (&rhs)[KB],
-                                              double (&cs)[KB], double& sumr, double& sumr2, int lane) {
-    constexpr int NB = blk64(I1, 0) - blk64(I0, 0);
-    constexpr int GS = 4;                                    // rating steps whose gathers are in flight together
-    const int c = lane & 15, q = lane >> 4;
-    const float* Fc = P.F + KB * c;
-    f64x4 acc[NB];
-#pragma unroll
-    for (int a = 0; a < NB; ++a) acc[a] = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int base = 0; base < len; base += 64) {
-        const int t = base + lane;
-        const bool ok = t < len;
-        const int idx = ok ? P.indices[beg + t] : P.F_zero_row;
-        double r_l = 0.0;
-        if (FIRST) {            // r = R - (mu + b_self + b_other) in fp64 (scripts/als.py:425, 447)
-            const float v = ok ? P.vals[beg + t] : 0.f;
-            const float bo = ok ? P.bias_other[idx] : 0.f;
-            const double rb = ok ? ((double)v - mu - (double)bo) : 0.0;
-            sumr += rb;
-            sumr2 = fma(rb, rb, sumr2);
-            r_l = ok ? rb - bself : 0.0;
-        }
-        const int off_l = idx * P.ld;
-        const int nvalid = min(64, len - base);
-#pragma unroll 1
-        for (int g0 = 0; g0 < 16; g0 += GS) {
-            if (4 * g0 >= nvalid) break;
-            float f[GS][KB];
-            double r_t[GS];
-#pragma unroll
-            for (int s = 0; s < GS; ++s) {
-                const int off = bperm_i(off_l, 4 * (g0 + s) + q);
-                if (FIRST) r_t[s] = bperm_d(r_l, 4 * (g0 + s) + q);
-                load_frow<KB>(Fc + (uint32_t)off, f[s]);
-            }
-#pragma unroll
-            for (int s = 0; s < GS; ++s) {
-                double fd[KB];
-#pragma unroll
-                for (int b = 0; b < KB; ++b) fd[b] = (double)f[s][b];
-                if (FIRST) {
-#pragma unroll
-                    for (int b = 0; b < KB; ++b) { rhs[b] = fma(fd[b], r_t[s], rhs[b]); cs[b] += fd[b]; }
-                }
-#pragma unroll
-                for (int I = I0; I < I1; ++I)
-#pragma unroll
-                    for (int K = 0; K <= I; ++K)
-                        acc[blk64(I, K) - blk64(I0, 0)] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                            fd[I], fd[K], acc[blk64(I, K) - blk64(I0, 0)], 0, 0, 0);
-            }
-        }
-    }
-    // accumulator register i of lane (c, q) is element (row q + 4 i, col c) of its block
-#pragma unroll
-    for (int I = I0; I < I1; ++I)
-#pragma unroll
-        for (int K = 0; K <= I; ++K)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                img[blk64(I, K) * 256 + (q + 4 * i) * 16 + c] = acc[blk64(I, K) - blk64(I0, 0)][i];
-}
-
-template <int KB, int I0, bool FIRST>
-__device__ __forceinline__ void gram_passes_f64(const als_row_solve_params& P, int64_t beg, int len, double mu,
-                                                double bself, double* __restrict__ img, double (&rhs)[KB],
-                                                double (&cs)[KB], double& sumr, double& sumr2, int lane) {
-    if constexpr (I0 < KB) {
-        constexpr int I1 = F64Cfg<KB>::pass_end(I0);
-        gram_pass_f64<KB, I0, I1, FIRST>(P, beg, len, mu, bself, img, rhs, cs, sumr, sumr2, lane);
-        gram_passes_f64<KB, I1, false>(P, beg, len, mu, bself, img, rhs, cs, sumr, sumr2, lane);
-    }
-}
-
-// rhs / colsum from "block b, position c, partial over q" to "perm position i = lane + 64 rr"
-template <int KB>
-__device__ __forceinline__ void to_rows_f64(double (&rhs)[KB], double (&cs)[KB], double (&rhs_p)[F64Cfg<KB>::NR],
-                                            double (&cs_p)[F64Cfg<KB>::NR], int lane) {
-    const int q = lane >> 4;
-#pragma unroll
-    for (int b = 0; b < KB; ++b) {
-        rhs[b] += __shfl_xor(rhs[b], 16, 64); rhs[b] += __shfl_xor(rhs[b], 32, 64);
-        cs[b] += __shfl_xor(cs[b], 16, 64);   cs[b] += __shfl_xor(cs[b], 32, 64);
-    }
-#pragma unroll
-    for (int rr = 0; rr < F64Cfg<KB>::NR; ++rr) {
-        double bsel = 0.0, csel = 0.0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (4 * rr + e < KB) {
-                bsel = (q == e) ? rhs[4 * rr + e] : bsel;
-                csel = (q == e) ? cs[4 * rr + e] : csel;
-            }
-        rhs_p[rr] = bsel;
-        cs_p[rr] = csel;
-    }
-}
+using namespace f64row;
 
 // ---------------------------------------------------------------------------------------------------------
 // regularise, factorise, solve / emit the factor.  img: lower blocks of F^T F; rhs_p / cs_p: lane = perm row.
@@ -224,6 +88,9 @@ __device__ __forceinline__ void finish_row_f64(const als_row_solve_params& P, in
     bool bad = false;
 
     // ---- blocked Cholesky, 16-column panels --------------------------------------------------------------
+    // (row_f64_common.hpp has the same loop for NRHS right-hand sides - cholesky_f64, solve_lt_f64 - for the
+    // fold-in kernel; this copy stays inline because calling those helpers here changes the block layout and
+    // schedule of the K1 kernels, which are kept instruction for instruction as measured)
 #pragma unroll 1
     for (int J = 0; J < KB; ++J) {
         // the panel part of the lane's matrix rows: p[rr][t] = A[i][16 J + t], i = lane + 64 rr >= 16 J

@@ -144,16 +144,65 @@ def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: 
     users, ub = np.unique(rows, return_inverse=True)
     if users.size == 0:
         return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan")}
-    n = int(max(model.V.shape[0], cols.max() + 1))
-    rel = np.unique(ub * n + cols)                                      # (user position, item), duplicates merged
-    nrel = np.bincount(rel // n, minlength=users.size)
     items, _ = model.recommend(users, K, features=features)
-    hit = (items >= 0) & np.isin(np.arange(users.size)[:, None] * n + items, rel)
+    return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
+
+
+def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int) -> Dict[str, Any]:
+    """recall@K / NDCG@K of ranked lists `items` [U, K] (-1 = empty slot) against the relevant (position ub, item
+    cols) pairs; every position 0 .. U-1 has at least one (see ranking_at_k)."""
+    nu = items.shape[0]
+    n = int(max(n_items, cols.max() + 1))
+    rel = np.unique(ub * n + cols)                                      # (user position, item), duplicates merged
+    nrel = np.bincount(rel // n, minlength=nu)
+    hit = (items >= 0) & np.isin(np.arange(nu)[:, None] * n + items, rel)
     disc = 1.0 / np.log2(np.arange(2, K + 2, dtype=np.float64))         # rank r = 1 .. K
     dcg = (hit * disc).sum(axis=1)
     idcg = np.cumsum(disc)[np.minimum(nrel, K) - 1]
-    return {"users": int(users.size), "recall@K": float(np.mean(hit.sum(axis=1) / nrel)),
+    return {"users": int(nu), "recall@K": float(np.mean(hit.sum(axis=1) / nrel)),
             "ndcg@K": float(np.mean(dcg / idcg))}
+
+
+def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating: Optional[float] = None,
+                         features: Optional[Dict[str, np.ndarray]] = None,
+                         n_sweeps: Optional[int] = None) -> Dict[str, Any]:
+    """recall@K and NDCG@K for users outside the fit (strong generalisation): every user of `held_out` is folded
+    in from its `known` ratings (`model.recommend_new`, the known items excluded) and scored on its held-out items
+    with the definitions of `ranking_at_k`.
+
+    known: (rows, cols, vals) - the new users' ratings that the model may see; held_out: (rows, cols) or
+    (rows, cols, vals).  Row ids are labels of the new users shared by the two sets (any integers; they are not
+    user ids of the fit).  A held-out user without known ratings is scored with zero factors (mu + b_i).
+    min_rating, features, n_sweeps: as in ranking_at_k / ALS.fold_in."""
+    if len(known) != 3:
+        raise ValueError("known must be (rows, cols, vals)")
+    if len(held_out) not in (2, 3):
+        raise ValueError("held_out must be (rows, cols) or (rows, cols, vals)")
+    rows = np.asarray(held_out[0], dtype=np.int64).ravel()
+    cols = np.asarray(held_out[1], dtype=np.int64).ravel()
+    if rows.shape != cols.shape:
+        raise ValueError("held-out rows and cols must have the same length")
+    if min_rating is not None:
+        if len(held_out) != 3:
+            raise ValueError("min_rating needs the held-out ratings (vals)")
+        keep = np.asarray(held_out[2], dtype=np.float64).ravel() >= min_rating
+        rows, cols = rows[keep], cols[keep]
+    users, ub = np.unique(rows, return_inverse=True)
+    if users.size == 0:
+        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan")}
+    kr = np.asarray(known[0], dtype=np.int64).ravel()
+    kc = np.asarray(known[1], dtype=np.int64).ravel()
+    kv = np.asarray(known[2], dtype=np.float64).ravel()
+    if not kr.shape == kc.shape == kv.shape:
+        raise ValueError("known rows, cols and vals must have the same length")
+    pos = np.searchsorted(users, kr)
+    mine = (pos < users.size) & (users[np.minimum(pos, users.size - 1)] == kr)     # known ratings of scored users
+    pos, kc, kv = pos[mine], kc[mine], kv[mine]
+    order = np.argsort(pos, kind="stable")
+    indptr = np.zeros(users.size + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pos, minlength=users.size), out=indptr[1:])
+    items, _ = model.recommend_new((indptr, kc[order], kv[order]), K, features=features, n_sweeps=n_sweeps)
+    return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
 
 
 def popularity_bins(item_counts: np.ndarray, n_bins: int = N_POP_BINS,

@@ -410,6 +410,39 @@ int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int6
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user
+ * half-step (scripts/als.py:411-433) for new rows.  For every row r < nrows of the CSR (indptr [nrows+1] /
+ * indices / vals: device, column indices in [0, n), unique and ascending within a row), with S its items, n_r = |S|:
+ *   A = Z_S^T Z_S + (lambda_u + 1e-10) I,  g = Z_S^T (r - mu - b_i[S]),  h = Z_S^T 1,  s = sum (r - mu - b_i[S]),
+ *   d = n_r + lambda_bu + 1e-10;
+ *   n_sweeps = T >= 1: T alternations from b = 0, u_t = A^-1 (g - b_{t-1} h), b_t = (s - h.u_t) / d -> (u_T, b_T);
+ *   n_sweeps = 0: their fixed point, the solution of [[A, h], [h^T, d]] [u; b] = [g; s].
+ * One fp64 factorisation per row (Gram on the fp64 matrix cores from the fp32 Z, Cholesky and substitutions in
+ * fp64); U_out [nrows][ld] (fp32, laid out as als_row_solve's X_out: columns >= k written 0) and b_u_out [nrows].
+ * A row without ratings gets u = 0, b = 0.  A row's result depends only on its own ratings.
+ * Z [n][ld] with zero padding columns (k .. ld-1), b_i [n], mu: device double.  ld = als_padded_k(k), n * ld < 2^31,
+ * nrows < 2^31 - 1; nrows == 0 is a no-op.  status (device int32): a non-positive or NaN pivot (only a non-finite Z
+ * makes one) sets it to max(status, row + 1).
+ * ------------------------------------------------------------------------- */
+typedef struct als_fold_in_params {
+    int k, ld;
+    int64_t nrows;
+    int n_sweeps;                                   /* 0 = fixed point */
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* vals;
+    int64_t n;
+    const float* Z;
+    const float* b_i;
+    const double* mu;
+    float lambda_u, lambda_bu;
+    float* U_out;
+    float* b_u_out;
+    int32_t* status;
+} als_fold_in_params;
+int als_fold_in(const als_fold_in_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
