@@ -21,7 +21,7 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_sumsq", "als_history_row", "als_compose_z", "als_predict_at", "als_predict_dense",
            "als_topk_similarity", "als_graph_classify", "als_normalize_features", "als_impute_col_median",
            "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
-           "als_recommend_workspace_bytes", "als_recommend_topk", "als_fold_in")
+           "als_recommend_workspace_bytes", "als_recommend_topk", "als_fold_in", "als_fold_in_items")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -81,6 +81,19 @@ class FoldInParams(C.Structure):
     ]
 
 
+class FoldInItemsParams(C.Structure):
+    """struct als_fold_in_items_params (include/als_hip.h)."""
+    _fields_ = [
+        ("k", _i32), ("ld", _i32), ("nrows", _i64), ("n_sweeps", _i32), ("pop_reg", _i32),
+        ("indptr", _vp), ("indices", _vp), ("vals", _vp),
+        ("m", _i64), ("U", _vp), ("b_u", _vp), ("mu", _vp),
+        ("S_ptr", _vp), ("S_idx", _vp), ("S_val", _vp),
+        ("n", _i64), ("V", _vp),
+        ("lambda_v", _f32), ("lambda_bi", _f32), ("alpha", _f32), ("reserved", _f32),
+        ("V_out", _vp), ("b_i_out", _vp), ("status", _vp),
+    ]
+
+
 class HipLibraryMissing(RuntimeError):
     pass
 
@@ -132,6 +145,7 @@ def load():
     lib.als_recommend_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_fold_in.argtypes = [C.POINTER(FoldInParams), _vp]
+    lib.als_fold_in_items.argtypes = [C.POINTER(FoldInItemsParams), _vp]
     lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]

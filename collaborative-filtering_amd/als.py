@@ -189,6 +189,68 @@ def fold_in_csr(R_new, n: int):
     return indptr, indices.astype(np.int32), vals32
 
 
+@dataclass
+class FoldedItems:
+    """Items outside the fit, placed by `ALS.fold_in_items`; folded item b is item n + b in `ALS.recommend`.
+
+    V, Z: float64 [B, k], the fp32 device values (Z = V + sum_f X_new,f W_f, what predictions use); b_i: float64
+    [B].  graph: the graph rows used, (ptr int64 [B+1], idx int32 fitted item ids, val float32), or None without a
+    graph.  ratings: the ratings CSR (ptr int64 [B+1], idx int32 user ids ascending, val float32)."""
+    V: np.ndarray
+    b_i: np.ndarray
+    Z: np.ndarray
+    graph: Optional[tuple]
+    ratings: tuple
+
+    @property
+    def n_items(self) -> int:
+        return int(self.b_i.shape[0])
+
+
+def new_item_features(features_new, W_dims: Dict[str, int], B: int) -> Dict[str, np.ndarray]:
+    """Validated features of new items: every feature of the fit (`W_dims`: name -> columns) and nothing else, each
+    a finite (B, d) array.  Raises ValueError otherwise."""
+    fn = _host_features(features_new)
+    missing = [f for f in W_dims if f not in fn]
+    if missing:
+        raise ValueError(f"features_new must name every feature of the fit; missing: {missing}")
+    unknown = [f for f in fn if f not in W_dims]
+    if unknown:
+        raise ValueError(f"features_new names features the model was not fitted with: {unknown}")
+    out = {}
+    for f, d in W_dims.items():
+        X = np.asarray(fn[f])
+        if X.ndim != 2 or X.shape != (B, d):
+            raise ValueError(f"Feature '{f}' of the new items has shape {X.shape}; expected ({B}, {d})")
+        if not np.isfinite(X).all():
+            raise ValueError(f"Feature '{f}' of the new items contains non-finite values.")
+        out[f] = X
+    return out
+
+
+def new_item_graph_csr(S_new, B: int, n: int):
+    """Caller-supplied graph rows of new items -> host CSR (ptr int64 [B+1], idx int32 in [0, n), val float32).
+    Raises ValueError for a malformed triple, a wrong row count, an index outside [0, n) or a non-finite weight."""
+    if not (isinstance(S_new, (tuple, list)) and len(S_new) == 3):
+        raise ValueError("S_new must be a CSR triple (ptr, idx, val)")
+    ptr, idx, val = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a) for a in S_new)
+    if (ptr.ndim != 1 or idx.ndim != 1 or val.ndim != 1 or (ptr.size and not np.issubdtype(ptr.dtype, np.integer))
+            or (idx.size and not np.issubdtype(idx.dtype, np.integer))):
+        raise ValueError("S_new must be 1-D (ptr, idx, val) with integer ptr / idx")
+    if ptr.size != B + 1:
+        raise ValueError(f"S_new has {ptr.size - 1} rows; expected {B} (one per new item)")
+    ptr = ptr.astype(np.int64)
+    if ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != idx.size or idx.size != val.size:
+        raise ValueError("S_new: ptr must start at 0, not decrease, and end at len(idx) == len(val)")
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise ValueError(f"S_new: item indices must lie in [0, {n}) (fitted items)")
+    with np.errstate(over="ignore"):
+        val32 = val.astype(np.float32)
+    if not np.isfinite(val32).all():
+        raise ValueError("S_new contains non-finite weights")
+    return ptr, idx.astype(np.int32), val32
+
+
 def _on(device):
     """Make `device` the current HIP device for the enclosed calls: the C-ABI library launches on the current
     device (and sizes its persistent grids from that device's occupancy), torch only hands it a stream."""
@@ -467,7 +529,7 @@ class ALS:
             return self._eng.predict_at(np.asarray(flat_idx, dtype=np.int64), features)
 
     def recommend(self, users=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
-                  exclude_seen: bool = True):
+                  exclude_seen: bool = True, new_items: Optional[FoldedItems] = None):
         """Top-N items per user: returns (items int64 [B, N], scores float64 [B, N]), each row ordered by score
         descending, ties to the lower item index.
 
@@ -479,8 +541,14 @@ class ALS:
         Contract: scores[b, j] == predict(features)[users[b], items[b, j]] exactly, and no item outside the
         returned list scores higher (or equal with a lower index) than items[b, N - 1], seen items aside.
         Nothing m x n is formed: one fused kernel scores and selects (als_recommend_topk).  On a sharded fit the
-        call is local to the calling rank (no collective)."""
+        call is local to the calling rank (no collective).
+
+        `new_items` (a `fold_in_items` result): rank the n fitted items and the B folded ones together, folded item
+        b as item n + b, scored as `predict_new_items`; with `exclude_seen` the folded items a user rated in their
+        ratings are left out as well."""
         features = self._check_predict(features)
+        if new_items is not None:
+            self._check_folded(new_items)
         if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= N <= RECOMMEND_MAX_N:
             raise ValueError(f"N must be an integer in [1, {RECOMMEND_MAX_N}], got {N!r}")
         N = int(N)
@@ -497,6 +565,8 @@ class ALS:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
+            if new_items is not None:
+                return self._eng.recommend_with_items(us, N, features, exclude_seen, new_items)
             return self._eng.recommend(us, N, features, exclude_seen)
 
     @staticmethod
@@ -543,6 +613,114 @@ class ALS:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen)
+
+    # ---------------------------------------------------------- new items
+    def fold_in_items(self, C_new=None, *, features_new: Optional[Dict[str, np.ndarray]] = None,
+                      features: Optional[Dict[str, np.ndarray]] = None, S_new=None,
+                      n_sweeps: Optional[int] = None) -> FoldedItems:
+        """Factors and biases of items outside the fit, the user side (U, b_u, mu), the fitted items' V and W held
+        fixed: the fit's item half-step (scripts/als.py:436-466) for B new columns, T = `n_sweeps` times from
+        b_i = 0, or (None) its fixed point.  Returns a `FoldedItems` record.
+
+        `C_new`: the new items' ratings, a dense (B, m) array with NaN for missing, or a CSR triple (indptr,
+        indices, vals) over user ids; None = no ratings.  An item without ratings still gets a factor from its
+        graph neighbours (v = alpha sum_j s_j V_j / lambda_i, b_i = 0; v = 0 without a graph), and its score is
+        then carried by its features.  `features_new`: every feature of the fit with B rows each, transformed
+        exactly as the fit's features were (normalisation, imputation) - that is the caller's job; Z = V +
+        sum_f X_new,f W_f.  With the graph on (the fit had one), the graph rows are the new items' top-`sim.topk`
+        cosines against the fitted items' sim feature - `features[sim.feature_name]`, by default the fit's own copy
+        - positive entries only; a fit with a caller-supplied graph passes the rows as `S_new=(ptr, idx, val)`.
+        Each item's result depends only on its own ratings and graph row, bitwise.  Local to the calling rank."""
+        if self.U is None or self.V is None:
+            raise RuntimeError("Model must be fitted before prediction.")
+        T = self._check_sweeps(n_sweeps)
+        m, n = self.U.shape[0], self.V.shape[0]
+        eng = self._eng
+        sources = []
+        if C_new is not None:
+            ratings = fold_in_csr(C_new, m)
+            sources.append(("C_new", ratings[0].size - 1))
+        fn = _host_features(features_new)
+        if fn:
+            sources.append(("features_new", int(np.shape(next(iter(fn.values())))[0])))
+        if S_new is not None and isinstance(S_new, (tuple, list)) and len(S_new) == 3:
+            sources.append(("S_new", int(np.shape(S_new[0])[0]) - 1))
+        if not sources:
+            raise ValueError("fold_in_items needs the new items' ratings (C_new), features (features_new) or "
+                             "graph rows (S_new)")
+        B = sources[0][1]
+        if any(b != B for _, b in sources):
+            raise ValueError(f"new item counts disagree: {sources}")
+        if C_new is None:
+            ratings = (np.zeros(B + 1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
+        X_new = new_item_features(fn, {f: int(W.shape[0]) for f, W in self.W.items()}, B)
+        S_host, X_pair = None, None
+        if eng.use_graph:
+            if S_new is not None:
+                S_host = new_item_graph_csr(S_new, B, n)
+            else:
+                name = self.cfg.graph.sim.feature_name
+                Xf = _host_features(features).get(name) if features else None
+                if Xf is None:
+                    Xf = eng.X64.get(name) if getattr(eng, "X64", None) else None
+                if name not in X_new or Xf is None:
+                    raise ValueError(f"the model was fitted with a similarity graph: pass the new items' "
+                                     f"'{name}' feature (features_new; the fitted items' one in features) or "
+                                     f"their graph rows (S_new)")
+                if tuple(Xf.shape) != (n, X_new[name].shape[1]):
+                    raise ValueError(f"Feature '{name}' of the fitted items has shape {tuple(Xf.shape)}; "
+                                     f"expected ({n}, {X_new[name].shape[1]})")
+                X_pair = (X_new[name], Xf)
+        elif S_new is not None:
+            raise ValueError("S_new given, but the model was fitted without a similarity graph")
+        k = self.V.shape[1]
+        if B == 0:
+            e = np.empty((0, k), dtype=np.float64)
+            return FoldedItems(e, np.empty(0), e.copy(), (np.zeros(1, np.int64), np.zeros(0, np.int32),
+                                                          np.zeros(0, np.float32)) if eng.use_graph else None, ratings)
+        with _on(eng.dev):
+            if X_pair is not None:
+                S_dev = eng.graph_rows_new(*X_pair)
+            elif S_host is not None:
+                S_dev = tuple(torch.from_numpy(a).to(eng.dev) for a in S_host)
+            else:
+                S_dev = None
+            V, b, Z = eng.fold_in_items(*ratings, S_dev, X_new, T)
+            graph = None if S_dev is None else tuple(t.cpu().numpy() for t in S_dev)
+            return FoldedItems(V[:, :k].to(torch.float64).cpu().numpy(), b.to(torch.float64).cpu().numpy(),
+                               Z[:, :k].to(torch.float64).cpu().numpy(), graph, ratings)
+
+    def _check_folded(self, folded) -> None:
+        if self.U is None or self.V is None:
+            raise RuntimeError("Model must be fitted before prediction.")
+        if not isinstance(folded, FoldedItems):
+            raise ValueError("new items must be a FoldedItems record (ALS.fold_in_items)")
+        k, B = self.V.shape[1], folded.n_items
+        if folded.Z.shape != (B, k) or folded.b_i.shape != (B,):
+            raise ValueError(f"FoldedItems holds Z {folded.Z.shape} and b_i {folded.b_i.shape}; this model needs "
+                             f"({B}, {k}) and ({B},)")
+        ptr = folded.ratings[0]
+        if len(ptr) != B + 1:
+            raise ValueError("FoldedItems: ratings CSR does not have one row per item")
+
+    def predict_new_items(self, folded: FoldedItems, users=None) -> np.ndarray:
+        """Scores of folded items: (len(users), B) float64 - all m users in id order for None - each bitwise the
+        predict epilogue ((U_u.Z_b + mu) + b_u) + b_b of the fp32 tables (als_predict_dense)."""
+        self._check_folded(folded)
+        m = self.U.shape[0]
+        if users is None:
+            u = np.arange(m, dtype=np.int64)
+        else:
+            u = np.asarray(users)
+            if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
+                raise ValueError("users must be a 1-D array-like of integer user ids")
+            if u.size and (u.min() < 0 or u.max() >= m):
+                raise IndexError(f"user ids must lie in [0, {m})")
+        if u.size == 0 or folded.n_items == 0:
+            return np.empty((u.size, folded.n_items), dtype=np.float64)
+        with _on(self._eng.dev):
+            us = torch.from_numpy(u.astype(np.int64)).to(self._eng.dev)
+            return self._eng.predict_new_items(us, folded).cpu().numpy().astype(np.float64)
 
 
 class _Engine:
@@ -1350,6 +1528,161 @@ class _Engine:
             items[b0: b0 + nb] = top_idx.cpu().numpy()
             scores[b0: b0 + nb] = top_val.cpu().numpy()
         return items, scores
+
+    # ----------------------------------------------------------- new items
+    GRAPH_ROWS_MAX_D = 160      # sim feature width the top-k kernel takes (its k)
+
+    def graph_rows_new(self, X_new: np.ndarray, X_fit) -> tuple:
+        """Graph rows of new items against the fitted ones: top-`sim.topk` fp32 cosines
+        under (similarity descending, index ascending), positive entries only, as device CSR (ptr int64, idx
+        int32, val float32).  als_recommend_topk with k = d, U = normalised new rows, Z = normalised fitted rows,
+        zero biases and mu = 0 computes exactly that; topk None / > 128 or d > 160 take the blocked torch
+        formulation (same contract)."""
+        md = self.model
+        eps, topk = md.S_eps, md.S_topk
+        Xn_new = layout.normalize_rows_f32(X_new, eps, self.dev)
+        Xn_fit = layout.normalize_rows_f32(X_fit, eps, self.dev)
+        B, d = Xn_new.shape
+        if topk is None or topk > RECOMMEND_MAX_N or d > self.GRAPH_ROWS_MAX_D or d < 1:
+            logger.warning("graph rows of new items: top-k %s / %d feature columns are outside what the top-k "
+                           "kernel takes (top-k <= %d, d <= %d); using the blocked torch formulation", topk, d,
+                           RECOMMEND_MAX_N, self.GRAPH_ROWS_MAX_D)
+            return layout.similarity_rows_torch(Xn_new, Xn_fit, topk)
+        ldd = layout.padded_k(d)
+        Un = torch.zeros(B, ldd, dtype=torch.float32, device=self.dev)
+        Un[:, :d] = Xn_new
+        Zn = torch.zeros(self.n, ldd, dtype=torch.float32, device=self.dev)
+        Zn[:, :d] = Xn_fit
+        zu = torch.zeros(B, dtype=torch.float32, device=self.dev)
+        zi = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
+        mu0 = torch.zeros(1, dtype=torch.float64, device=self.dev)
+        top_val = torch.empty(B, topk, dtype=torch.float32, device=self.dev)
+        top_idx = torch.empty(B, topk, dtype=torch.int32, device=self.dev)
+        top_cnt = torch.empty(B, dtype=torch.int32, device=self.dev)
+        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            self.be.recommend_topk(k=d, ld=ldd, users=users[:nb], n=self.n, U=Un[b0:], Z=Zn, b_u=zu[b0:], b_i=zi,
+                                   mu=mu0, seen_ptr=None, seen_idx=None, topn=topk, top_val=top_val[b0:],
+                                   top_idx=top_idx[b0:], top_cnt=top_cnt[b0:])
+        return layout.rows_from_topk(top_val, top_idx)
+
+    def fold_in_items(self, indptr, indices, vals, S, X_new: Dict[str, np.ndarray], n_sweeps: int):
+        """Factors / biases of new items (host ratings CSR by user id, rows sorted; device graph rows S or None)
+        against this fit's user side and V (one als_fold_in_items launch), and their Z = V + X_new W
+        (als_compose_z): device fp32 ([B, ld], [B], [B, ld])."""
+        md = self.model
+        B = indptr.size - 1
+        ptr_d = torch.from_numpy(indptr).to(self.dev)
+        idx_d = torch.from_numpy(indices if indices.size else np.zeros(1, np.int32)).to(self.dev)
+        val_d = torch.from_numpy(vals if vals.size else np.zeros(1, np.float32)).to(self.dev)
+        if S is not None and S[1].numel() == 0:     # the library wants valid pointers
+            S = (S[0], torch.zeros(1, dtype=torch.int32, device=self.dev),
+                 torch.zeros(1, dtype=torch.float32, device=self.dev))
+        V = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
+        b = torch.empty(B, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.be.fold_in_items(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, m=self.m, U=self.U,
+                              b_u=self.b_u, mu=self.mu, S=S, n=self.n, V=self.V, lam_v=md.lambda_v,
+                              pop_reg=bool(md.pop_reg_mode), lam_bi=md.lambda_bi,
+                              alpha=md.alpha if S is not None else 0.0, n_sweeps=n_sweeps, V_out=V, b_i_out=b,
+                              status=status)
+        bad = int(status.item())
+        if bad:
+            raise np.linalg.LinAlgError(f"item fold-in normal equations of row {bad - 1} are not positive definite")
+        if not self.feat_names:
+            return V, b, V
+        Xcat = np.concatenate([np.asarray(X_new[f], dtype=np.float32) for f in self.feat_names], axis=1)
+        W = torch.zeros(Xcat.shape[1], self.ld, dtype=torch.float32, device=self.dev)
+        off = 0
+        for f, d in zip(self.feat_names, self.feat_dims):
+            W[off:off + d, : self.k] = self.W64[f].to(torch.float32)
+            off += d
+        Z = torch.empty_like(V)
+        self.be.compose_z(V, torch.from_numpy(Xcat).to(self.dev), W, Z)
+        return V, b, Z
+
+    def _folded_dev(self, folded: "FoldedItems"):
+        """Z [B, ld] and b_i [B] of folded items back on the device (exact: they are fp32 values)."""
+        B = folded.n_items
+        Z = torch.zeros(B, self.ld, dtype=torch.float32, device=self.dev)
+        Z[:, : self.k] = torch.from_numpy(folded.Z.astype(np.float32)).to(self.dev)
+        return Z, torch.from_numpy(folded.b_i.astype(np.float32)).to(self.dev)
+
+    def predict_new_items(self, us: torch.Tensor, folded: "FoldedItems") -> torch.Tensor:
+        """Scores of the folded items for users `us` (int64, device): als_predict_dense on the gathered user rows,
+        fp32 [len(us), B]."""
+        Z, b_new = self._folded_dev(folded)
+        out = torch.empty(us.numel(), folded.n_items, dtype=torch.float32, device=self.dev)
+        self.be.predict_dense(k=self.k, ld=self.ld, m=us.numel(), n=folded.n_items, U=self.U.index_select(0, us),
+                              Z=Z, b_u=self.b_u.index_select(0, us), b_i=b_new, mu=self.mu, out=out)
+        return out
+
+    def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
+                             folded: "FoldedItems"):
+        """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
+        concatenated Z / b_i tables; the batch's user rows are gathered (batch row r = user users_t[r]) and their
+        seen lists are the training row followed by the folded items they rated - ascending, as the new ids come
+        last."""
+        Z_fit = self._compose_for(features)
+        Z_new, b_new = self._folded_dev(folded)
+        n_all = self.n + folded.n_items
+        Z = torch.cat([Z_fit[: self.n], Z_new])
+        b_i = torch.cat([self.b_i[: self.n], b_new])
+        if exclude_seen:
+            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item
+            rp, ri = folded.ratings[0], folded.ratings[1]
+            new_u = ri.astype(np.int64)
+            new_i = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
+            o = np.lexsort((new_i, new_u))
+            new_u_d = torch.from_numpy(new_u[o]).to(self.dev)
+            new_i_d = torch.from_numpy(new_i[o].astype(np.int32)).to(self.dev)
+        B = users_t.numel()
+        items = np.empty((B, N), dtype=np.int64)
+        scores = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            us = users_t[b0: b0 + self.REC_BATCH].to(torch.int64)
+            nb = us.numel()
+            seen_ptr = seen_idx = None
+            if exclude_seen:
+                seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d)
+            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.recommend_topk(k=self.k, ld=self.ld, users=torch.arange(nb, dtype=torch.int32, device=self.dev),
+                                   n=n_all, U=self.U.index_select(0, us), Z=Z, b_u=self.b_u.index_select(0, us),
+                                   b_i=b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
+                                   top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
+            items[b0: b0 + nb] = top_idx.cpu().numpy()
+            scores[b0: b0 + nb] = top_val.cpu().numpy()
+        return items, scores
+
+    def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
+        """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items
+        (ids >= n) they rated, taken from the (user, item)-sorted pairs new_u / new_i."""
+        ptr, idx = self.csr.indptr, self.csr.indices
+        beg_f = ptr[us]
+        cnt_f = ptr[us + 1] - beg_f
+        beg_n = torch.searchsorted(new_u, us)
+        cnt_n = torch.searchsorted(new_u, us, right=True) - beg_n
+        cnt = cnt_f + cnt_n
+        out_ptr = torch.zeros(us.numel() + 1, dtype=torch.int64, device=self.dev)
+        out_ptr[1:] = torch.cumsum(cnt, 0)
+        total = int(out_ptr[-1])
+        out_idx = torch.empty(max(total, 1), dtype=torch.int32, device=self.dev)
+        rows = torch.arange(us.numel(), device=self.dev)
+        for beg, c, skip, src in ((beg_f, cnt_f, None, idx), (beg_n, cnt_n, cnt_f, new_i)):
+            tot = int(c.sum())
+            if tot == 0:
+                continue
+            r = torch.repeat_interleave(rows, c)
+            first = torch.cumsum(c, 0) - c                       # position of each row's first entry in this part
+            off = torch.arange(tot, device=self.dev) - first[r]
+            dst = out_ptr[r] + off + (skip[r] if skip is not None else 0)
+            out_idx[dst] = src[beg[r] + off]
+        if total == 0:
+            return None, None
+        return out_ptr, out_idx
 
     def predict_pairs(self, us: torch.Tensor, is_: torch.Tensor, features, features_of_fit: bool = False) -> torch.Tensor:
         """Predictions at (user, item) index tensors already on the device (int32); fp32 device tensor."""

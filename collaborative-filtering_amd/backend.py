@@ -319,3 +319,19 @@ class HipBackend:
         p.lambda_u, p.lambda_bu = float(lam_u), float(lam_bu)
         p.U_out, p.b_u_out, p.status = _p(U_out), _p(b_u_out), _p(status)
         self._check(self.lib.als_fold_in(C.byref(p), self._stream()), "als_fold_in")
+
+    def fold_in_items(self, *, k, ld, indptr, indices, vals, m, U, b_u, mu, S, n, V, lam_v, pop_reg, lam_bi, alpha,
+                      n_sweeps, V_out, b_i_out, status):
+        """Factors / biases of new items (ratings CSR by rater id; device: int64 indptr, int32 indices, fp32 vals)
+        against the fixed user side and the fitted V, with graph rows S = (ptr, idx, val) or None:
+        als_fold_in_items.  n_sweeps 0 = fixed point."""
+        p = _hip.FoldInItemsParams()
+        p.k, p.ld, p.nrows, p.n_sweeps, p.pop_reg = k, ld, indptr.numel() - 1, int(n_sweeps), int(bool(pop_reg))
+        p.indptr, p.indices, p.vals = _p(indptr), _p(indices), _p(vals)
+        p.m, p.U, p.b_u, p.mu = int(m), _p(U), _p(b_u), _p(mu)
+        if S is not None:
+            p.S_ptr, p.S_idx, p.S_val = _p(S[0]), _p(S[1]), _p(S[2])
+        p.n, p.V = int(n), _p(V)
+        p.lambda_v, p.lambda_bi, p.alpha = float(lam_v), float(lam_bi), float(alpha)
+        p.V_out, p.b_i_out, p.status = _p(V_out), _p(b_i_out), _p(status)
+        self._check(self.lib.als_fold_in_items(C.byref(p), self._stream()), "als_fold_in_items")

@@ -205,6 +205,54 @@ def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating
     return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
 
 
+def cold_item_rmse(model: ALS, held_out, *, known=None, features_new: Optional[Dict[str, np.ndarray]] = None,
+                   features: Optional[Dict[str, np.ndarray]] = None,
+                   n_sweeps: Optional[int] = None) -> Dict[str, Any]:
+    """RMSE on items outside the fit (strong generalisation for items): the B new items are folded in from their
+    `known` ratings (`model.fold_in_items`; None = no ratings, the cold-start case), scored with
+    `model.predict_new_items` on the `held_out` pairs, and compared with the bias-only baseline mu + b_u on the
+    same pairs.
+
+    held_out / known: (user ids, new item positions b in [0, B), ratings).  B is the row count of `features_new`
+    (every feature of the fit, as in fold_in_items), or 1 + the largest position when the model has no features.
+    features (the fitted items', for the graph rows) and n_sweeps: as in fold_in_items.
+    Returns {"pairs": held-out pairs, "rmse": folded-in RMSE, "baseline_rmse": mu + b_u RMSE} (NaN when empty)."""
+    if len(held_out) != 3:
+        raise ValueError("held_out must be (user ids, new item positions, ratings)")
+    hu, hb, hv = (np.asarray(a).ravel() for a in held_out)
+    if not hu.shape == hb.shape == hv.shape:
+        raise ValueError("held-out users, items and ratings must have the same length")
+    if known is not None:
+        if len(known) != 3:
+            raise ValueError("known must be (user ids, new item positions, ratings)")
+        ku, kb, kv = (np.asarray(a).ravel() for a in known)
+        if not ku.shape == kb.shape == kv.shape:
+            raise ValueError("known users, items and ratings must have the same length")
+    else:
+        ku = kb = np.zeros(0, np.int64)
+        kv = np.zeros(0)
+    if features_new:
+        B = int(np.shape(next(iter(features_new.values())))[0])
+    else:
+        B = int(max(hb.max(initial=-1), kb.max(initial=-1))) + 1
+    for what, b in (("held_out", hb), ("known", kb)):
+        if b.size and (b.min() < 0 or b.max() >= B):
+            raise IndexError(f"{what}: new item positions must lie in [0, {B})")
+    kb = kb.astype(np.int64)
+    order = np.lexsort((ku, kb))
+    indptr = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(np.bincount(kb, minlength=B), out=indptr[1:])
+    folded = model.fold_in_items((indptr, ku[order], kv[order]), features_new=features_new, features=features,
+                                 n_sweeps=n_sweeps)
+    if hu.size == 0:
+        return {"pairs": 0, "rmse": float("nan"), "baseline_rmse": float("nan")}
+    users, inv = np.unique(hu.astype(np.int64), return_inverse=True)
+    pred = model.predict_new_items(folded, users)[inv, hb.astype(np.int64)]
+    y = hv.astype(np.float64)
+    base = model.mu + model.b_u[users][inv]
+    return {"pairs": int(hu.size), "rmse": rmse_at(y, pred), "baseline_rmse": rmse_at(y, base)}
+
+
 def popularity_bins(item_counts: np.ndarray, n_bins: int = N_POP_BINS,
                     strategy: str = POP_BIN_STRATEGY) -> Tuple[np.ndarray, np.ndarray]:
     """Item popularity bins from per-item rating counts: (bin per item, bin edges)."""

@@ -376,6 +376,47 @@ def build_similarity_device(X, topk: Optional[int], eps: float, device, block: i
     return ptr, sc.to(torch.int32), sv32, D
 
 
+def normalize_rows_f32(X, eps: float, device):
+    """X / (||X|| + eps) row by row in fp32 on `device`, as `build_similarity_kernel` normalises the sim feature."""
+    import torch
+    if torch.is_tensor(X):
+        Xd = X.to(device=device, dtype=torch.float32)
+    else:
+        Xd = torch.as_tensor(np.asarray(X, dtype=np.float32), device=device)
+    return Xd / (torch.sqrt((Xd * Xd).sum(1, keepdim=True)) + np.float32(eps))
+
+
+def rows_from_topk(top_val, top_idx):
+    """Per-row top lists (val, idx [B, t], unused slots idx -1) -> CSR (ptr int64, idx int32, val float32) of the
+    positive entries, each row in list order."""
+    import torch
+    keep = (top_idx >= 0) & (top_val > 0)
+    ptr = torch.zeros(top_val.shape[0] + 1, dtype=torch.int64, device=top_val.device)
+    ptr[1:] = torch.cumsum(keep.sum(1), 0)
+    return ptr, top_idx[keep].to(torch.int32), top_val[keep].to(torch.float32)
+
+
+def similarity_rows_torch(Xn_new, Xn_fit, topk: Optional[int], block: int = 4096):
+    """Graph rows of new items against fitted ones (both row-normalised, same dtype and device): row b holds the
+    top-`topk` entries of Xn_new[b] Xn_fit^T (all of them for topk None) under the total order (similarity
+    descending, index ascending), positive entries only - (ptr int64, idx int32, val float32).  The blocked torch
+    formulation of `build_similarity_device`, without the diagonal and the mirror half (the fitted items are
+    frozen)."""
+    import torch
+    B, n = Xn_new.shape[0], Xn_fit.shape[0]
+    t = n if topk is None else min(int(topk), n)
+    vals, idxs = [], []
+    for b in range(0, B, block):
+        Sb = Xn_new[b: b + block] @ Xn_fit.T
+        tv, ti = torch.sort(Sb, dim=1, descending=True, stable=True)     # ties keep ascending index order
+        vals.append(tv[:, :t]); idxs.append(ti[:, :t])
+    if B == 0 or t == 0:
+        return (torch.zeros(B + 1, dtype=torch.int64, device=Xn_new.device),
+                torch.zeros(0, dtype=torch.int32, device=Xn_new.device),
+                torch.zeros(0, dtype=torch.float32, device=Xn_new.device))
+    return rows_from_topk(torch.cat(vals), torch.cat(idxs))
+
+
 def dense_graph_to_csr(S: np.ndarray):
     ri, ci = np.nonzero(S)
     ptr = np.zeros(S.shape[0] + 1, dtype=np.int64)

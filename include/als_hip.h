@@ -443,6 +443,45 @@ typedef struct als_fold_in_params {
 int als_fold_in(const als_fold_in_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Item fold-in: factors and biases of items outside the fit, the user side (U, b_u, mu) and the fitted items' V
+ * held fixed - the fit's item half-step (scripts/als.py:436-466) for new columns.  For every row r < nrows of the
+ * ratings CSR (indptr [nrows+1] / indices / vals: device, rater ids in [0, m), unique within a row), with S its
+ * raters, n_r = |S|, and its graph row N_r (S_ptr [nrows+1] / S_idx / S_val: fitted item ids j in [0, n) with
+ * weights s_rj, in any order; all three NULL = no graph), D_r = sum_j s_rj:
+ *   lambda_r = (pop_reg ? lambda_v / sqrt(n_r + 1) : lambda_v) + 1e-10 + alpha D_r,
+ *   A = U_S^T U_S + lambda_r I,  g = U_S^T (r - mu - b_u[S]) + alpha sum_j s_rj V_j,  h = U_S^T 1,
+ *   s = sum (r - mu - b_u[S]),  d = n_r + lambda_bi + 1e-10;
+ * then the recurrence / fixed point of als_fold_in (n_sweeps = T >= 1 or 0).  D_r and the neighbour sum run in
+ * fp64 in the row's storage order.  A row without ratings is solved too: v = alpha sum_j s_rj V_j / lambda_r,
+ * b = 0.  V_out [nrows][ld] (columns >= k written 0), b_i_out [nrows].  U [m][ld] and V [n][ld] with zero padding
+ * columns, mu: device double.  ld = als_padded_k(k), m * ld < 2^31 and n * ld < 2^31, nrows < 2^31 - 1; nrows == 0
+ * is a no-op.  status as in als_fold_in.
+ * ------------------------------------------------------------------------- */
+typedef struct als_fold_in_items_params {
+    int k, ld;
+    int64_t nrows;
+    int n_sweeps;                                   /* 0 = fixed point */
+    int pop_reg;                                    /* 1: lambda_v / sqrt(n_r + 1) */
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* vals;
+    int64_t m;
+    const float* U;
+    const float* b_u;
+    const double* mu;
+    const int64_t* S_ptr;
+    const int32_t* S_idx;
+    const float* S_val;
+    int64_t n;
+    const float* V;
+    float lambda_v, lambda_bi, alpha, reserved;
+    float* V_out;
+    float* b_i_out;
+    int32_t* status;
+} als_fold_in_items_params;
+int als_fold_in_items(const als_fold_in_items_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
