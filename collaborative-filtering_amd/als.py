@@ -614,6 +614,74 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen)
 
+    # ---------------------------------------------------------- evaluation
+    def _check_pairs(self, users, items, bound_u: Optional[int]):
+        u, i = np.asarray(users), np.asarray(items)
+        if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
+            raise ValueError("users must be a 1-D array-like of integer user ids")
+        if i.ndim != 1 or (i.size and not np.issubdtype(i.dtype, np.integer)):
+            raise ValueError("items must be a 1-D array-like of integer item ids")
+        if u.shape != i.shape:
+            raise ValueError("users and items must have the same length")
+        n = self.V.shape[0]
+        if bound_u is not None and u.size and (u.min() < 0 or u.max() >= bound_u):
+            raise IndexError(f"user ids must lie in [0, {bound_u})")
+        if i.size and (i.min() < 0 or i.max() >= n):
+            raise IndexError(f"item ids must lie in [0, {n})")
+        return u.astype(np.int64), i.astype(np.int64)
+
+    def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True):
+        """Exact full-catalogue rank of item items[p] for user users[p], P pairs: returns
+        (rank int64 [P], n_candidates int64 [P], scores float32 [P]).
+
+        rank[p] is the number of candidate items that precede items[p] in `recommend`'s order for users[p] (score
+        descending, ties to the lower item index), 0-based: an item `recommend` returns at position j has rank j,
+        for any N.  The candidates are the items `recommend` could return: all n items, without the user's seen
+        items when `exclude_seen`, without NaN scores; n_candidates[p] is their number.  The rank is defined
+        whether or not items[p] itself is seen (it is then the position the item would take); -1 when its score is
+        NaN.  scores[p] == predict(features)[users[p], items[p]] exactly.  Order and duplicates of the pairs are
+        kept.  `features` as in `predict`.  Nothing m x n is formed, and there is no limit like `recommend`'s
+        N <= 128: one fused kernel scores the catalogue and counts (als_rank_count).  Local to the calling rank."""
+        features = self._check_predict(features)
+        u, i = self._check_pairs(users, items, self.U.shape[0])
+        if u.size == 0:
+            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
+        with _on(self._eng.dev):
+            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
+            is_ = torch.from_numpy(i.astype(np.int32)).to(self._eng.dev)
+            return self._eng.rank_of(us, is_, features, exclude_seen)
+
+    def rank_of_new(self, R_new, targets, *, features: Optional[Dict[str, np.ndarray]] = None,
+                    n_sweeps: Optional[int] = None, exclude_seen: bool = True):
+        """`rank_of` for users outside the fit: `fold_in(R_new, features=features, n_sweeps=n_sweeps)`, then the
+        ranks of each new row's target items among the candidates `recommend_new` ranks (with `exclude_seen` the
+        items rated in R_new are no candidates).  `targets` = (indptr [B + 1], items): row b's targets are
+        items[indptr[b]:indptr[b + 1]].  Returns (rank, n_candidates, scores) as `rank_of`, one entry per target in
+        the order of `items`."""
+        features = self._check_predict(features)
+        T = self._check_sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        B = indptr.size - 1
+        if not isinstance(targets, (tuple, list)) or len(targets) != 2:
+            raise ValueError("targets must be (indptr, items)")
+        tptr = np.asarray(targets[0])
+        if tptr.ndim != 1 or tptr.size != B + 1 or not np.issubdtype(tptr.dtype, np.integer):
+            raise ValueError(f"targets indptr must hold {B + 1} integers (one row per row of R_new)")
+        tptr = tptr.astype(np.int64)
+        _, ti = self._check_pairs(np.zeros(np.asarray(targets[1]).shape, dtype=np.int64), targets[1], None)
+        if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
+            raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
+        if ti.size == 0:
+            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
+        with _on(self._eng.dev):
+            return self._eng.rank_of_new(indptr, indices, vals, tptr, ti.astype(np.int32), features, T, exclude_seen)
+
+    def _seen_pairs(self, users, items) -> np.ndarray:
+        """bool [P]: items[p] is among the ratings of users[p] in the last fit (what `exclude_seen` leaves out)."""
+        u, i = self._check_pairs(users, items, self.U.shape[0])
+        with _on(self._eng.dev):
+            return self._eng.seen_pairs(torch.from_numpy(u).to(self._eng.dev), torch.from_numpy(i).to(self._eng.dev))
+
     # ---------------------------------------------------------- new items
     def fold_in_items(self, C_new=None, *, features_new: Optional[Dict[str, np.ndarray]] = None,
                       features: Optional[Dict[str, np.ndarray]] = None, S_new=None,
@@ -1528,6 +1596,83 @@ class _Engine:
             items[b0: b0 + nb] = top_idx.cpu().numpy()
             scores[b0: b0 + nb] = top_val.cpu().numpy()
         return items, scores
+
+    def _rank_outputs(self, above, ncand_rows, counts, score, order=None):
+        rank = above.to(torch.int64)
+        cand = torch.repeat_interleave(ncand_rows.to(torch.int64), counts)
+        if order is not None:
+            inv = torch.empty_like(order)
+            inv[order] = torch.arange(order.numel(), device=order.device)
+            rank, cand, score = rank[inv], cand[inv], score[inv]
+        return rank.cpu().numpy(), cand.cpu().numpy(), score.cpu().numpy()
+
+    def rank_of(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool):
+        """Ranks of the pairs (us[p], is_[p]) (int32, device): the pairs are grouped by user on the device, every
+        user of a REC_BATCH chunk is scored once (als_rank_count), and the outputs go back to the pairs' order:
+        (rank int64 [P], n_candidates int64 [P], scores float32 [P]).  Z and the seen items as in `recommend`."""
+        Z = self._compose_for(features)
+        seen_ptr = seen_idx = None
+        if exclude_seen and self.nnz > 0:
+            seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
+        P = us.numel()
+        order = torch.sort(us.to(torch.int64), stable=True).indices
+        q_items = is_[order].contiguous()
+        uniq, counts = torch.unique_consecutive(us[order], return_counts=True)
+        nu = uniq.numel()
+        ptr = torch.zeros(nu + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        ptr_h = ptr.cpu().numpy()
+        above = torch.empty(P, dtype=torch.int32, device=self.dev)
+        score = torch.empty(P, dtype=torch.float32, device=self.dev)
+        ncand = torch.empty(nu, dtype=torch.int32, device=self.dev)
+        for b0 in range(0, nu, self.REC_BATCH):
+            nb = min(self.REC_BATCH, nu - b0)
+            t0, t1 = int(ptr_h[b0]), int(ptr_h[b0 + nb])
+            self.be.rank_count(k=self.k, ld=self.ld, n=self.n, U=self.U, Z=Z, b_u=self.b_u, b_i=self.b_i, mu=self.mu,
+                               seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=uniq[b0: b0 + nb],
+                               q_ptr=(ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
+                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb])
+        return self._rank_outputs(above, ncand, counts, score, order)
+
+    def rank_of_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, features, n_sweeps: int,
+                    exclude_seen: bool):
+        """Fold in, then als_rank_count on the folded table (batch row b = new row b, the given ratings as the seen
+        CSR, as `recommend_new` composes it) for the targets titems[tptr[b]:tptr[b + 1]], in REC_BATCH chunks."""
+        Z = self._compose_for(features)
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        B = indptr.size - 1
+        tptr_d = torch.from_numpy(tptr).to(self.dev)
+        q_items = torch.from_numpy(titems).to(self.dev)
+        P = q_items.numel()
+        above = torch.empty(P, dtype=torch.int32, device=self.dev)
+        score = torch.empty(P, dtype=torch.float32, device=self.dev)
+        ncand = torch.empty(B, dtype=torch.int32, device=self.dev)
+        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            seen_ptr = seen_idx = None
+            if exclude_seen and indptr[b0 + nb] > indptr[b0]:
+                seen_ptr, seen_idx = ptr_d[b0: b0 + nb + 1], idx_d
+            t0, t1 = int(tptr[b0]), int(tptr[b0 + nb])
+            self.be.rank_count(k=self.k, ld=self.ld, n=self.n, U=U[b0:], Z=Z, b_u=b[b0:], b_i=self.b_i, mu=self.mu,
+                               seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users[:nb],
+                               q_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
+                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb])
+        return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
+
+    def seen_pairs(self, us: torch.Tensor, is_: torch.Tensor) -> np.ndarray:
+        """bool [P]: (us[p], is_[p]) (int64, device) is an entry of the training CSR (a binary search per pair)."""
+        if self.nnz == 0:
+            return np.zeros(us.numel(), dtype=bool)
+        ptr, idx = self.csr.indptr, self.csr.indices
+        lo, hi = ptr[us].clone(), ptr[us + 1].clone()
+        end = hi.clone()
+        while bool((lo < hi).any()):                                     # first entry >= the item
+            act, mid = lo < hi, (lo + hi) >> 1
+            below = act & (idx[mid.clamp(max=idx.numel() - 1)] < is_)
+            lo, hi = torch.where(below, mid + 1, lo), torch.where(act & ~below, mid, hi)
+        found = (lo < end) & (idx[lo.clamp(max=idx.numel() - 1)] == is_)
+        return found.cpu().numpy()
 
     # ----------------------------------------------------------- new items
     GRAPH_ROWS_MAX_D = 160      # sim feature width the top-k kernel takes (its k)

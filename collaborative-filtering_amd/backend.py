@@ -48,6 +48,7 @@ class HipBackend:
         self._stats_partials: Optional[torch.Tensor] = None
         self._spd_ws: Optional[torch.Tensor] = None
         self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
+        self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -306,6 +307,24 @@ class HipBackend:
                                                 _p(mu), _p(seen_ptr), _p(seen_idx), topn, nsl, _p(top_val),
                                                 _p(top_idx), _p(top_cnt), _p(self._rec_ws) if need > 0 else None, need,
                                                 self._stream()), "als_recommend_topk")
+
+    def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score,
+                   above, n_cand):
+        """For every target of every batch row (user q_users[b], targets q_items[q_ptr[b]:q_ptr[b+1]]) the score
+        and the number of unseen items ranked above it, and per row the number of candidates: als_rank_count.
+        The item-slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
+        if seen_idx is not None and seen_idx.numel() == 0:
+            seen_ptr = seen_idx = None
+        nq, nt = q_users.numel(), q_items.numel()
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_rank_count_workspace_bytes(k, nq, nt, n, nsl))
+        if need > 0 and (self._rank_ws is None or self._rank_ws.numel() < need):
+            self._rank_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_rank_count(k, ld, n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr),
+                                            _p(seen_idx), nq, _p(q_users), _p(q_ptr), _p(q_items) if nt else None, nt,
+                                            nsl, _p(t_score) if nt else None, _p(above) if nt else None, _p(n_cand),
+                                            _p(self._rank_ws) if need > 0 else None, need, self._stream()),
+                    "als_rank_count")
 
     # -- K9 --------------------------------------------------------------------
     def fold_in(self, *, k, ld, indptr, indices, vals, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, U_out, b_u_out,

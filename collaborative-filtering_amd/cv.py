@@ -13,6 +13,7 @@ schema, so that results can be compared file by file:
   metrics      rmse_at, popularity_bins, split_by_popularity            tune_params.py:147-167,
                                                                         evaluate_models.py:131-191
                ranking_at_k (recall@K / NDCG@K of ALS.recommend)        new: the reference has RMSE only
+               rank_metrics (recall / NDCG at any K, MRR, AUC, MPR from ALS.rank_of)    new
   statistics   aggregate_convergence, aggregate_bins_mean,              evaluate_models.py:279-379
                sign_test_paired, fdr_bh
   variants     variant_grid                                             evaluate_models.py:382-455
@@ -203,6 +204,137 @@ def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating
     np.cumsum(np.bincount(pos, minlength=users.size), out=indptr[1:])
     items, _ = model.recommend_new((indptr, kc[order], kv[order]), K, features=features, n_sweeps=n_sweeps)
     return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
+
+
+def _check_Ks(Ks) -> Tuple[int, ...]:
+    Ks = tuple(Ks)
+    for K in Ks:
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+            raise ValueError(f"every K must be an integer >= 1, got {K!r}")
+    return tuple(int(K) for K in Ks)
+
+
+def _empty_rank_metrics(Ks, pairs: int, dropped: int) -> Dict[str, Any]:
+    out: Dict[str, Any] = {"users": 0, "pairs": pairs, "dropped": dropped}
+    for name in [f"{a}@{K}" for K in Ks for a in ("recall", "ndcg")] + ["mrr", "auc", "mpr"]:
+        out[name] = float("nan")
+    return out
+
+
+def _rank_metrics(ub: np.ndarray, rank: np.ndarray, cand: np.ndarray, dropped: int, Ks) -> Dict[str, Any]:
+    """Means over users of the rank measures (see rank_metrics) from the kept pairs: user position ub, 0-based
+    rank, candidate count of the pair's user.  The ranks of one user are distinct (a total order over distinct
+    candidate items)."""
+    if ub.size == 0:
+        return _empty_rank_metrics(Ks, 0, dropped)
+    order = np.lexsort((rank, ub))                                      # by user, ranks ascending within a user
+    ub, rho, cand = ub[order], rank[order].astype(np.float64), cand[order].astype(np.float64)
+    users, first, nrel = np.unique(ub, return_index=True, return_counts=True)
+    pos = np.arange(ub.size) - np.repeat(first, nrel)                   # relevant items ranked above, same user
+    c = cand[first]
+    out: Dict[str, Any] = {"users": int(users.size), "pairs": int(ub.size), "dropped": int(dropped)}
+    disc_t = 1.0 / np.log2(rho + 2.0)                                   # rank r = rho + 1
+    ideal = np.cumsum(1.0 / np.log2(np.arange(2, int(nrel.max()) + 2, dtype=np.float64)))
+    for K in Ks:
+        hit = rho < K
+        out[f"recall@{K}"] = float(np.mean(np.add.reduceat(hit.astype(np.float64), first) / nrel))
+        dcg = np.add.reduceat(np.where(hit, disc_t, 0.0), first)
+        out[f"ndcg@{K}"] = float(np.mean(dcg / ideal[np.minimum(nrel, K) - 1]))
+    out["mrr"] = float(np.mean(1.0 / (1.0 + rho[first])))
+    neg = c - nrel                                                      # candidates that are not relevant
+    ok = neg > 0
+    inv = np.add.reduceat(rho - pos, first)                             # (irrelevant, relevant) pairs in the wrong order
+    out["auc"] = float(np.mean(1.0 - inv[ok] / (nrel[ok] * neg[ok]))) if ok.any() else float("nan")
+    out["mpr"] = float(np.mean(np.add.reduceat(rho / np.maximum(np.repeat(c, nrel) - 1.0, 1.0), first) / nrel))
+    return out
+
+
+def _held_out_pairs(rows, cols, vals, min_rating, what: str = ""):
+    rows = np.asarray(rows, dtype=np.int64).ravel()
+    cols = np.asarray(cols, dtype=np.int64).ravel()
+    if rows.shape != cols.shape:
+        raise ValueError(f"{what}rows and cols must have the same length")
+    if min_rating is not None:
+        if vals is None:
+            raise ValueError("min_rating needs the held-out ratings (vals)")
+        keep = np.asarray(vals, dtype=np.float64).ravel() >= min_rating
+        rows, cols = rows[keep], cols[keep]
+    return rows, cols
+
+
+def rank_metrics(model: ALS, rows, cols, vals=None, *, Ks: Sequence[int] = (10, 100),
+                 min_rating: Optional[float] = None,
+                 features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+    """Full-catalogue ranking measures of held-out (user, item) pairs from exact ranks (`model.rank_of`; no
+    sampled negatives, no list limit).  Arguments as `ranking_at_k`.  For every user u of the held-out set, with
+    rel(u) as in `ranking_at_k` (duplicates merged), c(u) the number of candidates (items that are neither
+    training items of the fit nor NaN-scored) and rho_t the 0-based rank of t among them:
+
+      a pair whose item is a training item of u, or whose score is NaN, is DROPPED (it cannot be ranked among the
+      candidates) and counted in "dropped"; R(u) is what is left, users with an empty R(u) are left out;
+      recall@K(u) = |{t in R(u): rho_t < K}| / |R(u)|, NDCG@K(u) as `ranking_at_k` with "t in top-K" = rho_t < K,
+          for every K of `Ks` (any K >= 1);
+      mrr(u)      = 1 / (1 + min_t rho_t);
+      auc(u)      = 1 - sum_t (rho_t - #{t' in R(u): rho_t' < rho_t}) / (|R(u)| (c(u) - |R(u)|)): the fraction of
+                    (relevant, other candidate) pairs the model orders correctly; users with c(u) = |R(u)| are
+                    left out of this mean only;
+      mpr(u)      = mean over t of rho_t / max(c(u) - 1, 1)   (mean percentile rank, 0 = best).
+
+    Returns the means over users under "recall@K", "ndcg@K" (per K), "mrr", "auc", "mpr", with "users", "pairs"
+    (kept, after merging) and "dropped" (NaN means when no user is left)."""
+    Ks = _check_Ks(Ks)
+    rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
+    if rows.size:
+        w = max(model.V.shape[0] if model.V is not None else 1, int(cols.max()) + 1)
+        rows, cols = np.divmod(np.unique(rows * w + cols), w)           # duplicates merged
+    rank, cand, _ = model.rank_of(rows, cols, features=features)
+    if rows.size == 0:
+        return _empty_rank_metrics(Ks, 0, 0)
+    keep = ~model._seen_pairs(rows, cols) & (rank >= 0)
+    _, ub = np.unique(rows[keep], return_inverse=True)
+    return _rank_metrics(ub, rank[keep], cand[keep], int((~keep).sum()), Ks)
+
+
+def fold_in_rank_metrics(model: ALS, known, held_out, *, Ks: Sequence[int] = (10, 100),
+                         min_rating: Optional[float] = None, features: Optional[Dict[str, np.ndarray]] = None,
+                         n_sweeps: Optional[int] = None) -> Dict[str, Any]:
+    """`rank_metrics` for users outside the fit (strong generalisation), with the conventions of
+    `fold_in_ranking_at_k`: every user of `held_out` is folded in from its `known` ratings (`model.rank_of_new`,
+    the known items are no candidates) and its held-out items are ranked.  A held-out pair whose item is among the
+    user's known items is dropped and counted, as is one with a NaN score."""
+    Ks = _check_Ks(Ks)
+    if len(known) != 3:
+        raise ValueError("known must be (rows, cols, vals)")
+    if len(held_out) not in (2, 3):
+        raise ValueError("held_out must be (rows, cols) or (rows, cols, vals)")
+    if min_rating is not None and len(held_out) != 3:
+        raise ValueError("min_rating needs the held-out ratings (vals)")
+    rows, cols = _held_out_pairs(held_out[0], held_out[1], held_out[2] if len(held_out) == 3 else None, min_rating,
+                                 "held-out ")
+    if rows.size == 0:
+        model._check_predict(features)
+        return _empty_rank_metrics(Ks, 0, 0)
+    users, ub = np.unique(rows, return_inverse=True)
+    w = max(model.V.shape[0] if model.V is not None else 1, int(cols.max()) + 1)
+    ub, cols = np.divmod(np.unique(ub * w + cols), w)                   # by user position, duplicates merged
+    kr = np.asarray(known[0], dtype=np.int64).ravel()
+    kc = np.asarray(known[1], dtype=np.int64).ravel()
+    kv = np.asarray(known[2], dtype=np.float64).ravel()
+    if not kr.shape == kc.shape == kv.shape:
+        raise ValueError("known rows, cols and vals must have the same length")
+    pos = np.searchsorted(users, kr)
+    mine = (pos < users.size) & (users[np.minimum(pos, users.size - 1)] == kr)     # known ratings of scored users
+    pos, kc, kv = pos[mine], kc[mine], kv[mine]
+    order = np.argsort(pos, kind="stable")
+    indptr = np.zeros(users.size + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pos, minlength=users.size), out=indptr[1:])
+    tptr = np.zeros(users.size + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ub, minlength=users.size), out=tptr[1:])
+    rank, cand, _ = model.rank_of_new((indptr, kc[order], kv[order]), (tptr, cols), features=features,
+                                      n_sweeps=n_sweeps)
+    keep = ~np.isin(ub * w + cols, pos * w + kc) & (rank >= 0)
+    _, ubk = np.unique(ub[keep], return_inverse=True)
+    return _rank_metrics(ubk, rank[keep], cand[keep], int((~keep).sum()), Ks)
 
 
 def cold_item_rmse(model: ALS, held_out, *, known=None, features_new: Optional[Dict[str, np.ndarray]] = None,

@@ -410,6 +410,32 @@ int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int6
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Exact full-catalogue ranks (evaluation).  Model arguments as als_recommend_topk: score(u, j) is bitwise the fp32
+ * value als_predict_dense writes; seen_ptr / seen_idx a CSR by USER ID, ascending (both NULL = exclude nothing).
+ * For user u the candidates are C(u) = { j < n : j not in u's seen row, score(u, j) is not NaN }.
+ * Queries: nq batch rows; row b has user q_users[b] (in [0, m), duplicates allowed) and the targets
+ *   q_items[q_ptr[b] .. q_ptr[b+1]) (q_ptr [nq+1] int64, q_ptr[0] = 0, q_ptr[nq] = nt; items in [0, n), any order,
+ *   duplicates allowed, any number per row: a row with more than 16 targets is served by further passes over
+ *   the catalogue inside the kernel).
+ * Outputs, per target t of row b (position p in q_items), u = q_users[b]:
+ *   t_score[p] = score(u, t);
+ *   above[p]   = |{ j in C(u) : score(u, j) > score(u, t), or score(u, j) == score(u, t) and j < t }| - the number
+ *                of candidates that precede t in als_recommend_topk's order (score descending, item ascending;
+ *                -0.0 == +0.0).  Defined whether or not t is seen (t never precedes itself); -1 if score(u, t) is NaN.
+ *   n_cand[b]  = |C(u)|.
+ * n < 2^31; nq == 0 is a no-op.  nslices as als_recommend_topk (0 = automatic; the counts of the item slices are
+ *   added by a second launch, so the result does not depend on it).
+ * workspace: als_rank_count_workspace_bytes(k, nq, nt, n, nslices) bytes of device memory (0: may be NULL); the
+ *   call allocates nothing.
+ * ------------------------------------------------------------------------- */
+size_t als_rank_count_workspace_bytes(int k, int64_t nq, int64_t nt, int64_t n, int nslices);
+int als_rank_count(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u, const float* b_i,
+                   const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx, int64_t nq,
+                   const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items, int64_t nt, int nslices,
+                   float* t_score, int32_t* above, int32_t* n_cand, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user
  * half-step (scripts/als.py:411-433) for new rows.  For every row r < nrows of the CSR (indptr [nrows+1] /
  * indices / vals: device, column indices in [0, n), unique and ascending within a row), with S its items, n_r = |S|:
