@@ -22,7 +22,7 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_topk_similarity", "als_graph_classify", "als_normalize_features", "als_impute_col_median",
            "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
            "als_recommend_workspace_bytes", "als_recommend_topk", "als_rank_count_workspace_bytes", "als_rank_count",
-           "als_fold_in", "als_fold_in_items")
+           "als_fold_in", "als_fold_in_items", "als_explain")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -95,6 +95,21 @@ class FoldInItemsParams(C.Structure):
     ]
 
 
+class ExplainParams(C.Structure):
+    """struct als_explain_params (include/als_hip.h)."""
+    _fields_ = [
+        ("k", _i32), ("ld", _i32), ("nrows", _i64), ("n_sweeps", _i32), ("topm", _i32), ("largest", _i32),
+        ("reserved", _i32),
+        ("indptr", _vp), ("indices", _vp), ("vals", _vp), ("rows", _vp),
+        ("n", _i64), ("Z", _vp), ("b_i", _vp), ("mu", _vp),
+        ("lambda_u", _f32), ("lambda_bu", _f32),
+        ("t_ptr", _vp), ("t_items", _vp),
+        ("score", _vp), ("latent", _vp), ("leverage", _vp),
+        ("top_item", _vp), ("top_contrib", _vp), ("top_weight", _vp), ("top_cnt", _vp),
+        ("b_u_out", _vp), ("status", _vp),
+    ]
+
+
 class HipLibraryMissing(RuntimeError):
     pass
 
@@ -150,6 +165,7 @@ def load():
                                    _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_fold_in.argtypes = [C.POINTER(FoldInParams), _vp]
     lib.als_fold_in_items.argtypes = [C.POINTER(FoldInItemsParams), _vp]
+    lib.als_explain.argtypes = [C.POINTER(ExplainParams), _vp]
     lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]

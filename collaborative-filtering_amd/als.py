@@ -207,6 +207,30 @@ class FoldedItems:
         return int(self.b_i.shape[0])
 
 
+@dataclass
+class Explanation:
+    """What `ALS.explain` / `explain_new` return for P (row, target) pairs, all float64 / int64 host arrays.
+
+    score, latent, leverage, b_u: [P] - the half-step user's score mu + b_u + b_i[i] + latent, its latent part
+    u.z_i (the sum of ALL the row's contributions), z_i^T A^-1 z_i, and the user bias.  items [P, M] (-1 padded),
+    contributions, weights [P, M] (0 padded): the M strongest rated items with contribution = weight * (r_j - mu -
+    b_i[j] - b) and weight = z_i^T A^-1 z_j.  counts [P] = min(M, ratings of the row)."""
+    score: np.ndarray
+    latent: np.ndarray
+    leverage: np.ndarray
+    b_u: np.ndarray
+    items: np.ndarray
+    contributions: np.ndarray
+    weights: np.ndarray
+    counts: np.ndarray
+
+    @staticmethod
+    def empty(M: int) -> "Explanation":
+        z = lambda *sh: np.empty(sh, dtype=np.float64)                  # noqa: E731
+        return Explanation(z(0), z(0), z(0), z(0), np.empty((0, M), dtype=np.int64), z(0, M), z(0, M),
+                           np.empty(0, dtype=np.int64))
+
+
 def new_item_features(features_new, W_dims: Dict[str, int], B: int) -> Dict[str, np.ndarray]:
     """Validated features of new items: every feature of the fit (`W_dims`: name -> columns) and nothing else, each
     a finite (B, d) array.  Raises ValueError otherwise."""
@@ -681,6 +705,68 @@ class ALS:
         u, i = self._check_pairs(users, items, self.U.shape[0])
         with _on(self._eng.dev):
             return self._eng.seen_pairs(torch.from_numpy(u).to(self._eng.dev), torch.from_numpy(i).to(self._eng.dev))
+
+    # ---------------------------------------------------------- explanation
+    @staticmethod
+    def _check_topm(M) -> int:
+        if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= RECOMMEND_MAX_N:
+            raise ValueError(f"M must be an integer in [1, {RECOMMEND_MAX_N}], got {M!r}")
+        return int(M)
+
+    def explain(self, users, items, M: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                n_sweeps: Optional[int] = None, largest: bool = True) -> Explanation:
+        """Why item items[p] scores what it scores for user users[p] of the fit, P pairs: an `Explanation`.
+
+        The row is the user's training row and the explained factor is the user's HALF-STEP at the final item side
+        (Z, b_i, mu): u = A^-1 sum_j z_j rho_j with A = Z_S^T Z_S + lambda_u I over the rated items S - exactly
+        what `fold_in` computes from that row (`n_sweeps` as there; None = the fixed point).  It is linear in the
+        ratings, so its latent score splits exactly: contribution[j] = (z_i^T A^-1 z_j) (r_j - mu - b_i[j] - b) and
+        latent = sum_j contribution[j].  The fitted `U[u]` was solved one item update earlier and is NOT a linear
+        function of the final Z, so it has no exact decomposition; `score` is the half-step user's score - compare
+        it with `predict` to see how far the two are apart.  leverage = z_i^T A^-1 z_i is the ridge posterior
+        variance of the latent score up to the noise variance: near 0 when the user's history pins down the
+        direction of z_i, up to |z_i|^2 / lambda_u when it says nothing about it.
+
+        The M <= 128 strongest rated items per pair, ordered by (float32(contribution) descending, item ascending);
+        `largest=False`: the items that pulled the score down most first.  Values are float64 (fp64 arithmetic on
+        the fp32 device tables).  A user without ratings: no contributions, latent 0, leverage |z_i|^2 / lambda_u,
+        score mu + b_i[i].  Order and duplicates of the pairs are kept; `features` as in `predict`.  One kernel
+        (als_explain) per 65 536 distinct users.  Local to the calling rank, like `rank_of`."""
+        features = self._check_predict(features)
+        M = self._check_topm(M)
+        T = self._check_sweeps(n_sweeps)
+        u, i = self._check_pairs(users, items, self.U.shape[0])
+        if u.size == 0:
+            return Explanation.empty(M)
+        with _on(self._eng.dev):
+            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
+            is_ = torch.from_numpy(i.astype(np.int32)).to(self._eng.dev)
+            return self._eng.explain(us, is_, M, features, T, bool(largest))
+
+    def explain_new(self, R_new, targets, M: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                    n_sweeps: Optional[int] = None, largest: bool = True) -> Explanation:
+        """`explain` for users outside the fit - the users `recommend_new` / `rank_of_new` serve, for whom the
+        half-step user IS the served user: `R_new` as `fold_in`, `targets` = (indptr [B + 1], items) as
+        `rank_of_new`.  One entry per target, in the order of `items`."""
+        features = self._check_predict(features)
+        M = self._check_topm(M)
+        T = self._check_sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        B = indptr.size - 1
+        if not isinstance(targets, (tuple, list)) or len(targets) != 2:
+            raise ValueError("targets must be (indptr, items)")
+        tptr = np.asarray(targets[0])
+        if tptr.ndim != 1 or tptr.size != B + 1 or not np.issubdtype(tptr.dtype, np.integer):
+            raise ValueError(f"targets indptr must hold {B + 1} integers (one row per row of R_new)")
+        tptr = tptr.astype(np.int64)
+        _, ti = self._check_pairs(np.zeros(np.asarray(targets[1]).shape, dtype=np.int64), targets[1], None)
+        if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
+            raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
+        if ti.size == 0:
+            return Explanation.empty(M)
+        with _on(self._eng.dev):
+            return self._eng.explain_new(indptr, indices, vals, tptr, ti.astype(np.int32), M, features, T,
+                                         bool(largest))
 
     # ---------------------------------------------------------- new items
     def fold_in_items(self, C_new=None, *, features_new: Optional[Dict[str, np.ndarray]] = None,
@@ -1659,6 +1745,81 @@ class _Engine:
                                q_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
                                t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb])
         return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
+
+    def _explain_rows(self, ptr_d, idx_d, val_d, rows_d, tptr_d, tptr_h: np.ndarray, q_items, Z, M: int,
+                      n_sweeps: int, largest: bool, row_name):
+        """als_explain over W work rows in REC_BATCH chunks.  rows_d (int32 [W]) names the CSR row of every work
+        row; None: work row w is CSR row w.  Targets q_items[tptr[w]:tptr[w + 1]].  Returns the device outputs in
+        target order and b_u per work row.  row_name(w): how an error names work row w."""
+        md = self.model
+        W, P = tptr_h.size - 1, q_items.numel()
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        score, latent, lev = (torch.empty(P, **f64) for _ in range(3))
+        top_item = torch.empty(P, M, dtype=torch.int32, device=self.dev)
+        top_c, top_w = torch.empty(P, M, **f64), torch.empty(P, M, **f64)
+        top_cnt = torch.empty(P, dtype=torch.int32, device=self.dev)
+        b_u = torch.empty(W, **f64)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if idx_d.numel() == 0:          # no row has ratings: the library wants valid pointers
+            idx_d = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            val_d = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        for b0 in range(0, W, self.REC_BATCH):
+            nb = min(self.REC_BATCH, W - b0)
+            t0, t1 = int(tptr_h[b0]), int(tptr_h[b0 + nb])
+            if t1 == t0:
+                b_u[b0: b0 + nb] = float("nan")                          # rows without targets: never read
+                continue
+            # views: without rows_d work row w of the chunk reads ptr_d[b0 + w]; the offsets stay absolute
+            self.be.explain(k=self.k, ld=self.ld, indptr=ptr_d if rows_d is not None else ptr_d[b0: b0 + nb + 1],
+                            indices=idx_d, vals=val_d, rows=None if rows_d is None else rows_d[b0: b0 + nb],
+                            n=self.n, Z=Z, b_i=self.b_i, mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu,
+                            n_sweeps=n_sweeps, t_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(),
+                            t_items=q_items[t0:t1], topm=M, largest=largest, score=score[t0:t1],
+                            latent=latent[t0:t1], leverage=lev[t0:t1], top_item=top_item[t0:t1],
+                            top_contrib=top_c[t0:t1], top_weight=top_w[t0:t1], top_cnt=top_cnt[t0:t1],
+                            b_u_out=b_u[b0: b0 + nb], status=status)
+            bad = int(status.item())
+            if bad:
+                raise np.linalg.LinAlgError(
+                    f"fold-in normal equations of {row_name(b0 + bad - 1)} are not positive definite")
+        return score, latent, lev, b_u, top_item, top_c, top_w, top_cnt
+
+    @staticmethod
+    def _explanation(score, latent, lev, b_u_t, top_item, top_c, top_w, top_cnt, inv=None) -> "Explanation":
+        outs = [score, latent, lev, b_u_t, top_item.to(torch.int64), top_c, top_w, top_cnt.to(torch.int64)]
+        if inv is not None:
+            outs = [o[inv] for o in outs]
+        return Explanation(*(o.cpu().numpy() for o in outs))
+
+    def explain(self, us: torch.Tensor, is_: torch.Tensor, M: int, features, n_sweeps: int, largest: bool):
+        """Explanations of the pairs (us[p], is_[p]) (int32, device), the rows read from the resident training CSR:
+        the pairs are grouped by user on the device (as `rank_of`), every distinct user of a REC_BATCH chunk is
+        factorised once (als_explain, `rows` = the users), and the outputs go back to the pairs' order."""
+        Z = self._compose_for(features)
+        order = torch.sort(us.to(torch.int64), stable=True).indices
+        q_items = is_[order].contiguous()
+        uniq, counts = torch.unique_consecutive(us[order], return_counts=True)
+        nu = uniq.numel()
+        ptr = torch.zeros(nu + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        uniq = uniq.contiguous()
+        out = self._explain_rows(self.csr.indptr, self.csr.indices, self.csr.vals, uniq, ptr, ptr.cpu().numpy(),
+                                 q_items, Z, M, n_sweeps, largest, lambda w: f"user {int(uniq[w])}")
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.numel(), device=order.device)
+        return self._explanation(*out[:3], torch.repeat_interleave(out[3], counts), *out[4:], inv=inv)
+
+    def explain_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, M: int, features,
+                    n_sweeps: int, largest: bool):
+        """Explanations for new rows (host CSR, rows sorted), targets titems[tptr[b]:tptr[b + 1]] of row b."""
+        Z = self._compose_for(features)
+        ptr_d = torch.from_numpy(indptr).to(self.dev)
+        idx_d = torch.from_numpy(indices).to(self.dev)
+        val_d = torch.from_numpy(vals).to(self.dev)
+        tptr_d = torch.from_numpy(tptr).to(self.dev)
+        out = self._explain_rows(ptr_d, idx_d, val_d, None, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z, M,
+                                 n_sweeps, largest, lambda w: f"row {w}")
+        return self._explanation(*out[:3], torch.repeat_interleave(out[3], tptr_d[1:] - tptr_d[:-1]), *out[4:])
 
     def seen_pairs(self, us: torch.Tensor, is_: torch.Tensor) -> np.ndarray:
         """bool [P]: (us[p], is_[p]) (int64, device) is an entry of the training CSR (a binary search per pair)."""

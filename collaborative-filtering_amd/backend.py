@@ -354,3 +354,21 @@ class HipBackend:
         p.lambda_v, p.lambda_bi, p.alpha = float(lam_v), float(lam_bi), float(alpha)
         p.V_out, p.b_i_out, p.status = _p(V_out), _p(b_i_out), _p(status)
         self._check(self.lib.als_fold_in_items(C.byref(p), self._stream()), "als_fold_in_items")
+
+    # -- K11 -------------------------------------------------------------------
+    def explain(self, *, k, ld, indptr, indices, vals, rows, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, t_ptr, t_items,
+                topm, largest, score, latent, leverage, top_item, top_contrib, top_weight, top_cnt, b_u_out, status):
+        """Per target of every work row (work row w reads CSR row rows[w], or row w when `rows` is None; targets
+        t_items[t_ptr[w]:t_ptr[w+1]]) the score, its latent part, the leverage and the `topm` strongest
+        contributions of the row's ratings: als_explain.  n_sweeps 0 = fixed point."""
+        p = _hip.ExplainParams()
+        p.k, p.ld, p.nrows, p.n_sweeps = k, ld, t_ptr.numel() - 1, int(n_sweeps)
+        p.topm, p.largest = int(topm), int(bool(largest))
+        p.indptr, p.indices, p.vals, p.rows = _p(indptr), _p(indices), _p(vals), _p(rows)
+        p.n, p.Z, p.b_i, p.mu = int(n), _p(Z), _p(b_i), _p(mu)
+        p.lambda_u, p.lambda_bu = float(lam_u), float(lam_bu)
+        p.t_ptr, p.t_items = _p(t_ptr), _p(t_items)
+        p.score, p.latent, p.leverage = _p(score), _p(latent), _p(leverage)
+        p.top_item, p.top_contrib, p.top_weight, p.top_cnt = _p(top_item), _p(top_contrib), _p(top_weight), _p(top_cnt)
+        p.b_u_out, p.status = _p(b_u_out), _p(status)
+        self._check(self.lib.als_explain(C.byref(p), self._stream()), "als_explain")

@@ -1,7 +1,8 @@
 // fp64 row-solve building blocks shared by K1's fp64 kernels (row_solve_f64.hip) and the fold-in kernel
 // (fold_in.hip): the Gram passes on the fp64 matrix cores, and - used by fold_in.hip; finish_row_f64 keeps its own
 // one-right-hand-side copy inline - the right-looking panel Cholesky of the LDS image with NRHS right-hand sides
-// riding along the forward substitution, and the transposed solve.
+// riding along the forward substitution, and the transposed solve; for explain.hip also the forward substitution on
+// its own (solve_l_f64: a right-hand side that arrives after the factorisation).
 //
 // The image: lower 16x16 blocks of the KP x KP matrix in perm space (perm_to_col), fp64, row-major inside a block,
 // block (I, K) at blk64(I, K) * 256.  Vectors in "rows" form: lane (+ 64 rr) holds perm position lane + 64 rr.
@@ -282,6 +283,39 @@ __device__ __forceinline__ void solve_lt_f64(const double* img, double (&xs)[F64
             const int ic = below ? i : 0;
             const double lpi = img[blk64(p >> 4, ic >> 4) * 256 + (p & 15) * 16 + (ic & 15)];
             xs[rr] = below ? fma(-lpi, xp, xs[rr]) : ((i == p) ? xp : xs[rr]);
+        }
+    }
+}
+
+// L x = b in place (xs holds b on entry, x on exit), the stand-alone form of the forward substitution that rides
+// along cholesky_f64: per 16-column panel every lane takes the panel part of its rows from the factorised image
+// (rows above the panel: a dummy row, never applied), the panel's unknowns are broadcast one by one
+template <int KB>
+__device__ __forceinline__ void solve_l_f64(const double* img, double (&xs)[F64Cfg<KB>::NR],
+                                            const double (&dinv)[F64Cfg<KB>::NR], int lane) {
+    constexpr int KP = F64Cfg<KB>::KP, NR = F64Cfg<KB>::NR;
+#pragma unroll 1
+    for (int J = 0; J < KB; ++J) {
+        double p[NR][16];
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            const int i = min(max(lane + 64 * rr, 16 * J), KP - 1);
+            const double* src = img + blk64(i >> 4, J) * 256 + (i & 15) * 16;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) p[rr][t] = src[t];
+        }
+#pragma unroll
+        for (int T = 0; T < 16; ++T) {
+            const int piv = 16 * J + T, RP = piv >> 6, LP = piv & 63;
+            double xsel = xs[0] * dinv[0];
+#pragma unroll
+            for (int rr = 1; rr < NR; ++rr) xsel = (RP == rr) ? xs[rr] * dinv[rr] : xsel;
+            const double xp = readlane_d(xsel, LP);
+#pragma unroll
+            for (int rr = 0; rr < NR; ++rr) {
+                const int i = lane + 64 * rr;
+                xs[rr] = (i > piv) ? fma(-p[rr][T], xp, xs[rr]) : ((i == piv) ? xp : xs[rr]);
+            }
         }
     }
 }

@@ -337,6 +337,32 @@ def fold_in_rank_metrics(model: ALS, known, held_out, *, Ks: Sequence[int] = (10
     return _rank_metrics(ubk, rank[keep], cand[keep], int((~keep).sum()), Ks)
 
 
+def leverage_calibration(model: ALS, rows, cols, vals, *, features: Optional[Dict[str, np.ndarray]] = None,
+                         n_bins: int = 10) -> Dict[str, Any]:
+    """Does the leverage of `model.explain` order the prediction error?  For held-out ratings (rows, cols, vals) of
+    users of the fit: leverage[p] = z_i^T A^-1 z_i of the pair (`model.explain`), the pairs sorted by leverage
+    (stable: ties keep the order given) and cut into `n_bins` consecutive groups of equal size (the first
+    P mod n_bins groups hold one pair more, as numpy.array_split); per group the mean leverage, the number of pairs
+    and the RMSE of `model.predict_at` on its pairs.  Returns {"leverage": [n_bins], "count": [n_bins],
+    "rmse": [n_bins]} as lists, low leverage first; a group without pairs has count 0 and NaN elsewhere.  A
+    calibrated leverage shows an RMSE that rises along the bins."""
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or n_bins < 1:
+        raise ValueError(f"n_bins must be an integer >= 1, got {n_bins!r}")
+    rows, cols = _held_out_pairs(rows, cols, None, None)
+    vals = np.asarray(vals, dtype=np.float64).ravel()
+    if vals.shape != rows.shape:
+        raise ValueError("rows, cols and vals must have the same length")
+    lev = model.explain(rows, cols, 1, features=features).leverage
+    pred = model.predict_at(rows * model.V.shape[0] + cols, features=features) if rows.size else np.empty(0)
+    err2 = (np.asarray(pred, dtype=np.float64) - vals) ** 2
+    out: Dict[str, Any] = {"leverage": [], "count": [], "rmse": []}
+    for grp in np.array_split(np.argsort(lev, kind="stable"), int(n_bins)):
+        out["count"].append(int(grp.size))
+        out["leverage"].append(float(lev[grp].mean()) if grp.size else float("nan"))
+        out["rmse"].append(float(np.sqrt(err2[grp].mean())) if grp.size else float("nan"))
+    return out
+
+
 def cold_item_rmse(model: ALS, held_out, *, known=None, features_new: Optional[Dict[str, np.ndarray]] = None,
                    features: Optional[Dict[str, np.ndarray]] = None,
                    n_sweeps: Optional[int] = None) -> Dict[str, Any]:

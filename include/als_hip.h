@@ -508,6 +508,56 @@ typedef struct als_fold_in_items_params {
 int als_fold_in_items(const als_fold_in_items_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Explanation of a score: how the ratings of a row make up the score of a target item, and the leverage of the
+ * target.  Work row w < nrows reads row rows[w] of the ratings CSR (rows NULL: row w; indptr / indices / vals:
+ * device, column indices in [0, n), unique and ascending within a row); S its items, n_w = |S|.  With als_fold_in's
+ *   A = Z_S^T Z_S + (lambda_u + 1e-10) I, g, h, s, d and n_sweeps: (u, b_u) as als_fold_in, and bprev the bias u was
+ *   solved with (n_sweeps = 0: b_u = bprev = the fixed point; T >= 1: b_u = b_T, bprev = b_{T-1}),
+ * every target i in t_items[t_ptr[w] .. t_ptr[w+1]) (t_ptr [nrows+1] int64, t_ptr[0] = 0; items in [0, n), any
+ * order, repeats allowed, a target may be in S) gets, all in fp64 from the fp32 tables (position p in t_items):
+ *   rho_j = r_j - mu - b_i[j] - bprev,  w = A^-1 z_i,  weight[j] = w.z_j,  contribution[j] = weight[j] rho_j (j in S);
+ *   latent[p] = sum_j contribution[j] (= u.z_i up to rounding),  leverage[p] = z_i^T A^-1 z_i = |L^-1 z_i|^2,
+ *   score[p] = mu + b_u + b_i[i] + latent[p];
+ *   the topm (1 .. ALS_TOPK_MAX) strongest rated items: top_item / top_contrib / top_weight [nt][topm], ordered by
+ *   (float32(contribution) descending, item ascending) for largest != 0 and by (float32(-contribution) descending,
+ *   item ascending) for largest == 0; the values written are the fp64 ones, only the ordering key is rounded.
+ *   Unused slots: item -1, contribution and weight 0.  top_cnt[p] = min(topm, n_w).
+ * b_u_out [nrows] (double): b_u of the work row.  A row without ratings: u = 0, b_u = 0, latent = 0,
+ * leverage = |z_i|^2 / (lambda_u + 1e-10), score = mu + b_i[i].  A (row, target) result depends only on that row's
+ * ratings and the target.  Sizes and status as als_fold_in (status: max(status, w + 1), the WORK row); nrows == 0
+ * is a no-op.  Every pointer but rows must be valid (device).
+ * ------------------------------------------------------------------------- */
+typedef struct als_explain_params {
+    int k, ld;
+    int64_t nrows;                                  /* work rows */
+    int n_sweeps;                                   /* 0 = fixed point */
+    int topm;
+    int largest;
+    int reserved;
+    const int64_t* indptr;
+    const int32_t* indices;
+    const float* vals;
+    const int32_t* rows;                            /* [nrows] CSR row of each work row, or NULL */
+    int64_t n;
+    const float* Z;
+    const float* b_i;
+    const double* mu;
+    float lambda_u, lambda_bu;
+    const int64_t* t_ptr;
+    const int32_t* t_items;
+    double* score;
+    double* latent;
+    double* leverage;
+    int32_t* top_item;
+    double* top_contrib;
+    double* top_weight;
+    int32_t* top_cnt;
+    double* b_u_out;
+    int32_t* status;
+} als_explain_params;
+int als_explain(const als_explain_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
