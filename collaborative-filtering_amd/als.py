@@ -14,6 +14,13 @@ signature is unchanged):
   fit_coo(rows, cols, vals, shape, ...)   sparse-native entry for large inputs
   predict_at(flat_idx, ...) predictions at flat indices u*n+i without the
                             dense m x n matrix
+  recommend / fold_in / recommend_new / rank_of / rank_of_new / explain / explain_new / fold_in_items /
+  predict_new_items         serving calls on the fitted tables
+
+This module holds the `ALS` facade (each public method: validate, enter the device, call the engine, convert)
+and the fit engine `_Engine`.  The input checks are plain functions in validate.py; the device side of the
+prediction and serving calls is serving._Serving, which `_Engine` inherits.  Names that moved there
+(`Explanation`, `FoldedItems`, `fold_in_csr`, ...) are re-exported here.
 """
 from __future__ import annotations
 
@@ -26,12 +33,14 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import layout
+from . import layout, validate
 from .als_config import ALSConfig
+from .serving import RECOMMEND_MAX_N, Explanation, FoldedItems, _Serving, concat_features  # noqa: F401
+from .validate import fold_in_csr, new_item_features, new_item_graph_csr  # noqa: F401
+from .validate import host_features as _host_features
 
 SCALE_FACTOR = 0.1      # scripts/als.py:93
 EPS = 1e-10             # scripts/als.py:94
-RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
 W_F64_BELOW = 1e-2      # solve_dtype="auto": fp64 V-step by-products when some lambda_w (+ 1e-10) is below this
 
 logger = logging.getLogger(__name__)
@@ -145,136 +154,6 @@ def _validate_graph(ptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, n: 
                          "symmetrise with max(S, S^T) as the reference does")
 
 
-def fold_in_csr(R_new, n: int):
-    """Ratings of users outside the fit -> host CSR (indptr int64 [B+1], indices int32, vals float32), every row's
-    columns ascending (values carried along).  `R_new`: a dense (B, n) array with NaN for missing ratings, or a CSR
-    triple (indptr, indices, vals) in any column order.  Raises ValueError for a wrong dense width, a malformed
-    triple, a duplicate column in a row or a non-finite rating, IndexError for a column outside [0, n)."""
-    if isinstance(R_new, (tuple, list)) and len(R_new) == 3 and not np.isscalar(R_new[0]) and np.ndim(R_new[0]) == 1:
-        indptr = np.asarray(R_new[0])
-        indices = np.asarray(R_new[1])
-        vals = np.asarray(R_new[2])
-        if (indptr.ndim != 1 or indptr.size < 1 or indices.ndim != 1 or vals.ndim != 1
-                or (indptr.size and not np.issubdtype(indptr.dtype, np.integer))
-                or (indices.size and not np.issubdtype(indices.dtype, np.integer))):
-            raise ValueError("R_new as CSR must be 1-D (indptr, indices, vals) with integer indptr / indices")
-        indptr = indptr.astype(np.int64)
-        if (indptr[0] != 0 or (np.diff(indptr) < 0).any() or indptr[-1] != indices.size
-                or indices.size != vals.size):
-            raise ValueError("R_new: indptr must start at 0, not decrease, and end at len(indices) == len(vals)")
-        indices = indices.astype(np.int64)
-        if indices.size and (indices.min() < 0 or indices.max() >= n):
-            raise IndexError(f"R_new: column indices must lie in [0, {n})")
-        vals = vals.astype(np.float64)
-    else:
-        R = np.asarray(R_new, dtype=np.float64)
-        if R.ndim != 2 or R.shape[1] != n:
-            raise ValueError(f"R_new must be a dense (B, {n}) array (NaN = missing) or a CSR triple, "
-                             f"got shape {R.shape}")
-        mask = ~np.isnan(R)
-        indptr = np.zeros(R.shape[0] + 1, dtype=np.int64)
-        np.cumsum(mask.sum(axis=1), out=indptr[1:])
-        indices = np.nonzero(mask)[1].astype(np.int64)
-        vals = R[mask]
-    with np.errstate(over="ignore"):
-        vals32 = vals.astype(np.float32)
-    if not np.isfinite(vals32).all():
-        raise ValueError("R_new contains non-finite ratings (or ones beyond the float32 range)")
-    B = indptr.size - 1
-    row = np.repeat(np.arange(B, dtype=np.int64), np.diff(indptr))
-    order = np.lexsort((indices, row))
-    indices, vals32 = indices[order], vals32[order]
-    if indices.size > 1 and ((np.diff(indices) == 0) & (np.diff(row) == 0)).any():
-        raise ValueError("R_new has a duplicate column within a row")
-    return indptr, indices.astype(np.int32), vals32
-
-
-@dataclass
-class FoldedItems:
-    """Items outside the fit, placed by `ALS.fold_in_items`; folded item b is item n + b in `ALS.recommend`.
-
-    V, Z: float64 [B, k], the fp32 device values (Z = V + sum_f X_new,f W_f, what predictions use); b_i: float64
-    [B].  graph: the graph rows used, (ptr int64 [B+1], idx int32 fitted item ids, val float32), or None without a
-    graph.  ratings: the ratings CSR (ptr int64 [B+1], idx int32 user ids ascending, val float32)."""
-    V: np.ndarray
-    b_i: np.ndarray
-    Z: np.ndarray
-    graph: Optional[tuple]
-    ratings: tuple
-
-    @property
-    def n_items(self) -> int:
-        return int(self.b_i.shape[0])
-
-
-@dataclass
-class Explanation:
-    """What `ALS.explain` / `explain_new` return for P (row, target) pairs, all float64 / int64 host arrays.
-
-    score, latent, leverage, b_u: [P] - the half-step user's score mu + b_u + b_i[i] + latent, its latent part
-    u.z_i (the sum of ALL the row's contributions), z_i^T A^-1 z_i, and the user bias.  items [P, M] (-1 padded),
-    contributions, weights [P, M] (0 padded): the M strongest rated items with contribution = weight * (r_j - mu -
-    b_i[j] - b) and weight = z_i^T A^-1 z_j.  counts [P] = min(M, ratings of the row)."""
-    score: np.ndarray
-    latent: np.ndarray
-    leverage: np.ndarray
-    b_u: np.ndarray
-    items: np.ndarray
-    contributions: np.ndarray
-    weights: np.ndarray
-    counts: np.ndarray
-
-    @staticmethod
-    def empty(M: int) -> "Explanation":
-        z = lambda *sh: np.empty(sh, dtype=np.float64)                  # noqa: E731
-        return Explanation(z(0), z(0), z(0), z(0), np.empty((0, M), dtype=np.int64), z(0, M), z(0, M),
-                           np.empty(0, dtype=np.int64))
-
-
-def new_item_features(features_new, W_dims: Dict[str, int], B: int) -> Dict[str, np.ndarray]:
-    """Validated features of new items: every feature of the fit (`W_dims`: name -> columns) and nothing else, each
-    a finite (B, d) array.  Raises ValueError otherwise."""
-    fn = _host_features(features_new)
-    missing = [f for f in W_dims if f not in fn]
-    if missing:
-        raise ValueError(f"features_new must name every feature of the fit; missing: {missing}")
-    unknown = [f for f in fn if f not in W_dims]
-    if unknown:
-        raise ValueError(f"features_new names features the model was not fitted with: {unknown}")
-    out = {}
-    for f, d in W_dims.items():
-        X = np.asarray(fn[f])
-        if X.ndim != 2 or X.shape != (B, d):
-            raise ValueError(f"Feature '{f}' of the new items has shape {X.shape}; expected ({B}, {d})")
-        if not np.isfinite(X).all():
-            raise ValueError(f"Feature '{f}' of the new items contains non-finite values.")
-        out[f] = X
-    return out
-
-
-def new_item_graph_csr(S_new, B: int, n: int):
-    """Caller-supplied graph rows of new items -> host CSR (ptr int64 [B+1], idx int32 in [0, n), val float32).
-    Raises ValueError for a malformed triple, a wrong row count, an index outside [0, n) or a non-finite weight."""
-    if not (isinstance(S_new, (tuple, list)) and len(S_new) == 3):
-        raise ValueError("S_new must be a CSR triple (ptr, idx, val)")
-    ptr, idx, val = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a) for a in S_new)
-    if (ptr.ndim != 1 or idx.ndim != 1 or val.ndim != 1 or (ptr.size and not np.issubdtype(ptr.dtype, np.integer))
-            or (idx.size and not np.issubdtype(idx.dtype, np.integer))):
-        raise ValueError("S_new must be 1-D (ptr, idx, val) with integer ptr / idx")
-    if ptr.size != B + 1:
-        raise ValueError(f"S_new has {ptr.size - 1} rows; expected {B} (one per new item)")
-    ptr = ptr.astype(np.int64)
-    if ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != idx.size or idx.size != val.size:
-        raise ValueError("S_new: ptr must start at 0, not decrease, and end at len(idx) == len(val)")
-    if idx.size and (idx.min() < 0 or idx.max() >= n):
-        raise ValueError(f"S_new: item indices must lie in [0, {n}) (fitted items)")
-    with np.errstate(over="ignore"):
-        val32 = val.astype(np.float32)
-    if not np.isfinite(val32).all():
-        raise ValueError("S_new contains non-finite weights")
-    return ptr, idx.astype(np.int32), val32
-
-
 def _on(device):
     """Make `device` the current HIP device for the enclosed calls: the C-ABI library launches on the current
     device (and sizes its persistent grids from that device's occupancy), torch only hands it a stream."""
@@ -353,14 +232,6 @@ class SweepNotResident(RuntimeError):
     """The persistent one-launch form of the Laplacian sweep (als_gs_sweep_dataflow) found some of its waves not
     running - another kernel or process held compute units - and gave up; `ALS.fit` then refits with the
     per-level launches, which have no residency requirement."""
-
-
-def _host_features(features):
-    """The features dict with device tensors (e.g. the output of features.normalize_feature_device) brought to the
-    host: the fit keeps float32 / float64 copies of its own in HBM and validates on the host, as the reference."""
-    if not features:
-        return {}
-    return {name: (X.detach().cpu().numpy() if torch.is_tensor(X) else X) for name, X in features.items()}
 
 
 class ALS:
@@ -527,18 +398,13 @@ class ALS:
 
     # -------------------------------------------------------------- predict
     def _check_predict(self, features):
-        features = _host_features(features)
-        if self.U is None or self.V is None:                 # scripts/als.py:554-555
-            raise RuntimeError("Model must be fitted before prediction.")
-        n = self.V.shape[0]
-        features = features or {}
-        for name, X in features.items():                     # scripts/als.py:560-565
-            if X.shape[0] != n:
-                raise ValueError(f"Feature '{name}' has {X.shape[0]} rows. "
-                                 f"Expected number of rows: {n}.")
-            if not np.isfinite(X).all():
-                raise ValueError(f"Feature '{name}' contains infinite values.")
-        return features
+        return validate.predict_features(self, features)
+
+    def _check_pairs(self, users, items):
+        return validate.id_pairs(users, items, self.U.shape[0], self.V.shape[0])
+
+    def _dev_i32(self, a: np.ndarray) -> torch.Tensor:
+        return torch.from_numpy(a.astype(np.int32)).to(self._eng.dev)
 
     def predict(self, features: Optional[Dict[str, np.ndarray]] = None) -> np.ndarray:
         """Completed matrix U Z^T + mu + b_u + b_i, (m, n) float64 (scripts/als.py:532-574)."""
@@ -572,34 +438,15 @@ class ALS:
         ratings are left out as well."""
         features = self._check_predict(features)
         if new_items is not None:
-            self._check_folded(new_items)
-        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= N <= RECOMMEND_MAX_N:
-            raise ValueError(f"N must be an integer in [1, {RECOMMEND_MAX_N}], got {N!r}")
-        N = int(N)
-        m = self.U.shape[0]
-        if users is None:
-            u = np.arange(m, dtype=np.int64)
-        else:
-            u = np.asarray(users)
-            if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
-                raise ValueError("users must be a 1-D array-like of integer user ids")
-            if u.size and (u.min() < 0 or u.max() >= m):
-                raise IndexError(f"user ids must lie in [0, {m})")
+            validate.folded_items(self, new_items)
+        N = validate.top_count(N, "N")
+        u = validate.user_ids(users, self.U.shape[0])
         if u.size == 0:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
-            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
             if new_items is not None:
-                return self._eng.recommend_with_items(us, N, features, exclude_seen, new_items)
-            return self._eng.recommend(us, N, features, exclude_seen)
-
-    @staticmethod
-    def _check_sweeps(n_sweeps) -> int:
-        if n_sweeps is None:
-            return 0
-        if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, (int, np.integer)) or not 1 <= n_sweeps < 2 ** 31:
-            raise ValueError(f"n_sweeps must be None (fixed point) or an integer >= 1, got {n_sweeps!r}")
-        return int(n_sweeps)
+                return self._eng.recommend_with_items(self._dev_i32(u), N, features, exclude_seen, new_items)
+            return self._eng.recommend(self._dev_i32(u), N, features, exclude_seen)
 
     def fold_in(self, R_new, *, features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None):
         """Factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed: returns
@@ -612,7 +459,7 @@ class ALS:
         gets zero factors and bias.  Each row's result depends only on that row's ratings, bitwise.  Local to the
         calling rank."""
         features = self._check_predict(features)
-        T = self._check_sweeps(n_sweeps)
+        T = validate.sweeps(n_sweeps)
         indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
         k, B = self.V.shape[1], indptr.size - 1
         if B == 0:
@@ -628,10 +475,8 @@ class ALS:
         score bitwise the predict epilogue U_b.Z_i + mu + b_b + b_i of the folded row; with `exclude_seen` the
         items rated in R_new are never returned.  The folded factors stay on the device."""
         features = self._check_predict(features)
-        if isinstance(N, bool) or not isinstance(N, (int, np.integer)) or not 1 <= N <= RECOMMEND_MAX_N:
-            raise ValueError(f"N must be an integer in [1, {RECOMMEND_MAX_N}], got {N!r}")
-        N = int(N)
-        T = self._check_sweeps(n_sweeps)
+        N = validate.top_count(N, "N")
+        T = validate.sweeps(n_sweeps)
         indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
         if indptr.size == 1:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
@@ -639,21 +484,6 @@ class ALS:
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen)
 
     # ---------------------------------------------------------- evaluation
-    def _check_pairs(self, users, items, bound_u: Optional[int]):
-        u, i = np.asarray(users), np.asarray(items)
-        if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
-            raise ValueError("users must be a 1-D array-like of integer user ids")
-        if i.ndim != 1 or (i.size and not np.issubdtype(i.dtype, np.integer)):
-            raise ValueError("items must be a 1-D array-like of integer item ids")
-        if u.shape != i.shape:
-            raise ValueError("users and items must have the same length")
-        n = self.V.shape[0]
-        if bound_u is not None and u.size and (u.min() < 0 or u.max() >= bound_u):
-            raise IndexError(f"user ids must lie in [0, {bound_u})")
-        if i.size and (i.min() < 0 or i.max() >= n):
-            raise IndexError(f"item ids must lie in [0, {n})")
-        return u.astype(np.int64), i.astype(np.int64)
-
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True):
         """Exact full-catalogue rank of item items[p] for user users[p], P pairs: returns
         (rank int64 [P], n_candidates int64 [P], scores float32 [P]).
@@ -667,13 +497,11 @@ class ALS:
         kept.  `features` as in `predict`.  Nothing m x n is formed, and there is no limit like `recommend`'s
         N <= 128: one fused kernel scores the catalogue and counts (als_rank_count).  Local to the calling rank."""
         features = self._check_predict(features)
-        u, i = self._check_pairs(users, items, self.U.shape[0])
+        u, i = self._check_pairs(users, items)
         if u.size == 0:
             return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
         with _on(self._eng.dev):
-            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
-            is_ = torch.from_numpy(i.astype(np.int32)).to(self._eng.dev)
-            return self._eng.rank_of(us, is_, features, exclude_seen)
+            return self._eng.rank_of(self._dev_i32(u), self._dev_i32(i), features, exclude_seen)
 
     def rank_of_new(self, R_new, targets, *, features: Optional[Dict[str, np.ndarray]] = None,
                     n_sweeps: Optional[int] = None, exclude_seen: bool = True):
@@ -683,18 +511,10 @@ class ALS:
         items[indptr[b]:indptr[b + 1]].  Returns (rank, n_candidates, scores) as `rank_of`, one entry per target in
         the order of `items`."""
         features = self._check_predict(features)
-        T = self._check_sweeps(n_sweeps)
-        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
-        B = indptr.size - 1
-        if not isinstance(targets, (tuple, list)) or len(targets) != 2:
-            raise ValueError("targets must be (indptr, items)")
-        tptr = np.asarray(targets[0])
-        if tptr.ndim != 1 or tptr.size != B + 1 or not np.issubdtype(tptr.dtype, np.integer):
-            raise ValueError(f"targets indptr must hold {B + 1} integers (one row per row of R_new)")
-        tptr = tptr.astype(np.int64)
-        _, ti = self._check_pairs(np.zeros(np.asarray(targets[1]).shape, dtype=np.int64), targets[1], None)
-        if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
-            raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
+        T = validate.sweeps(n_sweeps)
+        n = self.V.shape[0]
+        indptr, indices, vals = fold_in_csr(R_new, n)
+        tptr, ti = validate.target_lists(targets, indptr.size - 1, n)
         if ti.size == 0:
             return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
         with _on(self._eng.dev):
@@ -702,17 +522,11 @@ class ALS:
 
     def _seen_pairs(self, users, items) -> np.ndarray:
         """bool [P]: items[p] is among the ratings of users[p] in the last fit (what `exclude_seen` leaves out)."""
-        u, i = self._check_pairs(users, items, self.U.shape[0])
+        u, i = self._check_pairs(users, items)
         with _on(self._eng.dev):
             return self._eng.seen_pairs(torch.from_numpy(u).to(self._eng.dev), torch.from_numpy(i).to(self._eng.dev))
 
     # ---------------------------------------------------------- explanation
-    @staticmethod
-    def _check_topm(M) -> int:
-        if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= RECOMMEND_MAX_N:
-            raise ValueError(f"M must be an integer in [1, {RECOMMEND_MAX_N}], got {M!r}")
-        return int(M)
-
     def explain(self, users, items, M: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
                 n_sweeps: Optional[int] = None, largest: bool = True) -> Explanation:
         """Why item items[p] scores what it scores for user users[p] of the fit, P pairs: an `Explanation`.
@@ -733,15 +547,13 @@ class ALS:
         score mu + b_i[i].  Order and duplicates of the pairs are kept; `features` as in `predict`.  One kernel
         (als_explain) per 65 536 distinct users.  Local to the calling rank, like `rank_of`."""
         features = self._check_predict(features)
-        M = self._check_topm(M)
-        T = self._check_sweeps(n_sweeps)
-        u, i = self._check_pairs(users, items, self.U.shape[0])
+        M = validate.top_count(M, "M")
+        T = validate.sweeps(n_sweeps)
+        u, i = self._check_pairs(users, items)
         if u.size == 0:
             return Explanation.empty(M)
         with _on(self._eng.dev):
-            us = torch.from_numpy(u.astype(np.int32)).to(self._eng.dev)
-            is_ = torch.from_numpy(i.astype(np.int32)).to(self._eng.dev)
-            return self._eng.explain(us, is_, M, features, T, bool(largest))
+            return self._eng.explain(self._dev_i32(u), self._dev_i32(i), M, features, T, bool(largest))
 
     def explain_new(self, R_new, targets, M: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
                     n_sweeps: Optional[int] = None, largest: bool = True) -> Explanation:
@@ -749,19 +561,11 @@ class ALS:
         half-step user IS the served user: `R_new` as `fold_in`, `targets` = (indptr [B + 1], items) as
         `rank_of_new`.  One entry per target, in the order of `items`."""
         features = self._check_predict(features)
-        M = self._check_topm(M)
-        T = self._check_sweeps(n_sweeps)
-        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
-        B = indptr.size - 1
-        if not isinstance(targets, (tuple, list)) or len(targets) != 2:
-            raise ValueError("targets must be (indptr, items)")
-        tptr = np.asarray(targets[0])
-        if tptr.ndim != 1 or tptr.size != B + 1 or not np.issubdtype(tptr.dtype, np.integer):
-            raise ValueError(f"targets indptr must hold {B + 1} integers (one row per row of R_new)")
-        tptr = tptr.astype(np.int64)
-        _, ti = self._check_pairs(np.zeros(np.asarray(targets[1]).shape, dtype=np.int64), targets[1], None)
-        if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
-            raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
+        M = validate.top_count(M, "M")
+        T = validate.sweeps(n_sweeps)
+        n = self.V.shape[0]
+        indptr, indices, vals = fold_in_csr(R_new, n)
+        tptr, ti = validate.target_lists(targets, indptr.size - 1, n)
         if ti.size == 0:
             return Explanation.empty(M)
         with _on(self._eng.dev):
@@ -785,9 +589,8 @@ class ALS:
         cosines against the fitted items' sim feature - `features[sim.feature_name]`, by default the fit's own copy
         - positive entries only; a fit with a caller-supplied graph passes the rows as `S_new=(ptr, idx, val)`.
         Each item's result depends only on its own ratings and graph row, bitwise.  Local to the calling rank."""
-        if self.U is None or self.V is None:
-            raise RuntimeError("Model must be fitted before prediction.")
-        T = self._check_sweeps(n_sweeps)
+        validate.fitted(self)
+        T = validate.sweeps(n_sweeps)
         m, n = self.U.shape[0], self.V.shape[0]
         eng = self._eng
         sources = []
@@ -844,32 +647,11 @@ class ALS:
             return FoldedItems(V[:, :k].to(torch.float64).cpu().numpy(), b.to(torch.float64).cpu().numpy(),
                                Z[:, :k].to(torch.float64).cpu().numpy(), graph, ratings)
 
-    def _check_folded(self, folded) -> None:
-        if self.U is None or self.V is None:
-            raise RuntimeError("Model must be fitted before prediction.")
-        if not isinstance(folded, FoldedItems):
-            raise ValueError("new items must be a FoldedItems record (ALS.fold_in_items)")
-        k, B = self.V.shape[1], folded.n_items
-        if folded.Z.shape != (B, k) or folded.b_i.shape != (B,):
-            raise ValueError(f"FoldedItems holds Z {folded.Z.shape} and b_i {folded.b_i.shape}; this model needs "
-                             f"({B}, {k}) and ({B},)")
-        ptr = folded.ratings[0]
-        if len(ptr) != B + 1:
-            raise ValueError("FoldedItems: ratings CSR does not have one row per item")
-
     def predict_new_items(self, folded: FoldedItems, users=None) -> np.ndarray:
         """Scores of folded items: (len(users), B) float64 - all m users in id order for None - each bitwise the
         predict epilogue ((U_u.Z_b + mu) + b_u) + b_b of the fp32 tables (als_predict_dense)."""
-        self._check_folded(folded)
-        m = self.U.shape[0]
-        if users is None:
-            u = np.arange(m, dtype=np.int64)
-        else:
-            u = np.asarray(users)
-            if u.ndim != 1 or (u.size and not np.issubdtype(u.dtype, np.integer)):
-                raise ValueError("users must be a 1-D array-like of integer user ids")
-            if u.size and (u.min() < 0 or u.max() >= m):
-                raise IndexError(f"user ids must lie in [0, {m})")
+        validate.folded_items(self, folded)
+        u = validate.user_ids(users, self.U.shape[0])
         if u.size == 0 or folded.n_items == 0:
             return np.empty((u.size, folded.n_items), dtype=np.float64)
         with _on(self._eng.dev):
@@ -877,8 +659,10 @@ class ALS:
             return self._eng.predict_new_items(us, folded).cpu().numpy().astype(np.float64)
 
 
-class _Engine:
-    """Device state and the iteration loop of one `fit`."""
+class _Engine(_Serving):
+    """Device state and the iteration loop of one `fit`: construction (uploads, sharding, task lists, level
+    schedule), the half steps, the sweep, the W-step, the statistics, and iteration / replay / run / export.
+    What reads the fitted state afterwards is inherited from serving._Serving."""
 
     U_CHUNKS = 2        # sub-ranges of a rank's user shard (multi-rank runs only; ALS_U_CHUNKS overrides)
 
@@ -968,8 +752,6 @@ class _Engine:
         self.ibounds, _ = layout.shard_bounds_nnz(iptr_h, self.world, 1, self.row_cost)
         self.ub, self.ue = self.ubounds[self.rank]
         self.ib, self.ie = self.ibounds[self.rank]
-        m_pad, n_pad = self.m, self.n
-        self.m_pad, self.n_pad = m_pad, n_pad
         dl = layout.dual_max_len(k)          # rows this short are solved in the dual form (k_row_dual)
         dm = layout.dual_mid_len(k)          # ... and rows up to this length above k = 96 (k_row_dual_mid)
         lib = getattr(backend, "lib", None)  # HIP backend: set-up passes in the library (csrc/host_setup.cpp)
@@ -1011,22 +793,19 @@ class _Engine:
         U0d, V0d, W0d = cache.get(init_key, upload_init)
         if model._fit_cache is not None:        # the cached initial state stays pristine
             U0d, V0d, W0d = U0d.clone(), V0d.clone(), [w.clone() for w in W0d]
-        self.U, self.V = U0d[:m_pad], V0d[:n_pad]
-        self.b_u = torch.zeros(m_pad, dtype=f32, device=device)
-        self.b_i = torch.zeros(n_pad, dtype=f32, device=device)
+        self.U, self.V = U0d[: self.m], V0d[: self.n]        # (without the zero row)
+        self.b_u = torch.zeros(self.m, dtype=f32, device=device)
+        self.b_i = torch.zeros(self.n, dtype=f32, device=device)
         self.W64 = dict(zip(self.feat_names, W0d))
         if self.feat_names:
             def upload_features():
-                Xcat = np.concatenate([np.asarray(features[f], dtype=np.float32) for f in self.feat_names], axis=1)
-                Xp = np.zeros((n_pad, Xcat.shape[1]), dtype=np.float32)
-                Xp[: self.n] = Xcat
-                return (torch.from_numpy(Xp).to(device),
+                return (torch.from_numpy(concat_features(features, self.feat_names)).to(device),
                         {f: torch.from_numpy(np.asarray(features[f], dtype=np.float64)).to(device)
                          for f in self.feat_names})
-            fkey = ("features", tuple((f, cache.pin(features[f])) for f in self.feat_names), n_pad)
+            fkey = ("features", tuple((f, cache.pin(features[f])) for f in self.feat_names), self.n)
             self.Xcat, self.X64 = cache.get(fkey, upload_features)
             self.Wcat = torch.zeros(self.Xcat.shape[1], self.ld, dtype=f32, device=device)
-            self.Z = torch.zeros(n_pad + 1, self.ld, dtype=f32, device=device)[:n_pad]
+            self.Z = torch.zeros(self.n + 1, self.ld, dtype=f32, device=device)[: self.n]
             self._sync_wcat()
         else:
             self.Xcat = self.Wcat = None
@@ -1038,9 +817,7 @@ class _Engine:
             lam_v = np.full(self.n, float(model.lambda_v))
         else:
             lam_v = model.lambda_v / np.sqrt(counts + 1.0)
-        lv = np.zeros(n_pad, dtype=np.float32)
-        lv[: self.n] = lam_v
-        self.lam_v_row = torch.from_numpy(lv).to(device)
+        self.lam_v_row = torch.from_numpy(lam_v.astype(np.float32)).to(device)
 
         # --- graph
         self.use_graph = S_csr is not None
@@ -1066,8 +843,7 @@ class _Engine:
 
             self.S_ptr, self.S_idx, self.S_val, D, ptr, idx = cache.get(("graph", kg, bool(model._validate_S)),
                                                                         upload_graph)
-            self.diag_extra = torch.zeros(n_pad, dtype=f32, device=device)
-            self.diag_extra[: self.n] = np.float32(model.alpha) * D
+            self.diag_extra = np.float32(model.alpha) * D
             # Sweep modes with several ranks (one rank: all the same thing):
             #   "exact"  (default) the item shards sweep ONE AFTER THE OTHER in rank order, each followed by a
             #            broadcast of its rows: shard r sees the new rows of shards < r and the old rows of
@@ -1099,7 +875,7 @@ class _Engine:
             self.sched, self.sched_items, wait_dev = cache.get(("sched", kg, ki, lo, hi, bool(self.gs_dataflow)), schedule)
             if self.gs_dataflow:
                 self.S_idx_wait = wait_dev
-                self.gs_publish = torch.empty(n_pad, self.ld, dtype=f32, device=device)       # same shape as V
+                self.gs_publish = torch.empty(self.n, self.ld, dtype=f32, device=device)       # same shape as V
                 self.gs_err = self.gs_err_word
                 # Neighbour sums that do not depend on the sweep can be formed for all items by a parallel launch
                 # before it (same sums, same order).  On graphs without hubs the in-sweep gather hides behind the
@@ -1108,13 +884,13 @@ class _Engine:
                 # when the longest row of S has 1024 neighbours or more; ALS_GS_NONDEP=0 / 1 forces it.
                 nd_env = os.environ.get("ALS_GS_NONDEP")
                 hubs = bool(ptr.size > 1 and int(np.diff(ptr).max()) >= 1024)
-                self.gs_nondep = (torch.empty(n_pad, self.ld, dtype=f32, device=device)
+                self.gs_nondep = (torch.empty(self.n, self.ld, dtype=f32, device=device)
                                   if (nd_env == "1" or (nd_env is None and hubs)) else None)
         # By-products of the V-step exist for this rank's items only ([ib, ie): n / world rows instead of n - the
         # item Grams and Cholesky factors are n * ld^2 floats each, 65 GB at BASELINE configs[4]); the kernels index
         # them with absolute item ids through a shifted base pointer (_RowShift).  The numpy stand-in of the CPU
         # tests indexes tensors directly, so it keeps full-size arrays.
-        self.local_rows = (self.ib, self.ie - self.ib) if lib is not None else (0, n_pad)
+        self.local_rows = (self.ib, self.ie - self.ib) if lib is not None else (0, self.n)
         r0, nloc = self.local_rows
 
         byp = f64 if self.v_f64 else f32           # dtype of the V-step by-products
@@ -1181,10 +957,7 @@ class _Engine:
         return out
 
     def _sync_wcat(self):
-        off = 0
-        for f, d in zip(self.feat_names, self.feat_dims):
-            self.Wcat[off:off + d, : self.k] = self.W64[f].to(torch.float32)
-            off += d
+        self._concat_w(self.feat_names, self.feat_dims, out=self.Wcat)
 
     def _allgather_rows(self, t: torch.Tensor, bounds, async_op: bool = False, tag=None):
         """All-gather of the contiguous, unevenly sized row shards `bounds[r] = (begin, end)` of `t`: every rank
@@ -1278,7 +1051,7 @@ class _Engine:
         finished sub-range (async, on the collective stream) overlaps the solve of the next one.
         """
         md = self.model
-        kw = dict(k=self.k, ld=self.ld, side=self.csr, F=self.Z, zero_row=self.n_pad, bias_self=self.b_u,
+        kw = dict(k=self.k, ld=self.ld, side=self.csr, F=self.Z, zero_row=self.n, bias_self=self.b_u,
                   bias_other=self.b_i, mu=self.mu, lam=md.lambda_u, lam_row=None, lam_b=md.lambda_bu,
                   lam_b_row=None, rhs_extra=None, diag_extra=None, X_out=self.U, bias_out=self.b_u,
                   gram_out=None, factor_out=None, rhs_out=None, colsum_out=None, sumr_out=None,
@@ -1308,7 +1081,7 @@ class _Engine:
         :447,:465): F = U, and the bias update uses V, not Z.
         """
         md = self.model
-        common = dict(k=self.k, ld=self.ld, side=self.csc, F=self.U, zero_row=self.m_pad, bias_self=self.b_i,
+        common = dict(k=self.k, ld=self.ld, side=self.csc, F=self.U, zero_row=self.m, bias_self=self.b_i,
                       bias_other=self.b_u, mu=self.mu, lam=0.0, lam_row=self.lam_v_row,
                       lam_b=md.lambda_bi, lam_b_row=None, rhs_extra=None,
                       gram_out=self.gram if want_gram else None, status=self.status,
@@ -1424,7 +1197,7 @@ class _Engine:
             r0, nloc = self.local_rows
             H = torch.zeros(len(self.feat_names), nloc, ld, dtype=torch.float64 if self.v_f64 else torch.float32,
                             device=self.dev)
-            self.H = _RowShift(H, r0, ld) if r0 or nloc != self.n_pad else H
+            self.H = _RowShift(H, r0, ld) if r0 or nloc != self.n else H
             offs = np.concatenate([[0], np.cumsum(self.feat_dims)]).astype(np.int32)
             self.feat_off_host = offs
             self.feat_off = torch.from_numpy(offs).to(self.dev)
@@ -1557,443 +1330,13 @@ class _Engine:
     # --------------------------------------------------------------- export
     def export(self, model: ALS):
         k = self.k
-        model.U = self.U[: self.m, :k].to(torch.float64).cpu().numpy()
-        model.V = self.V[: self.n, :k].to(torch.float64).cpu().numpy()
-        model.b_u = self.b_u[: self.m].to(torch.float64).cpu().numpy()
-        model.b_i = self.b_i[: self.n].to(torch.float64).cpu().numpy()
+        model.U = self.U[:, :k].to(torch.float64).cpu().numpy()
+        model.V = self.V[:, :k].to(torch.float64).cpu().numpy()
+        model.b_u = self.b_u.to(torch.float64).cpu().numpy()
+        model.b_i = self.b_i.to(torch.float64).cpu().numpy()
         model.mu = float(self.mu.item())
         for f in self.feat_names:
             model.W[f] = self.W64[f].cpu().numpy()
         h = self.hist[: self.iters_run].cpu().numpy()
         for j, key in enumerate(("train_rmse", "U_norm", "V_norm", "bu_norm", "bi_norm")):
             model.history[key].extend(float(x) for x in h[:, j])
-
-    # -------------------------------------------------------------- predict
-    def _compose_for(self, features, features_of_fit: bool = False):
-        """Z for `features` as passed to predict (scripts/als.py:568-572): composed from whatever is passed.
-        `features_of_fit`: the caller vouches that these are the unchanged arrays of the fit (sweep.SweepDriver,
-        which owns them) - the fit's own Z = V + sum_f X_f W_f is then current and nothing is uploaded.  (Round 2
-        inferred that from object identity, which says nothing about the contents and can be recycled.)"""
-        names = [f for f in features if f in self.W64]
-        if not names:
-            return self.V
-        if features_of_fit and self.iters_run > 0 and names == self.feat_names:
-            return self.Z
-        Xcat = np.concatenate([np.asarray(features[f], dtype=np.float32) for f in names], axis=1)
-        Xp = np.zeros((self.n_pad, Xcat.shape[1]), dtype=np.float32)
-        Xp[: self.n] = Xcat
-        W = torch.zeros(Xcat.shape[1], self.ld, dtype=torch.float32, device=self.dev)
-        off = 0
-        for f in names:
-            d = features[f].shape[1]
-            W[off:off + d, : self.k] = self.W64[f].to(torch.float32)
-            off += d
-        Z = torch.empty_like(self.V)
-        self.be.compose_z(self.V, torch.from_numpy(Xp).to(self.dev), W, Z)
-        return Z
-
-    def predict_dense(self, features) -> np.ndarray:
-        Z = self._compose_for(features)
-        out = torch.empty(self.m, self.n, dtype=torch.float32, device=self.dev)
-        self.be.predict_dense(k=self.k, ld=self.ld, m=self.m, n=self.n, U=self.U, Z=Z, b_u=self.b_u,
-                              b_i=self.b_i, mu=self.mu, out=out)
-        return out.cpu().numpy().astype(np.float64)
-
-    def predict_at(self, flat_idx: np.ndarray, features) -> np.ndarray:
-        u, i = np.divmod(flat_idx, self.n)
-        us = torch.from_numpy(u.astype(np.int32)).to(self.dev)
-        is_ = torch.from_numpy(i.astype(np.int32)).to(self.dev)
-        return self.predict_pairs(us, is_, features).cpu().numpy().astype(np.float64)
-
-    REC_BATCH = 1 << 16     # users per als_recommend_topk call: bounds the outputs and the item-slice workspace
-
-    def recommend(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool):
-        """Top-N items of the users in `users_t` (int32, device): (items int64 [B, N], scores float64 [B, N]),
-        unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit.
-        Local to the calling rank: after the all-gathers every rank holds the full U, Z, biases and training CSR,
-        so no collective is issued."""
-        Z = self._compose_for(features)
-        seen_ptr = seen_idx = None
-        if exclude_seen and self.nnz > 0:
-            seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
-        B = users_t.numel()
-        items = np.empty((B, N), dtype=np.int64)
-        scores = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            us = users_t[b0: b0 + self.REC_BATCH]
-            nb = us.numel()
-            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            self.be.recommend_topk(k=self.k, ld=self.ld, users=us, n=self.n, U=self.U, Z=Z, b_u=self.b_u,
-                                   b_i=self.b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
-                                   top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
-            items[b0: b0 + nb] = top_idx.cpu().numpy()
-            scores[b0: b0 + nb] = top_val.cpu().numpy()
-        return items, scores
-
-    def _fold_in_dev(self, indptr: np.ndarray, indices: np.ndarray, vals: np.ndarray, Z, n_sweeps: int):
-        """Folded factors (fp32 [B, ld], zero padding columns) and biases (fp32 [B]) on the device, with the
-        device CSR they were computed from (one als_fold_in launch)."""
-        md = self.model
-        B = indptr.size - 1
-        ptr_d = torch.from_numpy(indptr).to(self.dev)
-        # a one-element buffer when no row has ratings: the library wants valid pointers
-        idx_d = torch.from_numpy(indices if indices.size else np.zeros(1, np.int32)).to(self.dev)
-        val_d = torch.from_numpy(vals if vals.size else np.zeros(1, np.float32)).to(self.dev)
-        U = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
-        b = torch.empty(B, dtype=torch.float32, device=self.dev)
-        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self.be.fold_in(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, n=self.n, Z=Z, b_i=self.b_i,
-                        mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu, n_sweeps=n_sweeps, U_out=U, b_u_out=b,
-                        status=status)
-        bad = int(status.item())
-        if bad:
-            raise np.linalg.LinAlgError(f"fold-in normal equations of row {bad - 1} are not positive definite")
-        return U, b, ptr_d, idx_d
-
-    def fold_in(self, indptr, indices, vals, features, n_sweeps: int):
-        """Factors / biases of new users (host CSR, rows sorted) against this fit's item side: device fp32
-        ([B, ld], [B]).  Z is composed as in `predict`.  Local to the calling rank, like `recommend`."""
-        U, b, _, _ = self._fold_in_dev(indptr, indices, vals, self._compose_for(features), n_sweeps)
-        return U, b
-
-    def recommend_new(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool):
-        """Fold in, then als_recommend_topk on the folded table (batch row b = user b, the given ratings as the
-        seen CSR), in REC_BATCH chunks: (items int64 [B, N], scores float64 [B, N])."""
-        Z = self._compose_for(features)
-        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
-        B = indptr.size - 1
-        items = np.empty((B, N), dtype=np.int64)
-        scores = np.empty((B, N), dtype=np.float64)
-        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            seen_ptr = seen_idx = None
-            if exclude_seen and indptr[b0 + nb] > indptr[b0]:
-                # views: row b of the chunk reads ptr_d[b0 + b]; the offsets stay absolute into idx_d
-                seen_ptr, seen_idx = ptr_d[b0: b0 + nb + 1], idx_d
-            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            self.be.recommend_topk(k=self.k, ld=self.ld, users=users[:nb], n=self.n, U=U[b0:], Z=Z,
-                                   b_u=b[b0:], b_i=self.b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx,
-                                   topn=N, top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
-            items[b0: b0 + nb] = top_idx.cpu().numpy()
-            scores[b0: b0 + nb] = top_val.cpu().numpy()
-        return items, scores
-
-    def _rank_outputs(self, above, ncand_rows, counts, score, order=None):
-        rank = above.to(torch.int64)
-        cand = torch.repeat_interleave(ncand_rows.to(torch.int64), counts)
-        if order is not None:
-            inv = torch.empty_like(order)
-            inv[order] = torch.arange(order.numel(), device=order.device)
-            rank, cand, score = rank[inv], cand[inv], score[inv]
-        return rank.cpu().numpy(), cand.cpu().numpy(), score.cpu().numpy()
-
-    def rank_of(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool):
-        """Ranks of the pairs (us[p], is_[p]) (int32, device): the pairs are grouped by user on the device, every
-        user of a REC_BATCH chunk is scored once (als_rank_count), and the outputs go back to the pairs' order:
-        (rank int64 [P], n_candidates int64 [P], scores float32 [P]).  Z and the seen items as in `recommend`."""
-        Z = self._compose_for(features)
-        seen_ptr = seen_idx = None
-        if exclude_seen and self.nnz > 0:
-            seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
-        P = us.numel()
-        order = torch.sort(us.to(torch.int64), stable=True).indices
-        q_items = is_[order].contiguous()
-        uniq, counts = torch.unique_consecutive(us[order], return_counts=True)
-        nu = uniq.numel()
-        ptr = torch.zeros(nu + 1, dtype=torch.int64, device=self.dev)
-        torch.cumsum(counts, 0, out=ptr[1:])
-        ptr_h = ptr.cpu().numpy()
-        above = torch.empty(P, dtype=torch.int32, device=self.dev)
-        score = torch.empty(P, dtype=torch.float32, device=self.dev)
-        ncand = torch.empty(nu, dtype=torch.int32, device=self.dev)
-        for b0 in range(0, nu, self.REC_BATCH):
-            nb = min(self.REC_BATCH, nu - b0)
-            t0, t1 = int(ptr_h[b0]), int(ptr_h[b0 + nb])
-            self.be.rank_count(k=self.k, ld=self.ld, n=self.n, U=self.U, Z=Z, b_u=self.b_u, b_i=self.b_i, mu=self.mu,
-                               seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=uniq[b0: b0 + nb],
-                               q_ptr=(ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
-                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb])
-        return self._rank_outputs(above, ncand, counts, score, order)
-
-    def rank_of_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, features, n_sweeps: int,
-                    exclude_seen: bool):
-        """Fold in, then als_rank_count on the folded table (batch row b = new row b, the given ratings as the seen
-        CSR, as `recommend_new` composes it) for the targets titems[tptr[b]:tptr[b + 1]], in REC_BATCH chunks."""
-        Z = self._compose_for(features)
-        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
-        B = indptr.size - 1
-        tptr_d = torch.from_numpy(tptr).to(self.dev)
-        q_items = torch.from_numpy(titems).to(self.dev)
-        P = q_items.numel()
-        above = torch.empty(P, dtype=torch.int32, device=self.dev)
-        score = torch.empty(P, dtype=torch.float32, device=self.dev)
-        ncand = torch.empty(B, dtype=torch.int32, device=self.dev)
-        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            seen_ptr = seen_idx = None
-            if exclude_seen and indptr[b0 + nb] > indptr[b0]:
-                seen_ptr, seen_idx = ptr_d[b0: b0 + nb + 1], idx_d
-            t0, t1 = int(tptr[b0]), int(tptr[b0 + nb])
-            self.be.rank_count(k=self.k, ld=self.ld, n=self.n, U=U[b0:], Z=Z, b_u=b[b0:], b_i=self.b_i, mu=self.mu,
-                               seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users[:nb],
-                               q_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
-                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb])
-        return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
-
-    def _explain_rows(self, ptr_d, idx_d, val_d, rows_d, tptr_d, tptr_h: np.ndarray, q_items, Z, M: int,
-                      n_sweeps: int, largest: bool, row_name):
-        """als_explain over W work rows in REC_BATCH chunks.  rows_d (int32 [W]) names the CSR row of every work
-        row; None: work row w is CSR row w.  Targets q_items[tptr[w]:tptr[w + 1]].  Returns the device outputs in
-        target order and b_u per work row.  row_name(w): how an error names work row w."""
-        md = self.model
-        W, P = tptr_h.size - 1, q_items.numel()
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        score, latent, lev = (torch.empty(P, **f64) for _ in range(3))
-        top_item = torch.empty(P, M, dtype=torch.int32, device=self.dev)
-        top_c, top_w = torch.empty(P, M, **f64), torch.empty(P, M, **f64)
-        top_cnt = torch.empty(P, dtype=torch.int32, device=self.dev)
-        b_u = torch.empty(W, **f64)
-        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        if idx_d.numel() == 0:          # no row has ratings: the library wants valid pointers
-            idx_d = torch.zeros(1, dtype=torch.int32, device=self.dev)
-            val_d = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        for b0 in range(0, W, self.REC_BATCH):
-            nb = min(self.REC_BATCH, W - b0)
-            t0, t1 = int(tptr_h[b0]), int(tptr_h[b0 + nb])
-            if t1 == t0:
-                b_u[b0: b0 + nb] = float("nan")                          # rows without targets: never read
-                continue
-            # views: without rows_d work row w of the chunk reads ptr_d[b0 + w]; the offsets stay absolute
-            self.be.explain(k=self.k, ld=self.ld, indptr=ptr_d if rows_d is not None else ptr_d[b0: b0 + nb + 1],
-                            indices=idx_d, vals=val_d, rows=None if rows_d is None else rows_d[b0: b0 + nb],
-                            n=self.n, Z=Z, b_i=self.b_i, mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu,
-                            n_sweeps=n_sweeps, t_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(),
-                            t_items=q_items[t0:t1], topm=M, largest=largest, score=score[t0:t1],
-                            latent=latent[t0:t1], leverage=lev[t0:t1], top_item=top_item[t0:t1],
-                            top_contrib=top_c[t0:t1], top_weight=top_w[t0:t1], top_cnt=top_cnt[t0:t1],
-                            b_u_out=b_u[b0: b0 + nb], status=status)
-            bad = int(status.item())
-            if bad:
-                raise np.linalg.LinAlgError(
-                    f"fold-in normal equations of {row_name(b0 + bad - 1)} are not positive definite")
-        return score, latent, lev, b_u, top_item, top_c, top_w, top_cnt
-
-    @staticmethod
-    def _explanation(score, latent, lev, b_u_t, top_item, top_c, top_w, top_cnt, inv=None) -> "Explanation":
-        outs = [score, latent, lev, b_u_t, top_item.to(torch.int64), top_c, top_w, top_cnt.to(torch.int64)]
-        if inv is not None:
-            outs = [o[inv] for o in outs]
-        return Explanation(*(o.cpu().numpy() for o in outs))
-
-    def explain(self, us: torch.Tensor, is_: torch.Tensor, M: int, features, n_sweeps: int, largest: bool):
-        """Explanations of the pairs (us[p], is_[p]) (int32, device), the rows read from the resident training CSR:
-        the pairs are grouped by user on the device (as `rank_of`), every distinct user of a REC_BATCH chunk is
-        factorised once (als_explain, `rows` = the users), and the outputs go back to the pairs' order."""
-        Z = self._compose_for(features)
-        order = torch.sort(us.to(torch.int64), stable=True).indices
-        q_items = is_[order].contiguous()
-        uniq, counts = torch.unique_consecutive(us[order], return_counts=True)
-        nu = uniq.numel()
-        ptr = torch.zeros(nu + 1, dtype=torch.int64, device=self.dev)
-        torch.cumsum(counts, 0, out=ptr[1:])
-        uniq = uniq.contiguous()
-        out = self._explain_rows(self.csr.indptr, self.csr.indices, self.csr.vals, uniq, ptr, ptr.cpu().numpy(),
-                                 q_items, Z, M, n_sweeps, largest, lambda w: f"user {int(uniq[w])}")
-        inv = torch.empty_like(order)
-        inv[order] = torch.arange(order.numel(), device=order.device)
-        return self._explanation(*out[:3], torch.repeat_interleave(out[3], counts), *out[4:], inv=inv)
-
-    def explain_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, M: int, features,
-                    n_sweeps: int, largest: bool):
-        """Explanations for new rows (host CSR, rows sorted), targets titems[tptr[b]:tptr[b + 1]] of row b."""
-        Z = self._compose_for(features)
-        ptr_d = torch.from_numpy(indptr).to(self.dev)
-        idx_d = torch.from_numpy(indices).to(self.dev)
-        val_d = torch.from_numpy(vals).to(self.dev)
-        tptr_d = torch.from_numpy(tptr).to(self.dev)
-        out = self._explain_rows(ptr_d, idx_d, val_d, None, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z, M,
-                                 n_sweeps, largest, lambda w: f"row {w}")
-        return self._explanation(*out[:3], torch.repeat_interleave(out[3], tptr_d[1:] - tptr_d[:-1]), *out[4:])
-
-    def seen_pairs(self, us: torch.Tensor, is_: torch.Tensor) -> np.ndarray:
-        """bool [P]: (us[p], is_[p]) (int64, device) is an entry of the training CSR (a binary search per pair)."""
-        if self.nnz == 0:
-            return np.zeros(us.numel(), dtype=bool)
-        ptr, idx = self.csr.indptr, self.csr.indices
-        lo, hi = ptr[us].clone(), ptr[us + 1].clone()
-        end = hi.clone()
-        while bool((lo < hi).any()):                                     # first entry >= the item
-            act, mid = lo < hi, (lo + hi) >> 1
-            below = act & (idx[mid.clamp(max=idx.numel() - 1)] < is_)
-            lo, hi = torch.where(below, mid + 1, lo), torch.where(act & ~below, mid, hi)
-        found = (lo < end) & (idx[lo.clamp(max=idx.numel() - 1)] == is_)
-        return found.cpu().numpy()
-
-    # ----------------------------------------------------------- new items
-    GRAPH_ROWS_MAX_D = 160      # sim feature width the top-k kernel takes (its k)
-
-    def graph_rows_new(self, X_new: np.ndarray, X_fit) -> tuple:
-        """Graph rows of new items against the fitted ones: top-`sim.topk` fp32 cosines
-        under (similarity descending, index ascending), positive entries only, as device CSR (ptr int64, idx
-        int32, val float32).  als_recommend_topk with k = d, U = normalised new rows, Z = normalised fitted rows,
-        zero biases and mu = 0 computes exactly that; topk None / > 128 or d > 160 take the blocked torch
-        formulation (same contract)."""
-        md = self.model
-        eps, topk = md.S_eps, md.S_topk
-        Xn_new = layout.normalize_rows_f32(X_new, eps, self.dev)
-        Xn_fit = layout.normalize_rows_f32(X_fit, eps, self.dev)
-        B, d = Xn_new.shape
-        if topk is None or topk > RECOMMEND_MAX_N or d > self.GRAPH_ROWS_MAX_D or d < 1:
-            logger.warning("graph rows of new items: top-k %s / %d feature columns are outside what the top-k "
-                           "kernel takes (top-k <= %d, d <= %d); using the blocked torch formulation", topk, d,
-                           RECOMMEND_MAX_N, self.GRAPH_ROWS_MAX_D)
-            return layout.similarity_rows_torch(Xn_new, Xn_fit, topk)
-        ldd = layout.padded_k(d)
-        Un = torch.zeros(B, ldd, dtype=torch.float32, device=self.dev)
-        Un[:, :d] = Xn_new
-        Zn = torch.zeros(self.n, ldd, dtype=torch.float32, device=self.dev)
-        Zn[:, :d] = Xn_fit
-        zu = torch.zeros(B, dtype=torch.float32, device=self.dev)
-        zi = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
-        mu0 = torch.zeros(1, dtype=torch.float64, device=self.dev)
-        top_val = torch.empty(B, topk, dtype=torch.float32, device=self.dev)
-        top_idx = torch.empty(B, topk, dtype=torch.int32, device=self.dev)
-        top_cnt = torch.empty(B, dtype=torch.int32, device=self.dev)
-        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            self.be.recommend_topk(k=d, ld=ldd, users=users[:nb], n=self.n, U=Un[b0:], Z=Zn, b_u=zu[b0:], b_i=zi,
-                                   mu=mu0, seen_ptr=None, seen_idx=None, topn=topk, top_val=top_val[b0:],
-                                   top_idx=top_idx[b0:], top_cnt=top_cnt[b0:])
-        return layout.rows_from_topk(top_val, top_idx)
-
-    def fold_in_items(self, indptr, indices, vals, S, X_new: Dict[str, np.ndarray], n_sweeps: int):
-        """Factors / biases of new items (host ratings CSR by user id, rows sorted; device graph rows S or None)
-        against this fit's user side and V (one als_fold_in_items launch), and their Z = V + X_new W
-        (als_compose_z): device fp32 ([B, ld], [B], [B, ld])."""
-        md = self.model
-        B = indptr.size - 1
-        ptr_d = torch.from_numpy(indptr).to(self.dev)
-        idx_d = torch.from_numpy(indices if indices.size else np.zeros(1, np.int32)).to(self.dev)
-        val_d = torch.from_numpy(vals if vals.size else np.zeros(1, np.float32)).to(self.dev)
-        if S is not None and S[1].numel() == 0:     # the library wants valid pointers
-            S = (S[0], torch.zeros(1, dtype=torch.int32, device=self.dev),
-                 torch.zeros(1, dtype=torch.float32, device=self.dev))
-        V = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
-        b = torch.empty(B, dtype=torch.float32, device=self.dev)
-        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self.be.fold_in_items(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, m=self.m, U=self.U,
-                              b_u=self.b_u, mu=self.mu, S=S, n=self.n, V=self.V, lam_v=md.lambda_v,
-                              pop_reg=bool(md.pop_reg_mode), lam_bi=md.lambda_bi,
-                              alpha=md.alpha if S is not None else 0.0, n_sweeps=n_sweeps, V_out=V, b_i_out=b,
-                              status=status)
-        bad = int(status.item())
-        if bad:
-            raise np.linalg.LinAlgError(f"item fold-in normal equations of row {bad - 1} are not positive definite")
-        if not self.feat_names:
-            return V, b, V
-        Xcat = np.concatenate([np.asarray(X_new[f], dtype=np.float32) for f in self.feat_names], axis=1)
-        W = torch.zeros(Xcat.shape[1], self.ld, dtype=torch.float32, device=self.dev)
-        off = 0
-        for f, d in zip(self.feat_names, self.feat_dims):
-            W[off:off + d, : self.k] = self.W64[f].to(torch.float32)
-            off += d
-        Z = torch.empty_like(V)
-        self.be.compose_z(V, torch.from_numpy(Xcat).to(self.dev), W, Z)
-        return V, b, Z
-
-    def _folded_dev(self, folded: "FoldedItems"):
-        """Z [B, ld] and b_i [B] of folded items back on the device (exact: they are fp32 values)."""
-        B = folded.n_items
-        Z = torch.zeros(B, self.ld, dtype=torch.float32, device=self.dev)
-        Z[:, : self.k] = torch.from_numpy(folded.Z.astype(np.float32)).to(self.dev)
-        return Z, torch.from_numpy(folded.b_i.astype(np.float32)).to(self.dev)
-
-    def predict_new_items(self, us: torch.Tensor, folded: "FoldedItems") -> torch.Tensor:
-        """Scores of the folded items for users `us` (int64, device): als_predict_dense on the gathered user rows,
-        fp32 [len(us), B]."""
-        Z, b_new = self._folded_dev(folded)
-        out = torch.empty(us.numel(), folded.n_items, dtype=torch.float32, device=self.dev)
-        self.be.predict_dense(k=self.k, ld=self.ld, m=us.numel(), n=folded.n_items, U=self.U.index_select(0, us),
-                              Z=Z, b_u=self.b_u.index_select(0, us), b_i=b_new, mu=self.mu, out=out)
-        return out
-
-    def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
-                             folded: "FoldedItems"):
-        """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
-        concatenated Z / b_i tables; the batch's user rows are gathered (batch row r = user users_t[r]) and their
-        seen lists are the training row followed by the folded items they rated - ascending, as the new ids come
-        last."""
-        Z_fit = self._compose_for(features)
-        Z_new, b_new = self._folded_dev(folded)
-        n_all = self.n + folded.n_items
-        Z = torch.cat([Z_fit[: self.n], Z_new])
-        b_i = torch.cat([self.b_i[: self.n], b_new])
-        if exclude_seen:
-            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item
-            rp, ri = folded.ratings[0], folded.ratings[1]
-            new_u = ri.astype(np.int64)
-            new_i = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
-            o = np.lexsort((new_i, new_u))
-            new_u_d = torch.from_numpy(new_u[o]).to(self.dev)
-            new_i_d = torch.from_numpy(new_i[o].astype(np.int32)).to(self.dev)
-        B = users_t.numel()
-        items = np.empty((B, N), dtype=np.int64)
-        scores = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            us = users_t[b0: b0 + self.REC_BATCH].to(torch.int64)
-            nb = us.numel()
-            seen_ptr = seen_idx = None
-            if exclude_seen:
-                seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d)
-            top_val = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            top_idx = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            top_cnt = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            self.be.recommend_topk(k=self.k, ld=self.ld, users=torch.arange(nb, dtype=torch.int32, device=self.dev),
-                                   n=n_all, U=self.U.index_select(0, us), Z=Z, b_u=self.b_u.index_select(0, us),
-                                   b_i=b_i, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
-                                   top_val=top_val, top_idx=top_idx, top_cnt=top_cnt)
-            items[b0: b0 + nb] = top_idx.cpu().numpy()
-            scores[b0: b0 + nb] = top_val.cpu().numpy()
-        return items, scores
-
-    def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
-        """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items
-        (ids >= n) they rated, taken from the (user, item)-sorted pairs new_u / new_i."""
-        ptr, idx = self.csr.indptr, self.csr.indices
-        beg_f = ptr[us]
-        cnt_f = ptr[us + 1] - beg_f
-        beg_n = torch.searchsorted(new_u, us)
-        cnt_n = torch.searchsorted(new_u, us, right=True) - beg_n
-        cnt = cnt_f + cnt_n
-        out_ptr = torch.zeros(us.numel() + 1, dtype=torch.int64, device=self.dev)
-        out_ptr[1:] = torch.cumsum(cnt, 0)
-        total = int(out_ptr[-1])
-        out_idx = torch.empty(max(total, 1), dtype=torch.int32, device=self.dev)
-        rows = torch.arange(us.numel(), device=self.dev)
-        for beg, c, skip, src in ((beg_f, cnt_f, None, idx), (beg_n, cnt_n, cnt_f, new_i)):
-            tot = int(c.sum())
-            if tot == 0:
-                continue
-            r = torch.repeat_interleave(rows, c)
-            first = torch.cumsum(c, 0) - c                       # position of each row's first entry in this part
-            off = torch.arange(tot, device=self.dev) - first[r]
-            dst = out_ptr[r] + off + (skip[r] if skip is not None else 0)
-            out_idx[dst] = src[beg[r] + off]
-        if total == 0:
-            return None, None
-        return out_ptr, out_idx
-
-    def predict_pairs(self, us: torch.Tensor, is_: torch.Tensor, features, features_of_fit: bool = False) -> torch.Tensor:
-        """Predictions at (user, item) index tensors already on the device (int32); fp32 device tensor."""
-        Z = self._compose_for(features, features_of_fit)
-        out = torch.empty(us.numel(), dtype=torch.float32, device=self.dev)
-        self.be.predict_at(k=self.k, ld=self.ld, us=us, is_=is_, U=self.U, Z=Z, b_u=self.b_u,
-                           b_i=self.b_i, mu=self.mu, out=out)
-        return out

@@ -135,17 +135,9 @@ class HipBackend:
         self._check(self.lib.als_row_solve(C.byref(p), self._stream()), "als_row_solve")
 
     # -- K2 ------------------------------------------------------------------
-    def gs_level(self, *, k, ld, items, S_ptr, S_idx, S_val, alpha, factor, rhs, colsum, sumr,
-                 indptr, lam_b, lam_b_row, V, bias, sumr2=None, lambda_eff=None, stat_out=None, f64=False):
-        p = _hip.GsSweepParams()
-        p.f64 = int(bool(f64))
-        p.sumr2, p.lambda_eff, p.stat_out = _p(sumr2), _p(lambda_eff), _p(stat_out)
-        p.k, p.ld = k, ld
-        p.items, p.nitems = _p(items), items.numel()
-        p.S_ptr, p.S_idx, p.S_val, p.alpha = _p(S_ptr), _p(S_idx), _p(S_val), float(alpha)
-        p.factor, p.rhs, p.colsum, p.sumr = _p(factor), _p(rhs), _p(colsum), _p(sumr)
-        p.indptr, p.lambda_bias_scalar, p.lambda_bias_row = _p(indptr), float(lam_b), _p(lam_b_row)
-        p.V, p.bias = _p(V), _p(bias)
+    def gs_level(self, *, items, **kw):
+        """One dependency level of the sweep (als_gs_sweep); `kw` as `_gs_params` reads it."""
+        p = self._gs_params(items, kw)
         self._check(self.lib.als_gs_sweep(C.byref(p), self._stream()), "als_gs_sweep")
 
     def _gs_params(self, items, kw):
@@ -170,16 +162,8 @@ class HipBackend:
 
     def gs_levels(self, *, offsets, **kw):
         """All levels of the sweep with one C call (offsets: host int64 numpy array, nlevels+1)."""
-        items = kw.pop("items")
-        p = _hip.GsSweepParams()
-        p.k, p.ld = kw["k"], kw["ld"]
-        p.items, p.nitems = _p(items), 0
-        p.S_ptr, p.S_idx, p.S_val, p.alpha = _p(kw["S_ptr"]), _p(kw["S_idx"]), _p(kw["S_val"]), float(kw["alpha"])
-        p.factor, p.rhs, p.colsum, p.sumr = _p(kw["factor"]), _p(kw["rhs"]), _p(kw["colsum"]), _p(kw["sumr"])
-        p.indptr, p.lambda_bias_scalar, p.lambda_bias_row = _p(kw["indptr"]), float(kw["lam_b"]), _p(kw["lam_b_row"])
-        p.V, p.bias = _p(kw["V"]), _p(kw["bias"])
-        p.sumr2, p.lambda_eff, p.stat_out = _p(kw.get("sumr2")), _p(kw.get("lambda_eff")), _p(kw.get("stat_out"))
-        p.f64 = int(bool(kw.get("f64", False)))
+        p = self._gs_params(kw.pop("items"), kw)
+        p.nitems = 0
         off = offsets.ctypes.data_as(C.c_void_p)
         self._check(self.lib.als_gs_sweep_levels(C.byref(p), off, len(offsets) - 1, self._stream()),
                     "als_gs_sweep_levels")

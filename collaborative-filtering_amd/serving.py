@@ -1,0 +1,490 @@
+"""Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in` and
+`fold_in_items`.
+
+`_Serving` is the part of the engine (als._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
+mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
+of the fit every rank holds the full tables and the training CSR, so nothing here issues a collective.  The
+arithmetic is in the HIP kernels behind the backend (`self.be`); what lives here is the host orchestration: which
+Z a call scores against, REC_BATCH chunking, grouping pairs by user, and bringing results back in the caller's
+order.  Arguments arrive validated (validate.py, through the `ALS` facade).
+"""
+from __future__ import annotations
+
+import logging
+from dataclasses import dataclass
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import layout
+
+RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
+
+logger = logging.getLogger(__name__)
+
+
+@dataclass
+class FoldedItems:
+    """Items outside the fit, placed by `ALS.fold_in_items`; folded item b is item n + b in `ALS.recommend`.
+
+    V, Z: float64 [B, k], the fp32 device values (Z = V + sum_f X_new,f W_f, what predictions use); b_i: float64
+    [B].  graph: the graph rows used, (ptr int64 [B+1], idx int32 fitted item ids, val float32), or None without a
+    graph.  ratings: the ratings CSR (ptr int64 [B+1], idx int32 user ids ascending, val float32)."""
+    V: np.ndarray
+    b_i: np.ndarray
+    Z: np.ndarray
+    graph: Optional[tuple]
+    ratings: tuple
+
+    @property
+    def n_items(self) -> int:
+        return int(self.b_i.shape[0])
+
+
+@dataclass
+class Explanation:
+    """What `ALS.explain` / `explain_new` return for P (row, target) pairs, all float64 / int64 host arrays.
+
+    score, latent, leverage, b_u: [P] - the half-step user's score mu + b_u + b_i[i] + latent, its latent part
+    u.z_i (the sum of ALL the row's contributions), z_i^T A^-1 z_i, and the user bias.  items [P, M] (-1 padded),
+    contributions, weights [P, M] (0 padded): the M strongest rated items with contribution = weight * (r_j - mu -
+    b_i[j] - b) and weight = z_i^T A^-1 z_j.  counts [P] = min(M, ratings of the row)."""
+    score: np.ndarray
+    latent: np.ndarray
+    leverage: np.ndarray
+    b_u: np.ndarray
+    items: np.ndarray
+    contributions: np.ndarray
+    weights: np.ndarray
+    counts: np.ndarray
+
+    @staticmethod
+    def empty(M: int) -> "Explanation":
+        z = lambda *sh: np.empty(sh, dtype=np.float64)                  # noqa: E731
+        return Explanation(z(0), z(0), z(0), z(0), np.empty((0, M), dtype=np.int64), z(0, M), z(0, M),
+                           np.empty(0, dtype=np.int64))
+
+
+def concat_features(features, names) -> np.ndarray:
+    """The feature matrices of `names` side by side, float32 [rows, sum of widths]: the X of als_compose_z."""
+    return np.concatenate([np.asarray(features[f], dtype=np.float32) for f in names], axis=1)
+
+
+def _raise_unless_solved(status: torch.Tensor, what: str, row_name=lambda r: f"row {r}") -> None:
+    """`status` is the one-word result of a solve kernel: 0, or 1 + the first row whose system failed."""
+    bad = int(status.item())
+    if bad:
+        raise np.linalg.LinAlgError(f"{what} normal equations of {row_name(bad - 1)} are not positive definite")
+
+
+class _Serving:
+    """Read-only calls on the device state of a fit; see the module docstring for what `self` has to hold."""
+
+    # rows per als_recommend_topk / als_rank_count / als_explain call: bounds the outputs and the item-slice
+    # workspace.  Looked up through the instance at call time (tests shrink it to cross chunk boundaries).
+    REC_BATCH = 1 << 16
+    GRAPH_ROWS_MAX_D = 160      # sim feature width the top-k kernel takes (its k)
+
+    # ------------------------------------------------------------- helpers
+    def _concat_w(self, names, dims, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fp32 projection matrix of the features `names` (widths `dims`), rows stacked as concat_features
+        stacks columns: [sum(dims), ld] with zero padding columns; into `out` when given."""
+        if out is None:
+            out = torch.zeros(sum(dims), self.ld, dtype=torch.float32, device=self.dev)
+        off = 0
+        for f, d in zip(names, dims):
+            out[off:off + d, : self.k] = self.W64[f].to(torch.float32)
+            off += d
+        return out
+
+    def _compose_for(self, features, features_of_fit: bool = False):
+        """Z for `features` as passed to predict (scripts/als.py:568-572): composed from whatever is passed.
+        `features_of_fit`: the caller vouches that these are the unchanged arrays of the fit (sweep.SweepDriver,
+        which owns them) - the fit's own Z = V + sum_f X_f W_f is then current and nothing is uploaded.  (Round 2
+        inferred that from object identity, which says nothing about the contents and can be recycled.)"""
+        names = [f for f in features if f in self.W64]
+        if not names:
+            return self.V
+        if features_of_fit and self.iters_run > 0 and names == self.feat_names:
+            return self.Z
+        X = torch.from_numpy(concat_features(features, names)).to(self.dev)
+        Z = torch.empty_like(self.V)
+        self.be.compose_z(self.V, X, self._concat_w(names, [features[f].shape[1] for f in names]), Z)
+        return Z
+
+    def _item_side(self, Z) -> dict:
+        """The fitted item tables as the scoring kernels name them."""
+        return dict(k=self.k, ld=self.ld, n=self.n, Z=Z, b_i=self.b_i, mu=self.mu)
+
+    def _csr_dev(self, ptr, idx, val):
+        """A CSR triple (host arrays or device tensors) on the device; `idx` / `val` are one-element buffers when
+        no row has an entry: the library wants valid pointers."""
+        if len(idx) == 0:
+            idx, val = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        return tuple(a if torch.is_tensor(a) else torch.from_numpy(a).to(self.dev) for a in (ptr, idx, val))
+
+    def _fitted_rows(self, users: torch.Tensor, exclude_seen: bool):
+        """Chunk source of the drivers below for users of the fit: the ids index the resident tables, the seen
+        items are the training CSR."""
+        seen_ptr = seen_idx = None
+        if exclude_seen and self.nnz > 0:
+            seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
+        return lambda b0, nb: (users[b0: b0 + nb], self.U, self.b_u, seen_ptr, seen_idx)
+
+    def _table_rows(self, B: int, U, b_u, seen=None):
+        """Chunk source for a table made for the call (batch row b = table row b): the chunk is addressed as rows
+        0 .. nb of the tables advanced to b0.  `seen` = (host indptr, device indptr, device indices) or None."""
+        users = torch.arange(min(B, self.REC_BATCH), dtype=torch.int32, device=self.dev)
+
+        def rows(b0, nb):
+            seen_ptr = seen_idx = None
+            if seen is not None and seen[0][b0 + nb] > seen[0][b0]:
+                # views: row b of the chunk reads ptr_d[b0 + b]; the offsets stay absolute into idx_d
+                seen_ptr, seen_idx = seen[1][b0: b0 + nb + 1], seen[2]
+            return users[:nb], U[b0:], b_u[b0:], seen_ptr, seen_idx
+        return rows
+
+    def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False):
+        """als_recommend_topk over B batch rows in REC_BATCH chunks.  rows(b0, nb) -> (users int32 [nb], U, b_u,
+        seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu).  Returns host
+        (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk, or with `on_device` the kernel's own
+        (top_val fp32 [B, N], top_idx int32 [B, N])."""
+        if on_device:
+            top_val = torch.empty(B, N, dtype=torch.float32, device=self.dev)
+            top_idx = torch.empty(B, N, dtype=torch.int32, device=self.dev)
+            top_cnt = torch.empty(B, dtype=torch.int32, device=self.dev)
+        else:
+            out_items = np.empty((B, N), dtype=np.int64)
+            out_scores = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+            if on_device:
+                tv, ti, tc = top_val[b0:], top_idx[b0:], top_cnt[b0:]
+            else:
+                tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+                ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+                tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.recommend_topk(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
+                                   top_val=tv, top_idx=ti, top_cnt=tc, **items)
+            if not on_device:
+                out_items[b0: b0 + nb] = ti.cpu().numpy()
+                out_scores[b0: b0 + nb] = tv.cpu().numpy()
+        return (top_val, top_idx) if on_device else (out_items, out_scores)
+
+    def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, Z):
+        """als_rank_count over the batch rows of the prefix sum `t_ptr` (device; `t_ptr_h` its host copy) in
+        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows` as in `_topk_chunks`.
+        Returns device (above int32 [P], n_cand int32 [rows], score fp32 [P])."""
+        B, P = t_ptr_h.size - 1, q_items.numel()
+        above = torch.empty(P, dtype=torch.int32, device=self.dev)
+        score = torch.empty(P, dtype=torch.float32, device=self.dev)
+        ncand = torch.empty(B, dtype=torch.int32, device=self.dev)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+            t0, t1 = int(t_ptr_h[b0]), int(t_ptr_h[b0 + nb])
+            self.be.rank_count(U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users,
+                               q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
+                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb],
+                               **self._item_side(Z))
+        return above, ncand, score
+
+    def _group_by_user(self, us: torch.Tensor):
+        """Pairs grouped by user on the device: (order, inv, uniq, counts, ptr, ptr_h) - `order` sorts the pairs by
+        user (stable), `inv` undoes it, `uniq` are the distinct users ascending with `counts` pairs each, `ptr`
+        (device) / `ptr_h` (host) the prefix sum of the counts."""
+        order = torch.sort(us.to(torch.int64), stable=True).indices
+        uniq, counts = torch.unique_consecutive(us[order], return_counts=True)
+        ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.numel(), device=order.device)
+        return order, inv, uniq.contiguous(), counts, ptr, ptr.cpu().numpy()
+
+    # ------------------------------------------------------------- predict
+    def predict_dense(self, features) -> np.ndarray:
+        Z = self._compose_for(features)
+        out = torch.empty(self.m, self.n, dtype=torch.float32, device=self.dev)
+        self.be.predict_dense(k=self.k, ld=self.ld, m=self.m, n=self.n, U=self.U, Z=Z, b_u=self.b_u,
+                              b_i=self.b_i, mu=self.mu, out=out)
+        return out.cpu().numpy().astype(np.float64)
+
+    def predict_at(self, flat_idx: np.ndarray, features) -> np.ndarray:
+        u, i = np.divmod(flat_idx, self.n)
+        us = torch.from_numpy(u.astype(np.int32)).to(self.dev)
+        is_ = torch.from_numpy(i.astype(np.int32)).to(self.dev)
+        return self.predict_pairs(us, is_, features).cpu().numpy().astype(np.float64)
+
+    def predict_pairs(self, us: torch.Tensor, is_: torch.Tensor, features, features_of_fit: bool = False) -> torch.Tensor:
+        """Predictions at (user, item) index tensors already on the device (int32); fp32 device tensor."""
+        Z = self._compose_for(features, features_of_fit)
+        out = torch.empty(us.numel(), dtype=torch.float32, device=self.dev)
+        self.be.predict_at(k=self.k, ld=self.ld, us=us, is_=is_, U=self.U, Z=Z, b_u=self.b_u,
+                           b_i=self.b_i, mu=self.mu, out=out)
+        return out
+
+    # ----------------------------------------------------- users of the fit
+    def recommend(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool):
+        """Top-N items of the users in `users_t` (int32, device): (items int64 [B, N], scores float64 [B, N]),
+        unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit."""
+        Z = self._compose_for(features)
+        return self._topk_chunks(users_t.numel(), N, self._fitted_rows(users_t, exclude_seen), self._item_side(Z))
+
+    def _rank_outputs(self, above, ncand_rows, counts, score, inv=None):
+        rank = above.to(torch.int64)
+        cand = torch.repeat_interleave(ncand_rows.to(torch.int64), counts)
+        if inv is not None:
+            rank, cand, score = rank[inv], cand[inv], score[inv]
+        return rank.cpu().numpy(), cand.cpu().numpy(), score.cpu().numpy()
+
+    def rank_of(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool):
+        """Ranks of the pairs (us[p], is_[p]) (int32, device): the pairs are grouped by user on the device, every
+        user of a REC_BATCH chunk is scored once (als_rank_count), and the outputs go back to the pairs' order:
+        (rank int64 [P], n_candidates int64 [P], scores float32 [P]).  Z and the seen items as in `recommend`."""
+        Z = self._compose_for(features)
+        order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
+        above, ncand, score = self._rank_chunks(self._fitted_rows(uniq, exclude_seen), ptr, ptr_h,
+                                                is_[order].contiguous(), Z)
+        return self._rank_outputs(above, ncand, counts, score, inv)
+
+    def explain(self, us: torch.Tensor, is_: torch.Tensor, M: int, features, n_sweeps: int, largest: bool):
+        """Explanations of the pairs (us[p], is_[p]) (int32, device), the rows read from the resident training CSR:
+        the pairs are grouped by user on the device (as `rank_of`), every distinct user of a REC_BATCH chunk is
+        factorised once (als_explain, `rows` = the users), and the outputs go back to the pairs' order."""
+        Z = self._compose_for(features)
+        order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
+        out = self._explain_rows((self.csr.indptr, self.csr.indices, self.csr.vals), uniq, ptr, ptr_h,
+                                 is_[order].contiguous(), Z, M, n_sweeps, largest, lambda w: f"user {int(uniq[w])}")
+        return self._explanation(*out[:3], torch.repeat_interleave(out[3], counts), *out[4:], inv=inv)
+
+    def seen_pairs(self, us: torch.Tensor, is_: torch.Tensor) -> np.ndarray:
+        """bool [P]: (us[p], is_[p]) (int64, device) is an entry of the training CSR (a binary search per pair)."""
+        if self.nnz == 0:
+            return np.zeros(us.numel(), dtype=bool)
+        ptr, idx = self.csr.indptr, self.csr.indices
+        lo, hi = ptr[us].clone(), ptr[us + 1].clone()
+        end = hi.clone()
+        while bool((lo < hi).any()):                                     # first entry >= the item
+            act, mid = lo < hi, (lo + hi) >> 1
+            below = act & (idx[mid.clamp(max=idx.numel() - 1)] < is_)
+            lo, hi = torch.where(below, mid + 1, lo), torch.where(act & ~below, mid, hi)
+        found = (lo < end) & (idx[lo.clamp(max=idx.numel() - 1)] == is_)
+        return found.cpu().numpy()
+
+    # -------------------------------------------------- users outside the fit
+    def _fold_in_dev(self, indptr: np.ndarray, indices: np.ndarray, vals: np.ndarray, Z, n_sweeps: int):
+        """Folded factors (fp32 [B, ld], zero padding columns) and biases (fp32 [B]) on the device, with the
+        device CSR they were computed from (one als_fold_in launch)."""
+        md = self.model
+        B = indptr.size - 1
+        ptr_d, idx_d, val_d = self._csr_dev(indptr, indices, vals)
+        U = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
+        b = torch.empty(B, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.be.fold_in(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, n=self.n, Z=Z, b_i=self.b_i,
+                        mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu, n_sweeps=n_sweeps, U_out=U, b_u_out=b,
+                        status=status)
+        _raise_unless_solved(status, "fold-in")
+        return U, b, ptr_d, idx_d
+
+    def _folded_rows(self, indptr: np.ndarray, indices, vals, Z, n_sweeps: int, exclude_seen: bool):
+        """Fold in, then the chunk source of the folded table: batch row b = new row b, the given ratings as the
+        seen CSR."""
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        return self._table_rows(indptr.size - 1, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
+
+    def fold_in(self, indptr, indices, vals, features, n_sweeps: int):
+        """Factors / biases of new users (host CSR, rows sorted) against this fit's item side: device fp32
+        ([B, ld], [B]).  Z is composed as in `predict`."""
+        U, b, _, _ = self._fold_in_dev(indptr, indices, vals, self._compose_for(features), n_sweeps)
+        return U, b
+
+    def recommend_new(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool):
+        """Fold in, then als_recommend_topk on the folded table in REC_BATCH chunks: (items int64 [B, N], scores
+        float64 [B, N])."""
+        Z = self._compose_for(features)
+        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z))
+
+    def rank_of_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, features, n_sweeps: int,
+                    exclude_seen: bool):
+        """Fold in, then als_rank_count on the folded table (as `recommend_new` composes it) for the targets
+        titems[tptr[b]:tptr[b + 1]], in REC_BATCH chunks."""
+        Z = self._compose_for(features)
+        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        tptr_d = torch.from_numpy(tptr).to(self.dev)
+        above, ncand, score = self._rank_chunks(rows, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z)
+        return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
+
+    def explain_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, M: int, features,
+                    n_sweeps: int, largest: bool):
+        """Explanations for new rows (host CSR, rows sorted), targets titems[tptr[b]:tptr[b + 1]] of row b."""
+        Z = self._compose_for(features)
+        tptr_d = torch.from_numpy(tptr).to(self.dev)
+        out = self._explain_rows((indptr, indices, vals), None, tptr_d, tptr, torch.from_numpy(titems).to(self.dev),
+                                 Z, M, n_sweeps, largest, lambda w: f"row {w}")
+        return self._explanation(*out[:3], torch.repeat_interleave(out[3], tptr_d[1:] - tptr_d[:-1]), *out[4:])
+
+    def _explain_rows(self, csr, rows_d, tptr_d, tptr_h: np.ndarray, q_items, Z, M: int, n_sweeps: int,
+                      largest: bool, row_name):
+        """als_explain over W work rows in REC_BATCH chunks.  rows_d (int32 [W]) names the row of `csr` (a triple,
+        host or device) of every work row; None: work row w is CSR row w.  Targets q_items[tptr[w]:tptr[w + 1]].
+        Returns the device outputs in target order and b_u per work row.  row_name(w): how an error names work
+        row w."""
+        md = self.model
+        W, P = tptr_h.size - 1, q_items.numel()
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        score, latent, lev = (torch.empty(P, **f64) for _ in range(3))
+        top_item = torch.empty(P, M, dtype=torch.int32, device=self.dev)
+        top_c, top_w = torch.empty(P, M, **f64), torch.empty(P, M, **f64)
+        top_cnt = torch.empty(P, dtype=torch.int32, device=self.dev)
+        b_u = torch.empty(W, **f64)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        ptr_d, idx_d, val_d = self._csr_dev(*csr)
+        for b0 in range(0, W, self.REC_BATCH):
+            nb = min(self.REC_BATCH, W - b0)
+            t0, t1 = int(tptr_h[b0]), int(tptr_h[b0 + nb])
+            if t1 == t0:
+                b_u[b0: b0 + nb] = float("nan")                          # rows without targets: never read
+                continue
+            # views: without rows_d work row w of the chunk reads ptr_d[b0 + w]; the offsets stay absolute
+            self.be.explain(k=self.k, ld=self.ld, indptr=ptr_d if rows_d is not None else ptr_d[b0: b0 + nb + 1],
+                            indices=idx_d, vals=val_d, rows=None if rows_d is None else rows_d[b0: b0 + nb],
+                            n=self.n, Z=Z, b_i=self.b_i, mu=self.mu, lam_u=md.lambda_u, lam_bu=md.lambda_bu,
+                            n_sweeps=n_sweeps, t_ptr=(tptr_d[b0: b0 + nb + 1] - t0).contiguous(),
+                            t_items=q_items[t0:t1], topm=M, largest=largest, score=score[t0:t1],
+                            latent=latent[t0:t1], leverage=lev[t0:t1], top_item=top_item[t0:t1],
+                            top_contrib=top_c[t0:t1], top_weight=top_w[t0:t1], top_cnt=top_cnt[t0:t1],
+                            b_u_out=b_u[b0: b0 + nb], status=status)
+            _raise_unless_solved(status, "fold-in", lambda r: row_name(b0 + r))
+        return score, latent, lev, b_u, top_item, top_c, top_w, top_cnt
+
+    @staticmethod
+    def _explanation(score, latent, lev, b_u_t, top_item, top_c, top_w, top_cnt, inv=None) -> "Explanation":
+        outs = [score, latent, lev, b_u_t, top_item.to(torch.int64), top_c, top_w, top_cnt.to(torch.int64)]
+        if inv is not None:
+            outs = [o[inv] for o in outs]
+        return Explanation(*(o.cpu().numpy() for o in outs))
+
+    # ----------------------------------------------------------- new items
+    def graph_rows_new(self, X_new: np.ndarray, X_fit) -> tuple:
+        """Graph rows of new items against the fitted ones: top-`sim.topk` fp32 cosines
+        under (similarity descending, index ascending), positive entries only, as device CSR (ptr int64, idx
+        int32, val float32).  als_recommend_topk with k = d, U = normalised new rows, Z = normalised fitted rows,
+        zero biases and mu = 0 computes exactly that; topk None / > 128 or d > 160 take the blocked torch
+        formulation (same contract)."""
+        md = self.model
+        eps, topk = md.S_eps, md.S_topk
+        Xn_new = layout.normalize_rows_f32(X_new, eps, self.dev)
+        Xn_fit = layout.normalize_rows_f32(X_fit, eps, self.dev)
+        B, d = Xn_new.shape
+        if topk is None or topk > RECOMMEND_MAX_N or d > self.GRAPH_ROWS_MAX_D or d < 1:
+            logger.warning("graph rows of new items: top-k %s / %d feature columns are outside what the top-k "
+                           "kernel takes (top-k <= %d, d <= %d); using the blocked torch formulation", topk, d,
+                           RECOMMEND_MAX_N, self.GRAPH_ROWS_MAX_D)
+            return layout.similarity_rows_torch(Xn_new, Xn_fit, topk)
+        ldd = layout.padded_k(d)
+        Un = torch.zeros(B, ldd, dtype=torch.float32, device=self.dev)
+        Un[:, :d] = Xn_new
+        Zn = torch.zeros(self.n, ldd, dtype=torch.float32, device=self.dev)
+        Zn[:, :d] = Xn_fit
+        zu = torch.zeros(B, dtype=torch.float32, device=self.dev)
+        side = dict(k=d, ld=ldd, n=self.n, Z=Zn, b_i=torch.zeros(self.n, dtype=torch.float32, device=self.dev),
+                    mu=torch.zeros(1, dtype=torch.float64, device=self.dev))
+        return layout.rows_from_topk(*self._topk_chunks(B, topk, self._table_rows(B, Un, zu), side, on_device=True))
+
+    def fold_in_items(self, indptr, indices, vals, S, X_new: Dict[str, np.ndarray], n_sweeps: int):
+        """Factors / biases of new items (host ratings CSR by user id, rows sorted; device graph rows S or None)
+        against this fit's user side and V (one als_fold_in_items launch), and their Z = V + X_new W
+        (als_compose_z): device fp32 ([B, ld], [B], [B, ld])."""
+        md = self.model
+        B = indptr.size - 1
+        ptr_d, idx_d, val_d = self._csr_dev(indptr, indices, vals)
+        if S is not None:
+            S = self._csr_dev(*S)
+        V = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
+        b = torch.empty(B, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.be.fold_in_items(k=self.k, ld=self.ld, indptr=ptr_d, indices=idx_d, vals=val_d, m=self.m, U=self.U,
+                              b_u=self.b_u, mu=self.mu, S=S, n=self.n, V=self.V, lam_v=md.lambda_v,
+                              pop_reg=bool(md.pop_reg_mode), lam_bi=md.lambda_bi,
+                              alpha=md.alpha if S is not None else 0.0, n_sweeps=n_sweeps, V_out=V, b_i_out=b,
+                              status=status)
+        _raise_unless_solved(status, "item fold-in")
+        if not self.feat_names:
+            return V, b, V
+        X = torch.from_numpy(concat_features(X_new, self.feat_names)).to(self.dev)
+        Z = torch.empty_like(V)
+        self.be.compose_z(V, X, self._concat_w(self.feat_names, self.feat_dims), Z)
+        return V, b, Z
+
+    def _folded_dev(self, folded: "FoldedItems"):
+        """Z [B, ld] and b_i [B] of folded items back on the device (exact: they are fp32 values)."""
+        B = folded.n_items
+        Z = torch.zeros(B, self.ld, dtype=torch.float32, device=self.dev)
+        Z[:, : self.k] = torch.from_numpy(folded.Z.astype(np.float32)).to(self.dev)
+        return Z, torch.from_numpy(folded.b_i.astype(np.float32)).to(self.dev)
+
+    def predict_new_items(self, us: torch.Tensor, folded: "FoldedItems") -> torch.Tensor:
+        """Scores of the folded items for users `us` (int64, device): als_predict_dense on the gathered user rows,
+        fp32 [len(us), B]."""
+        Z, b_new = self._folded_dev(folded)
+        out = torch.empty(us.numel(), folded.n_items, dtype=torch.float32, device=self.dev)
+        self.be.predict_dense(k=self.k, ld=self.ld, m=us.numel(), n=folded.n_items, U=self.U.index_select(0, us),
+                              Z=Z, b_u=self.b_u.index_select(0, us), b_i=b_new, mu=self.mu, out=out)
+        return out
+
+    def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
+                             folded: "FoldedItems"):
+        """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
+        concatenated Z / b_i tables; the batch's user rows are gathered (batch row r = user users_t[r]) and their
+        seen lists are the training row followed by the folded items they rated - ascending, as the new ids come
+        last."""
+        Z_fit = self._compose_for(features)
+        Z_new, b_new = self._folded_dev(folded)
+        side = dict(k=self.k, ld=self.ld, n=self.n + folded.n_items, Z=torch.cat([Z_fit, Z_new]),
+                    b_i=torch.cat([self.b_i, b_new]), mu=self.mu)
+        if exclude_seen:
+            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item
+            rp, ri = folded.ratings[0], folded.ratings[1]
+            new_u = ri.astype(np.int64)
+            new_i = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
+            o = np.lexsort((new_i, new_u))
+            new_u_d = torch.from_numpy(new_u[o]).to(self.dev)
+            new_i_d = torch.from_numpy(new_i[o].astype(np.int32)).to(self.dev)
+
+        def rows(b0, nb):
+            us = users_t[b0: b0 + nb].to(torch.int64)
+            seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d) if exclude_seen else (None, None)
+            return (torch.arange(nb, dtype=torch.int32, device=self.dev), self.U.index_select(0, us),
+                    self.b_u.index_select(0, us), seen_ptr, seen_idx)
+        return self._topk_chunks(users_t.numel(), N, rows, side)
+
+    def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
+        """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items
+        (ids >= n) they rated, taken from the (user, item)-sorted pairs new_u / new_i."""
+        ptr, idx = self.csr.indptr, self.csr.indices
+        beg_f = ptr[us]
+        cnt_f = ptr[us + 1] - beg_f
+        beg_n = torch.searchsorted(new_u, us)
+        cnt_n = torch.searchsorted(new_u, us, right=True) - beg_n
+        cnt = cnt_f + cnt_n
+        out_ptr = torch.zeros(us.numel() + 1, dtype=torch.int64, device=self.dev)
+        out_ptr[1:] = torch.cumsum(cnt, 0)
+        total = int(out_ptr[-1])
+        out_idx = torch.empty(max(total, 1), dtype=torch.int32, device=self.dev)
+        rows = torch.arange(us.numel(), device=self.dev)
+        for beg, c, skip, src in ((beg_f, cnt_f, None, idx), (beg_n, cnt_n, cnt_f, new_i)):
+            tot = int(c.sum())
+            if tot == 0:
+                continue
+            r = torch.repeat_interleave(rows, c)
+            first = torch.cumsum(c, 0) - c                       # position of each row's first entry in this part
+            off = torch.arange(tot, device=self.dev) - first[r]
+            dst = out_ptr[r] + off + (skip[r] if skip is not None else 0)
+            out_idx[dst] = src[beg[r] + off]
+        if total == 0:
+            return None, None
+        return out_ptr, out_idx

@@ -1,0 +1,212 @@
+"""Input checks of the `ALS` facade (als.py), as plain functions: everything a public method verifies about its
+arguments before any device work - fitted-ness, features, list lengths, id arrays, `targets`, `n_sweeps`, and the
+host CSR forms of new users' / new items' ratings and graph rows.  Exception types and messages are part of the
+public behaviour (the reference's where it has one: scripts/als.py:554-565)."""
+from __future__ import annotations
+
+from typing import Dict
+
+import numpy as np
+import torch
+
+from .serving import RECOMMEND_MAX_N, FoldedItems
+
+
+def host_features(features):
+    """The features dict with device tensors (e.g. the output of features.normalize_feature_device) brought to the
+    host: the fit keeps float32 / float64 copies of its own in HBM and validates on the host, as the reference."""
+    if not features:
+        return {}
+    return {name: (X.detach().cpu().numpy() if torch.is_tensor(X) else X) for name, X in features.items()}
+
+
+def fitted(model) -> None:
+    if model.U is None or model.V is None:                   # scripts/als.py:554-555
+        raise RuntimeError("Model must be fitted before prediction.")
+
+
+def predict_features(model, features):
+    features = host_features(features)
+    fitted(model)
+    n = model.V.shape[0]
+    for name, X in features.items():                         # scripts/als.py:560-565
+        if X.shape[0] != n:
+            raise ValueError(f"Feature '{name}' has {X.shape[0]} rows. "
+                             f"Expected number of rows: {n}.")
+        if not np.isfinite(X).all():
+            raise ValueError(f"Feature '{name}' contains infinite values.")
+    return features
+
+
+def top_count(x, name: str) -> int:
+    """The length N of a top-N list / M of an explanation: what the selection kernels hold per row."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= RECOMMEND_MAX_N:
+        raise ValueError(f"{name} must be an integer in [1, {RECOMMEND_MAX_N}], got {x!r}")
+    return int(x)
+
+
+def sweeps(n_sweeps) -> int:
+    if n_sweeps is None:
+        return 0
+    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, (int, np.integer)) or not 1 <= n_sweeps < 2 ** 31:
+        raise ValueError(f"n_sweeps must be None (fixed point) or an integer >= 1, got {n_sweeps!r}")
+    return int(n_sweeps)
+
+
+def _ids(a, kind: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{kind}s must be a 1-D array-like of integer {kind} ids")
+    return a
+
+
+def _in_range(a: np.ndarray, bound: int, kind: str) -> None:
+    if a.size and (a.min() < 0 or a.max() >= bound):
+        raise IndexError(f"{kind} ids must lie in [0, {bound})")
+
+
+def user_ids(users, m: int) -> np.ndarray:
+    """User ids in [0, m), order and duplicates kept; None = all m users in id order."""
+    if users is None:
+        return np.arange(m, dtype=np.int64)
+    u = _ids(users, "user")
+    _in_range(u, m, "user")
+    return u
+
+
+def id_pairs(users, items, m: int, n: int):
+    u, i = _ids(users, "user"), _ids(items, "item")
+    if u.shape != i.shape:
+        raise ValueError("users and items must have the same length")
+    _in_range(u, m, "user")
+    _in_range(i, n, "item")
+    return u.astype(np.int64), i.astype(np.int64)
+
+
+def target_lists(targets, B: int, n: int):
+    """`targets` = (indptr [B + 1], items in [0, n)) of `rank_of_new` / `explain_new` -> (int64, int64)."""
+    if not isinstance(targets, (tuple, list)) or len(targets) != 2:
+        raise ValueError("targets must be (indptr, items)")
+    tptr = np.asarray(targets[0])
+    if tptr.ndim != 1 or tptr.size != B + 1 or not np.issubdtype(tptr.dtype, np.integer):
+        raise ValueError(f"targets indptr must hold {B + 1} integers (one row per row of R_new)")
+    tptr = tptr.astype(np.int64)
+    ti = _ids(targets[1], "item")
+    _in_range(ti, n, "item")
+    if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
+        raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
+    return tptr, ti.astype(np.int64)
+
+
+def folded_items(model, folded) -> None:
+    fitted(model)
+    if not isinstance(folded, FoldedItems):
+        raise ValueError("new items must be a FoldedItems record (ALS.fold_in_items)")
+    k, B = model.V.shape[1], folded.n_items
+    if folded.Z.shape != (B, k) or folded.b_i.shape != (B,):
+        raise ValueError(f"FoldedItems holds Z {folded.Z.shape} and b_i {folded.b_i.shape}; this model needs "
+                         f"({B}, {k}) and ({B},)")
+    if len(folded.ratings[0]) != B + 1:
+        raise ValueError("FoldedItems: ratings CSR does not have one row per item")
+
+
+# ------------------------------------------------------------------ host CSR
+def _host_csr(triple, ncols: int, nrows=None):
+    """Structure of a host CSR triple: (fault, ptr int64, idx, val) with fault None or the first of "shape" (not
+    1-D, non-integer ptr / idx; without `nrows` also an empty ptr), "rows" (ptr.size != nrows + 1), "ptr" (does not
+    start at 0, decreases, or does not end at len(idx) == len(val)), "range" (idx outside [0, ncols)).  The callers
+    word the errors - and choose their types - themselves."""
+    ptr, idx, val = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a) for a in triple)
+    if (ptr.ndim != 1 or idx.ndim != 1 or val.ndim != 1 or (nrows is None and ptr.size < 1)
+            or (ptr.size and not np.issubdtype(ptr.dtype, np.integer))
+            or (idx.size and not np.issubdtype(idx.dtype, np.integer))):
+        return "shape", ptr, idx, val
+    if nrows is not None and ptr.size != nrows + 1:
+        return "rows", ptr, idx, val
+    ptr = ptr.astype(np.int64)
+    if ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != idx.size or idx.size != val.size:
+        return "ptr", ptr, idx, val
+    if idx.size and (idx.min() < 0 or idx.max() >= ncols):
+        return "range", ptr, idx, val
+    return None, ptr, idx, val
+
+
+def _finite_f32(vals: np.ndarray, message: str) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        vals32 = vals.astype(np.float32)
+    if not np.isfinite(vals32).all():
+        raise ValueError(message)
+    return vals32
+
+
+def fold_in_csr(R_new, n: int):
+    """Ratings of users outside the fit -> host CSR (indptr int64 [B+1], indices int32, vals float32), every row's
+    columns ascending (values carried along).  `R_new`: a dense (B, n) array with NaN for missing ratings, or a CSR
+    triple (indptr, indices, vals) in any column order.  Raises ValueError for a wrong dense width, a malformed
+    triple, a duplicate column in a row or a non-finite rating, IndexError for a column outside [0, n)."""
+    if isinstance(R_new, (tuple, list)) and len(R_new) == 3 and not np.isscalar(R_new[0]) and np.ndim(R_new[0]) == 1:
+        fault, indptr, indices, vals = _host_csr(R_new, n)
+        if fault == "shape":
+            raise ValueError("R_new as CSR must be 1-D (indptr, indices, vals) with integer indptr / indices")
+        if fault == "ptr":
+            raise ValueError("R_new: indptr must start at 0, not decrease, and end at len(indices) == len(vals)")
+        if fault == "range":
+            raise IndexError(f"R_new: column indices must lie in [0, {n})")
+        indices = indices.astype(np.int64)
+        vals = vals.astype(np.float64)
+    else:
+        R = np.asarray(R_new, dtype=np.float64)
+        if R.ndim != 2 or R.shape[1] != n:
+            raise ValueError(f"R_new must be a dense (B, {n}) array (NaN = missing) or a CSR triple, "
+                             f"got shape {R.shape}")
+        mask = ~np.isnan(R)
+        indptr = np.zeros(R.shape[0] + 1, dtype=np.int64)
+        np.cumsum(mask.sum(axis=1), out=indptr[1:])
+        indices = np.nonzero(mask)[1].astype(np.int64)
+        vals = R[mask]
+    vals32 = _finite_f32(vals, "R_new contains non-finite ratings (or ones beyond the float32 range)")
+    B = indptr.size - 1
+    row = np.repeat(np.arange(B, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((indices, row))
+    indices, vals32 = indices[order], vals32[order]
+    if indices.size > 1 and ((np.diff(indices) == 0) & (np.diff(row) == 0)).any():
+        raise ValueError("R_new has a duplicate column within a row")
+    return indptr, indices.astype(np.int32), vals32
+
+
+def new_item_features(features_new, W_dims: Dict[str, int], B: int) -> Dict[str, np.ndarray]:
+    """Validated features of new items: every feature of the fit (`W_dims`: name -> columns) and nothing else, each
+    a finite (B, d) array.  Raises ValueError otherwise."""
+    fn = host_features(features_new)
+    missing = [f for f in W_dims if f not in fn]
+    if missing:
+        raise ValueError(f"features_new must name every feature of the fit; missing: {missing}")
+    unknown = [f for f in fn if f not in W_dims]
+    if unknown:
+        raise ValueError(f"features_new names features the model was not fitted with: {unknown}")
+    out = {}
+    for f, d in W_dims.items():
+        X = np.asarray(fn[f])
+        if X.ndim != 2 or X.shape != (B, d):
+            raise ValueError(f"Feature '{f}' of the new items has shape {X.shape}; expected ({B}, {d})")
+        if not np.isfinite(X).all():
+            raise ValueError(f"Feature '{f}' of the new items contains non-finite values.")
+        out[f] = X
+    return out
+
+
+def new_item_graph_csr(S_new, B: int, n: int):
+    """Caller-supplied graph rows of new items -> host CSR (ptr int64 [B+1], idx int32 in [0, n), val float32).
+    Raises ValueError for a malformed triple, a wrong row count, an index outside [0, n) or a non-finite weight."""
+    if not (isinstance(S_new, (tuple, list)) and len(S_new) == 3):
+        raise ValueError("S_new must be a CSR triple (ptr, idx, val)")
+    fault, ptr, idx, val = _host_csr(S_new, n, nrows=B)
+    if fault == "shape":
+        raise ValueError("S_new must be 1-D (ptr, idx, val) with integer ptr / idx")
+    if fault == "rows":
+        raise ValueError(f"S_new has {ptr.size - 1} rows; expected {B} (one per new item)")
+    if fault == "ptr":
+        raise ValueError("S_new: ptr must start at 0, not decrease, and end at len(idx) == len(val)")
+    if fault == "range":
+        raise ValueError(f"S_new: item indices must lie in [0, {n}) (fitted items)")
+    return ptr, idx.astype(np.int32), _finite_f32(val, "S_new contains non-finite weights")
