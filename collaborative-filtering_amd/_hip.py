@@ -22,6 +22,7 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_topk_similarity", "als_graph_classify", "als_normalize_features", "als_impute_col_median",
            "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
            "als_recommend_workspace_bytes", "als_recommend_topk", "als_rank_count_workspace_bytes", "als_rank_count",
+           "als_recommend_topk_masked", "als_rank_count_masked",
            "als_fold_in", "als_fold_in_items", "als_explain")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -160,9 +161,13 @@ def load():
     lib.als_recommend_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
     lib.als_recommend_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_recommend_topk_masked.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_rank_count_workspace_bytes.argtypes = [C.c_int, _i64, _i64, _i64, C.c_int]
     lib.als_rank_count.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                    _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_rank_count_masked.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_fold_in.argtypes = [C.POINTER(FoldInParams), _vp]
     lib.als_fold_in_items.argtypes = [C.POINTER(FoldInItemsParams), _vp]
     lib.als_explain.argtypes = [C.POINTER(ExplainParams), _vp]

@@ -419,7 +419,8 @@ class ALS:
             return self._eng.predict_at(np.asarray(flat_idx, dtype=np.int64), features)
 
     def recommend(self, users=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
-                  exclude_seen: bool = True, new_items: Optional[FoldedItems] = None):
+                  exclude_seen: bool = True, new_items: Optional[FoldedItems] = None, items=None,
+                  filter_items=None):
         """Top-N items per user: returns (items int64 [B, N], scores float64 [B, N]), each row ordered by score
         descending, ties to the lower item index.
 
@@ -435,18 +436,28 @@ class ALS:
 
         `new_items` (a `fold_in_items` result): rank the n fitted items and the B folded ones together, folded item
         b as item n + b, scored as `predict_new_items`; with `exclude_seen` the folded items a user rated in their
-        ratings are left out as well."""
+        ratings are left out as well.
+
+        `items` (allow-list) / `filter_items` (block-list): restrict the catalogue to `items` minus `filter_items`.
+        Each is a 1-D array of item ids (any order, duplicates accepted) or a boolean mask over the catalogue;
+        None = no restriction.  An empty allow-list is legal (nothing is a candidate).  The restriction is applied
+        inside the kernel (a bitmap of one bit per item); 32-item chunks without an allowed item are not scored.
+        The contract above then holds with "all n items" replaced by "the allowed items"
+        (als_recommend_topk_masked).  With `new_items` the ids and the mask span the n + B items of the joint
+        catalogue."""
         features = self._check_predict(features)
         if new_items is not None:
             validate.folded_items(self, new_items)
         N = validate.top_count(N, "N")
         u = validate.user_ids(users, self.U.shape[0])
+        filters = validate.item_filters(items, filter_items,
+                                        self.V.shape[0] + (new_items.n_items if new_items is not None else 0))
         if u.size == 0:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             if new_items is not None:
-                return self._eng.recommend_with_items(self._dev_i32(u), N, features, exclude_seen, new_items)
-            return self._eng.recommend(self._dev_i32(u), N, features, exclude_seen)
+                return self._eng.recommend_with_items(self._dev_i32(u), N, features, exclude_seen, new_items, filters)
+            return self._eng.recommend(self._dev_i32(u), N, features, exclude_seen, filters)
 
     def fold_in(self, R_new, *, features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None):
         """Factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed: returns
@@ -469,22 +480,25 @@ class ALS:
             return U[:, :k].to(torch.float64).cpu().numpy(), b.to(torch.float64).cpu().numpy()
 
     def recommend_new(self, R_new, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
-                      n_sweeps: Optional[int] = None, exclude_seen: bool = True):
+                      n_sweeps: Optional[int] = None, exclude_seen: bool = True, items=None, filter_items=None):
         """Top-N items for users outside the fit: `fold_in(R_new, features=features, n_sweeps=n_sweeps)`, then
         the contract of `recommend` on the folded factors - (items int64 [B, N], scores float64 [B, N]), every
         score bitwise the predict epilogue U_b.Z_i + mu + b_b + b_i of the folded row; with `exclude_seen` the
-        items rated in R_new are never returned.  The folded factors stay on the device."""
+        items rated in R_new are never returned.  The folded factors stay on the device.  `items` /
+        `filter_items` as in `recommend`."""
         features = self._check_predict(features)
         N = validate.top_count(N, "N")
         T = validate.sweeps(n_sweeps)
         indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        filters = validate.item_filters(items, filter_items, self.V.shape[0])
         if indptr.size == 1:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
-            return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen)
+            return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen, filters)
 
     # ---------------------------------------------------------- evaluation
-    def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True):
+    def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                allow_items=None, filter_items=None):
         """Exact full-catalogue rank of item items[p] for user users[p], P pairs: returns
         (rank int64 [P], n_candidates int64 [P], scores float32 [P]).
 
@@ -495,30 +509,45 @@ class ALS:
         whether or not items[p] itself is seen (it is then the position the item would take); -1 when its score is
         NaN.  scores[p] == predict(features)[users[p], items[p]] exactly.  Order and duplicates of the pairs are
         kept.  `features` as in `predict`.  Nothing m x n is formed, and there is no limit like `recommend`'s
-        N <= 128: one fused kernel scores the catalogue and counts (als_rank_count).  Local to the calling rank."""
+        N <= 128: one fused kernel scores the catalogue and counts (als_rank_count).  Local to the calling rank.
+
+        `allow_items` / `filter_items`: `recommend`'s `items=` / `filter_items=` (the allow-list has another name
+        here because `items` are the targets): the candidates are intersected with `allow_items` minus
+        `filter_items`, and n_candidates counts that intersection.  As for a seen target, the rank of a target that
+        is itself not allowed is still defined - the position it would take - so an item
+        `recommend(..., items=A, filter_items=F)` returns at position j has rank j under allow_items=A,
+        filter_items=F (als_rank_count_masked)."""
         features = self._check_predict(features)
         u, i = self._check_pairs(users, items)
+        filters = validate.item_filters(allow_items, filter_items, self.V.shape[0])
         if u.size == 0:
             return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
         with _on(self._eng.dev):
-            return self._eng.rank_of(self._dev_i32(u), self._dev_i32(i), features, exclude_seen)
+            return self._eng.rank_of(self._dev_i32(u), self._dev_i32(i), features, exclude_seen, filters)
 
     def rank_of_new(self, R_new, targets, *, features: Optional[Dict[str, np.ndarray]] = None,
-                    n_sweeps: Optional[int] = None, exclude_seen: bool = True):
+                    n_sweeps: Optional[int] = None, exclude_seen: bool = True, items=None, filter_items=None,
+                    allow_items=None):
         """`rank_of` for users outside the fit: `fold_in(R_new, features=features, n_sweeps=n_sweeps)`, then the
         ranks of each new row's target items among the candidates `recommend_new` ranks (with `exclude_seen` the
         items rated in R_new are no candidates).  `targets` = (indptr [B + 1], items): row b's targets are
         items[indptr[b]:indptr[b + 1]].  Returns (rank, n_candidates, scores) as `rank_of`, one entry per target in
-        the order of `items`."""
+        the order of the targets.  `items` (the allow-list) / `filter_items` restrict the candidates as in
+        `rank_of`; `allow_items` is accepted as another name of `items`, so that the two rank calls can be written
+        alike (giving both is an error)."""
         features = self._check_predict(features)
         T = validate.sweeps(n_sweeps)
         n = self.V.shape[0]
         indptr, indices, vals = fold_in_csr(R_new, n)
         tptr, ti = validate.target_lists(targets, indptr.size - 1, n)
+        if items is not None and allow_items is not None:
+            raise ValueError("items and allow_items name the same allow-list; pass one of them")
+        filters = validate.item_filters(items if allow_items is None else allow_items, filter_items, n)
         if ti.size == 0:
             return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
         with _on(self._eng.dev):
-            return self._eng.rank_of_new(indptr, indices, vals, tptr, ti.astype(np.int32), features, T, exclude_seen)
+            return self._eng.rank_of_new(indptr, indices, vals, tptr, ti.astype(np.int32), features, T, exclude_seen,
+                                         filters)
 
     def _seen_pairs(self, users, items) -> np.ndarray:
         """bool [P]: items[p] is among the ratings of users[p] in the last fit (what `exclude_seen` leaves out)."""

@@ -281,22 +281,53 @@ class HipBackend:
                        top_cnt):
         """Top-`topn` items of every user in `users` (int32), seen items (CSR by user id; None = none) left out:
         als_recommend_topk.  The item-slice workspace is owned here and grows as needed."""
+        self._recommend(self.lib.als_recommend_topk, "als_recommend_topk", (), k, ld, users, n, U, Z, b_u, b_i, mu,
+                        seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
+
+    def recommend_topk_masked(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, topn, top_val,
+                              top_idx, top_cnt):
+        """`recommend_topk` over the items of the bitmap `allow` (int32 [ceil(n / 32)], item i = bit i & 31 of word
+        i >> 5): als_recommend_topk_masked."""
+        self._check_bitmap(allow, n)
+        self._recommend(self.lib.als_recommend_topk_masked, "als_recommend_topk_masked", (_p(allow),), k, ld, users,
+                        n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
+
+    def _check_bitmap(self, allow: torch.Tensor, n: int):
+        # the kernels index the words by item: a short bitmap would be an out-of-bounds read
+        if (allow.dtype != torch.int32 or not allow.is_cuda or not allow.is_contiguous()
+                or allow.numel() < (n + 31) // 32):
+            raise ValueError(f"allow bitmap must be a contiguous int32 device tensor of {(n + 31) // 32} words")
+
+    def _recommend(self, fn, what, allow, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val,
+                   top_idx, top_cnt):
         if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
             seen_ptr = seen_idx = None
         nsl = self.recommend_slices()
         need = int(self.lib.als_recommend_workspace_bytes(users.numel(), n, topn, nsl))
         if need > 0 and (self._rec_ws is None or self._rec_ws.numel() < need):
             self._rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._check(self.lib.als_recommend_topk(k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i),
-                                                _p(mu), _p(seen_ptr), _p(seen_idx), topn, nsl, _p(top_val),
-                                                _p(top_idx), _p(top_cnt), _p(self._rec_ws) if need > 0 else None, need,
-                                                self._stream()), "als_recommend_topk")
+        self._check(fn(k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr),
+                       _p(seen_idx), *allow, topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
+                       _p(self._rec_ws) if need > 0 else None, need, self._stream()), what)
 
     def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score,
                    above, n_cand):
         """For every target of every batch row (user q_users[b], targets q_items[q_ptr[b]:q_ptr[b+1]]) the score
         and the number of unseen items ranked above it, and per row the number of candidates: als_rank_count.
         The item-slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
+        self._rank(self.lib.als_rank_count, "als_rank_count", (), k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx,
+                   q_users, q_ptr, q_items, t_score, above, n_cand)
+
+    def rank_count_masked(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, q_users, q_ptr, q_items,
+                          t_score, above, n_cand):
+        """`rank_count` with the candidates limited to the bitmap `allow` (as `recommend_topk_masked`):
+        als_rank_count_masked."""
+        self._check_bitmap(allow, n)
+        self._rank(self.lib.als_rank_count_masked, "als_rank_count_masked", (_p(allow),), k, ld, n, U, Z, b_u, b_i, mu,
+                   seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above, n_cand)
+
+    def _rank(self, fn, what, allow, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items,
+              t_score, above, n_cand):
         if seen_idx is not None and seen_idx.numel() == 0:
             seen_ptr = seen_idx = None
         nq, nt = q_users.numel(), q_items.numel()
@@ -304,11 +335,10 @@ class HipBackend:
         need = int(self.lib.als_rank_count_workspace_bytes(k, nq, nt, n, nsl))
         if need > 0 and (self._rank_ws is None or self._rank_ws.numel() < need):
             self._rank_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        self._check(self.lib.als_rank_count(k, ld, n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr),
-                                            _p(seen_idx), nq, _p(q_users), _p(q_ptr), _p(q_items) if nt else None, nt,
-                                            nsl, _p(t_score) if nt else None, _p(above) if nt else None, _p(n_cand),
-                                            _p(self._rank_ws) if need > 0 else None, need, self._stream()),
-                    "als_rank_count")
+        self._check(fn(k, ld, n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr), _p(seen_idx), *allow, nq,
+                       _p(q_users), _p(q_ptr), _p(q_items) if nt else None, nt, nsl, _p(t_score) if nt else None,
+                       _p(above) if nt else None, _p(n_cand), _p(self._rank_ws) if need > 0 else None, need,
+                       self._stream()), what)
 
     # -- K9 --------------------------------------------------------------------
     def fold_in(self, *, k, ld, indptr, indices, vals, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, U_out, b_u_out,

@@ -19,6 +19,11 @@
 //
 // Item split as k_recommend (grid.y): a sliced call writes its counts to workspace [slice][nt + nq] and
 // k_rank_reduce adds them - integers, so the result cannot depend on the slice count.
+//
+// Allow bitmap (als_rank_count_masked; the MASKED instantiations) as k_recommend's: one wave-uniform word per chunk,
+// ANDed into the candidate test - so into `above` and `n_cand` alike -, chunks whose word is 0 skipped by the whole
+// workgroup, the prefetch aimed at the next chunk with a set bit.  Target scores are formed whether or not the
+// target is allowed.  The unmasked instantiations contain none of this.
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "topk_common.hpp"
@@ -33,14 +38,14 @@ constexpr int RK_TG = 8;            // targets per skip group
 constexpr int RK_MIN_SLICE = 2048;  // automatic slicing keeps at least this many items per slice
 constexpr unsigned long long RK_NONE = ~0ull;   // target key of a NaN score / an unused slot: nothing is above it
 
-template <int KB, int NW>
+template <int KB, int NW, bool MASKED>
 __global__ __launch_bounds__(NW * 64)
 void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const int64_t* __restrict__ q_ptr,
                   const int32_t* __restrict__ q_items, int64_t n, int64_t slice, const float* __restrict__ U,
                   const float* __restrict__ Z, const float* __restrict__ b_u, const float* __restrict__ b_i,
                   const double* __restrict__ mu_p, const int64_t* __restrict__ seen_ptr,
                   const int32_t* __restrict__ seen_idx, float* __restrict__ t_score, int32_t* __restrict__ above,
-                  int32_t* __restrict__ n_cand, int64_t slice_stride) {
+                  int32_t* __restrict__ n_cand, int64_t slice_stride, const uint32_t* __restrict__ allow) {
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = LD + 4;        // LDS row stride: +16 B spreads lanes c over the banks
     constexpr int NT = NW * 64, NV = RK_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     __shared__ unsigned long long tks[NW * 16][RK_TP];
@@ -106,6 +111,24 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
     };
 
     const int64_t nch = hi > lo ? (hi - lo + RK_CHUNK - 1) / RK_CHUNK : 0;
+    const uint32_t* aw = MASKED ? allow + lo / RK_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
+    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
+    auto next_chunk = [&](int64_t ch) -> int64_t {
+        for (; ch < nch; ch += 64) {
+            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
+            const unsigned long long m = __ballot(w != 0u);
+            if (m) return ch + __builtin_ctzll(m);
+        }
+        return nch;
+    };
+    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
+    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
+    unsigned pw = 0u;
+    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
+    auto after = [&](int64_t ch) -> int64_t {
+        const unsigned long long m = __ballot(pw != 0u);
+        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
+    };
     for (int pass = 0; pass < npass; ++pass) {
         const int64_t t0 = (int64_t)pass * RK_TP;                        // first target of this pass
         const int wt = (int)max(min(wtn - t0, (int64_t)RK_TP), (int64_t)0);      // targets of the wave's fullest row
@@ -160,6 +183,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
         }
 
+        unsigned deny = 0u; // MASKED: bit c set = item cb + c of the block `keys_of` is called for is not allowed
         // one 16-item block [cb, cb + 16): keys of the lane's four scores, 0 where the score is no candidate
         auto keys_of = [&](const f32x4& acc, int64_t cb, unsigned long long (&key)[4]) {
             unsigned msk[4] = {0u, 0u, 0u, 0u};
@@ -191,6 +215,10 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
                     if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
                 }
             }
+            if constexpr (MASKED) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) msk[r] |= deny;
+            }
             const int64_t col = cb + c;
             const float bi = b_i[min(col, n - 1)];
 #pragma unroll
@@ -202,13 +230,22 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             }
         };
 
-        if (nch > 0) fetch(lo);
-        for (int64_t ch = 0; ch < nch; ++ch) {
+        int64_t nx = 0;                                  // MASKED: the chunk after ch that is counted
+        if constexpr (MASKED) {
+            nx = next_chunk(0);
+            if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }
+        } else if (nch > 0) fetch(lo);
+        for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
             const int64_t it0 = lo + ch * RK_CHUNK;
+            unsigned word = 0u;
+            if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
             __syncthreads();                             // every wave is done with the previous chunk
             stage();
             __syncthreads();
-            if (ch + 1 < nch) fetch(it0 + RK_CHUNK);
+            if constexpr (MASKED) {
+                nx = after(ch);
+                if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }      // however far ahead
+            } else if (ch + 1 < nch) fetch(it0 + RK_CHUNK);
             if (!active) continue;                       // wave-uniform: this wave's rows have no targets left
             float z0[E], z1[E];
             load_frow<E>(&zs[c][E * q], z0);
@@ -220,7 +257,9 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
             }
             unsigned long long k0[4], k1[4];
+            if constexpr (MASKED) deny = ~word & 0xFFFFu;
             keys_of(acc0, it0, k0);
+            if constexpr (MASKED) deny = ~word >> 16;
             keys_of(acc1, it0 + 16, k1);
 #pragma unroll
             for (int g = 0; g < RK_TP / RK_TG; ++g) {
@@ -307,14 +346,15 @@ int rank_slices(int ld, int64_t nq, int64_t n, int nslices) {
 template <int KB>
 int launch_rank(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, const int32_t* q_items, int64_t n,
                 int nsl, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
-                const int64_t* seen_ptr, const int32_t* seen_idx, float* t_score, int32_t* above, int32_t* n_cand,
-                int64_t slice_stride, hipStream_t st) {
+                const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, float* t_score, int32_t* above,
+                int32_t* n_cand, int64_t slice_stride, hipStream_t st) {
     constexpr int NW = rk_waves(KB);
     const int64_t nchunks = (n + RK_CHUNK - 1) / RK_CHUNK;
     const int64_t slice = (nchunks + nsl - 1) / nsl * RK_CHUNK;
     const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
-    hipLaunchKernelGGL((k_rank_count<KB, NW>), grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n, slice, U,
-                       Z, b_u, b_i, mu, seen_ptr, seen_idx, t_score, above, n_cand, slice_stride);
+    auto kern = allow ? k_rank_count<KB, NW, true> : k_rank_count<KB, NW, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n, slice, U, Z, b_u, b_i, mu,
+                       seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, allow);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
@@ -327,11 +367,12 @@ extern "C" size_t als_rank_count_workspace_bytes(int k, int64_t nq, int64_t nt, 
     return s > 1 ? (size_t)s * (size_t)(nt + nq) * sizeof(int32_t) : 0;
 }
 
-extern "C" int als_rank_count(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
-                              const float* b_i, const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
-                              int64_t nq, const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items,
-                              int64_t nt, int nslices, float* t_score, int32_t* above, int32_t* n_cand,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int als_rank_count_masked(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
+                                     const float* b_i, const double* mu, const int64_t* seen_ptr,
+                                     const int32_t* seen_idx, const uint32_t* allow, int64_t nq,
+                                     const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items, int64_t nt,
+                                     int nslices, float* t_score, int32_t* above, int32_t* n_cand, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
     const int kp = als_padded_k(k);
     if (kp < 0) return ALS_E_BADK;
     if (ld != kp || nq < 0 || nt < 0 || n < 1 || n >= ((int64_t)1 << 31) || nslices < 0 ||
@@ -350,7 +391,8 @@ extern "C" int als_rank_count(int k, int ld, int64_t n, const float* U, const fl
     int rc;
 #define ALS_RK_CASE(KB) \
     case KB: rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, \
-                                  t_score, part ? part : above, part ? part + nt : n_cand, part ? nt + nq : 0, st); break;
+                                  allow, t_score, part ? part : above, part ? part + nt : n_cand, part ? nt + nq : 0, \
+                                  st); break;
     switch (ld / 16) {
         ALS_RK_CASE(1) ALS_RK_CASE(2) ALS_RK_CASE(3) ALS_RK_CASE(4) ALS_RK_CASE(5)
         ALS_RK_CASE(6) ALS_RK_CASE(7) ALS_RK_CASE(8) ALS_RK_CASE(9) ALS_RK_CASE(10)
@@ -361,4 +403,13 @@ extern "C" int als_rank_count(int k, int ld, int64_t n, const float* U, const fl
     hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
                        above, n_cand);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+extern "C" int als_rank_count(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
+                              const float* b_i, const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
+                              int64_t nq, const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items,
+                              int64_t nt, int nslices, float* t_score, int32_t* above, int32_t* n_cand,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    return als_rank_count_masked(k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, nullptr, nq, q_users, q_ptr, q_items,
+                                 nt, nslices, t_score, above, n_cand, workspace, workspace_bytes, stream);
 }

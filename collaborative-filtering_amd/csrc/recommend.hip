@@ -19,6 +19,14 @@
 // nslices slices (grid.y); each workgroup writes its per-(slice, user) list as raw keys to the workspace, and
 // k_recommend_merge merges the lists of every user with the same 256-key sort.  The order is total, so the
 // result does not depend on the slice count.
+//
+// Allow bitmap (als_recommend_topk_masked; the MASKED instantiations): slices start at multiples of 32, so chunk ch
+// of a slice is word lo / 32 + ch of the bitmap - one wave-uniform word per chunk.  Its low half joins block 0's
+// pass test, its high half block 1's.  A chunk whose word is 0 is never fetched, staged or scored: every wave finds
+// the next chunk with a set bit by the same scan (64 words per step: one per lane, ballot, count trailing zeros),
+// so the workgroup's barriers stay matched and the prefetch goes to the chunk that is scored next.  The seen cursors
+// catch up on their own: the exclusion walk consumes every entry below the block it is asked about.  The unmasked
+// instantiations contain none of this: they are the code they were before the bitmap existed.
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "topk_common.hpp"
@@ -37,14 +45,14 @@ constexpr int RC_MIN_SLICE = 2048;  // automatic slicing keeps at least this man
 __device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 
 // CAP keys per user: list [0, L) + survivor buffer [L, CAP)
-template <int KB, int NW, int CAP>
+template <int KB, int NW, int CAP, bool MASKED>
 __global__ __launch_bounds__(NW * 64)
 void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t n, int64_t slice,
                  const float* __restrict__ U, const float* __restrict__ Z, const float* __restrict__ b_u,
                  const float* __restrict__ b_i, const double* __restrict__ mu_p,
                  const int64_t* __restrict__ seen_ptr, const int32_t* __restrict__ seen_idx, int topn,
                  float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt,
-                 unsigned long long* __restrict__ part) {
+                 unsigned long long* __restrict__ part, const uint32_t* __restrict__ allow) {
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = LD + 4;        // LDS row stride: +16 B spreads lanes c over the banks
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
     constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
@@ -114,6 +122,7 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
             if (q == rq && e == re) { thr[e] = t; cnt[e] = 0; nlist[e] = nn; }
     };
 
+    unsigned deny = 0u;     // MASKED: bit c set = item cb + c of the block `select` is called for is not allowed
     // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold test, append
     auto select = [&](const f32x4& acc, int64_t cb) {
         unsigned msk[4] = {0u, 0u, 0u, 0u};
@@ -144,6 +153,10 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
                 }
                 if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
             }
+        }
+        if constexpr (MASKED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) msk[r] |= deny;
         }
         const int64_t col = cb + c;
         const float bi = b_i[min(col, n - 1)];
@@ -182,13 +195,40 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     };
 
     const int64_t nch = hi > lo ? (hi - lo + RC_CHUNK - 1) / RC_CHUNK : 0;
-    if (nch > 0) fetch(lo);
-    for (int64_t ch = 0; ch < nch; ++ch) {
+    const uint32_t* aw = MASKED ? allow + lo / RC_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
+    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
+    auto next_chunk = [&](int64_t ch) -> int64_t {
+        for (; ch < nch; ch += 64) {
+            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
+            const unsigned long long m = __ballot(w != 0u);
+            if (m) return ch + __builtin_ctzll(m);
+        }
+        return nch;
+    };
+    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
+    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
+    unsigned pw = 0u;
+    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
+    auto after = [&](int64_t ch) -> int64_t {
+        const unsigned long long m = __ballot(pw != 0u);
+        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
+    };
+    int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
+    if constexpr (MASKED) {
+        nx = next_chunk(0);
+        if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }
+    } else if (nch > 0) fetch(lo);
+    for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
         const int64_t it0 = lo + ch * RC_CHUNK;
+        unsigned word = 0u;
+        if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
         __syncthreads();                                 // every wave is done with the previous chunk
         stage();
         __syncthreads();
-        if (ch + 1 < nch) fetch(it0 + RC_CHUNK);
+        if constexpr (MASKED) {
+            nx = after(ch);
+            if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }      // however far ahead
+        } else if (ch + 1 < nch) fetch(it0 + RC_CHUNK);
         float z0[E], z1[E];
         load_frow<E>(&zs[c][E * q], z0);
         load_frow<E>(&zs[16 + c][E * q], z1);
@@ -198,7 +238,9 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
             acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
         }
+        if constexpr (MASKED) deny = ~word & 0xFFFFu;
         select(acc0, it0);
+        if constexpr (MASKED) deny = ~word >> 16;
         select(acc1, it0 + 16);
         bool full = false;
 #pragma unroll
@@ -295,19 +337,21 @@ int rec_slices(int64_t nusers, int64_t n, int topn, int nslices) {
 template <int KB>
 int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
                      const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
-                     const int32_t* seen_idx, int topn, float* tv, int32_t* ti, int32_t* tc,
+                     const int32_t* seen_idx, const uint32_t* allow, int topn, float* tv, int32_t* ti, int32_t* tc,
                      unsigned long long* part, hipStream_t st) {
     // slice length: a whole number of chunks, so every slice but the last is full
     const int64_t nchunks = (n + RC_CHUNK - 1) / RC_CHUNK;
     const int64_t slice = (nchunks + nsl - 1) / nsl * RC_CHUNK;
     if (topn <= 32) {
         const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
-        hipLaunchKernelGGL((k_recommend<KB, RC_NARROW / 16, 128>), grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users,
-                           n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part);
+        auto kern = allow ? k_recommend<KB, RC_NARROW / 16, 128, true> : k_recommend<KB, RC_NARROW / 16, 128, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow);
     } else {
         const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
-        hipLaunchKernelGGL((k_recommend<KB, RC_WIDE / 16, 256>), grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users,
-                           n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part);
+        auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true> : k_recommend<KB, RC_WIDE / 16, 256, false>;
+        hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow);
     }
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
@@ -320,11 +364,12 @@ extern "C" size_t als_recommend_workspace_bytes(int64_t nusers, int64_t n, int t
     return s > 1 ? (size_t)s * (size_t)nusers * (size_t)topn * sizeof(unsigned long long) : 0;
 }
 
-extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
-                                  const float* Z, const float* b_u, const float* b_i, const double* mu,
-                                  const int64_t* seen_ptr, const int32_t* seen_idx, int topn, int nslices,
-                                  float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+extern "C" int als_recommend_topk_masked(int k, int ld, int64_t nusers, const int32_t* users, int64_t n,
+                                         const float* U, const float* Z, const float* b_u, const float* b_i,
+                                         const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
+                                         const uint32_t* allow, int topn, int nslices, float* top_val,
+                                         int32_t* top_idx, int32_t* top_cnt, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
     const int kp = als_padded_k(k);
     if (kp < 0) return ALS_E_BADK;
     if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
@@ -340,8 +385,8 @@ extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* 
     hipStream_t st = (hipStream_t)stream;
     int rc;
 #define ALS_RC_CASE(KB) \
-    case KB: rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, \
-                                       top_val, top_idx, top_cnt, part, st); break;
+    case KB: rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, \
+                                       topn, top_val, top_idx, top_cnt, part, st); break;
     switch (ld / 16) {
         ALS_RC_CASE(1) ALS_RC_CASE(2) ALS_RC_CASE(3) ALS_RC_CASE(4) ALS_RC_CASE(5)
         ALS_RC_CASE(6) ALS_RC_CASE(7) ALS_RC_CASE(8) ALS_RC_CASE(9) ALS_RC_CASE(10)
@@ -352,4 +397,13 @@ extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* 
     hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
                        top_val, top_idx, top_cnt);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                                  const float* Z, const float* b_u, const float* b_i, const double* mu,
+                                  const int64_t* seen_ptr, const int32_t* seen_idx, int topn, int nslices,
+                                  float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return als_recommend_topk_masked(k, ld, nusers, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, nullptr, topn,
+                                     nslices, top_val, top_idx, top_cnt, workspace, workspace_bytes, stream);
 }

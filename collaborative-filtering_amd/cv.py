@@ -33,6 +33,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import validate
 from .als import ALS
 from .helpers import DEFAULT_RANDOM_STATE, ES_MIN_ITERS, ES_TOL, make_config, normalize_params
 
@@ -120,8 +121,25 @@ def rmse_at(y_true: np.ndarray, y_pred: np.ndarray) -> float:
     return float(np.sqrt(np.mean((np.asarray(y_true) - np.asarray(y_pred)) ** 2)))
 
 
+def _item_filter(model, cols: np.ndarray, items, filter_items, allow_name: str = "items"):
+    """The pass-through of `items=` / `filter_items=` (ALS.recommend) in the ranking measures: (keep, kw) - keep[p]
+    False when the held-out item cols[p] is not allowed (such a pair cannot be ranked within the restricted
+    catalogue and is left out), kw the keywords for the model's call ({} when neither is given: the call is then
+    today's), the allow-list under `allow_name` (the rank calls take it as allow_items)."""
+    if items is None and filter_items is None:
+        return np.ones(cols.size, dtype=bool), {}
+    validate.fitted(model)
+    n = model.V.shape[0]
+    mask = validate.allowed_mask(validate.item_filters(items, filter_items, n), n)
+    inside = (cols >= 0) & (cols < n)
+    keep = np.zeros(cols.size, dtype=bool)
+    keep[inside] = mask[cols[inside]]
+    kw = {"filter_items": filter_items} if items is None else {allow_name: items, "filter_items": filter_items}
+    return keep, kw
+
+
 def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
-                 features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+                 features: Optional[Dict[str, np.ndarray]] = None, items=None, filter_items=None) -> Dict[str, Any]:
     """recall@K and NDCG@K of `model.recommend` on held-out (user, item) pairs (new: the reference evaluates RMSE
     only).  For every user u of the held-out set:
 
@@ -132,7 +150,11 @@ def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: 
       NDCG@K(u)    = DCG@K(u) / IDCG@K(u),  IDCG@K(u) = sum over r = 1 .. min(K, |rel(u)|) of 1 / log2(r + 1)
 
     Users with an empty rel(u) are left out; the result holds the means over the others:
-    {"users": their number, "recall@K": mean recall, "ndcg@K": mean NDCG} (NaN means when no user is left)."""
+    {"users": their number, "recall@K": mean recall, "ndcg@K": mean NDCG} (NaN means when no user is left).
+
+    `items` / `filter_items` (as `ALS.recommend`): the measures within the restricted catalogue - top(u) is taken
+    among the allowed items, held-out pairs whose item is not allowed are left out of rel(u), and the result gains
+    "filtered_out", their number (after `min_rating`)."""
     rows = np.asarray(rows, dtype=np.int64).ravel()
     cols = np.asarray(cols, dtype=np.int64).ravel()
     if rows.shape != cols.shape:
@@ -142,11 +164,14 @@ def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: 
             raise ValueError("min_rating needs the held-out ratings (vals)")
         keep = np.asarray(vals, dtype=np.float64).ravel() >= min_rating
         rows, cols = rows[keep], cols[keep]
+    allowed, kw = _item_filter(model, cols, items, filter_items)
+    extra = {"filtered_out": int((~allowed).sum())} if kw else {}
+    rows, cols = rows[allowed], cols[allowed]
     users, ub = np.unique(rows, return_inverse=True)
     if users.size == 0:
-        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan")}
-    items, _ = model.recommend(users, K, features=features)
-    return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
+        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan"), **extra}
+    top, _ = model.recommend(users, K, features=features, **kw)
+    return {**_ranking_metrics(top, ub, cols, model.V.shape[0], K), **extra}
 
 
 def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int) -> Dict[str, Any]:
@@ -166,7 +191,7 @@ def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_item
 
 def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating: Optional[float] = None,
                          features: Optional[Dict[str, np.ndarray]] = None,
-                         n_sweeps: Optional[int] = None) -> Dict[str, Any]:
+                         n_sweeps: Optional[int] = None, items=None, filter_items=None) -> Dict[str, Any]:
     """recall@K and NDCG@K for users outside the fit (strong generalisation): every user of `held_out` is folded
     in from its `known` ratings (`model.recommend_new`, the known items excluded) and scored on its held-out items
     with the definitions of `ranking_at_k`.
@@ -174,7 +199,7 @@ def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating
     known: (rows, cols, vals) - the new users' ratings that the model may see; held_out: (rows, cols) or
     (rows, cols, vals).  Row ids are labels of the new users shared by the two sets (any integers; they are not
     user ids of the fit).  A held-out user without known ratings is scored with zero factors (mu + b_i).
-    min_rating, features, n_sweeps: as in ranking_at_k / ALS.fold_in."""
+    min_rating, features, n_sweeps, items, filter_items: as in ranking_at_k / ALS.fold_in."""
     if len(known) != 3:
         raise ValueError("known must be (rows, cols, vals)")
     if len(held_out) not in (2, 3):
@@ -188,9 +213,12 @@ def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating
             raise ValueError("min_rating needs the held-out ratings (vals)")
         keep = np.asarray(held_out[2], dtype=np.float64).ravel() >= min_rating
         rows, cols = rows[keep], cols[keep]
+    allowed, kw = _item_filter(model, cols, items, filter_items)
+    extra = {"filtered_out": int((~allowed).sum())} if kw else {}
+    rows, cols = rows[allowed], cols[allowed]
     users, ub = np.unique(rows, return_inverse=True)
     if users.size == 0:
-        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan")}
+        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan"), **extra}
     kr = np.asarray(known[0], dtype=np.int64).ravel()
     kc = np.asarray(known[1], dtype=np.int64).ravel()
     kv = np.asarray(known[2], dtype=np.float64).ravel()
@@ -202,8 +230,8 @@ def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating
     order = np.argsort(pos, kind="stable")
     indptr = np.zeros(users.size + 1, dtype=np.int64)
     np.cumsum(np.bincount(pos, minlength=users.size), out=indptr[1:])
-    items, _ = model.recommend_new((indptr, kc[order], kv[order]), K, features=features, n_sweeps=n_sweeps)
-    return _ranking_metrics(items, ub, cols, model.V.shape[0], K)
+    top, _ = model.recommend_new((indptr, kc[order], kv[order]), K, features=features, n_sweeps=n_sweeps, **kw)
+    return {**_ranking_metrics(top, ub, cols, model.V.shape[0], K), **extra}
 
 
 def _check_Ks(Ks) -> Tuple[int, ...]:
@@ -264,7 +292,7 @@ def _held_out_pairs(rows, cols, vals, min_rating, what: str = ""):
 
 def rank_metrics(model: ALS, rows, cols, vals=None, *, Ks: Sequence[int] = (10, 100),
                  min_rating: Optional[float] = None,
-                 features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+                 features: Optional[Dict[str, np.ndarray]] = None, items=None, filter_items=None) -> Dict[str, Any]:
     """Full-catalogue ranking measures of held-out (user, item) pairs from exact ranks (`model.rank_of`; no
     sampled negatives, no list limit).  Arguments as `ranking_at_k`.  For every user u of the held-out set, with
     rel(u) as in `ranking_at_k` (duplicates merged), c(u) the number of candidates (items that are neither
@@ -281,27 +309,33 @@ def rank_metrics(model: ALS, rows, cols, vals=None, *, Ks: Sequence[int] = (10, 
       mpr(u)      = mean over t of rho_t / max(c(u) - 1, 1)   (mean percentile rank, 0 = best).
 
     Returns the means over users under "recall@K", "ndcg@K" (per K), "mrr", "auc", "mpr", with "users", "pairs"
-    (kept, after merging) and "dropped" (NaN means when no user is left)."""
+    (kept, after merging) and "dropped" (NaN means when no user is left).
+
+    `items` / `filter_items` (as `ALS.recommend`): the measures within the restricted catalogue - the candidates
+    are intersected with the allowed items (`ALS.rank_of`), and a pair whose item is not allowed is dropped and
+    counted in "dropped" like a training pair."""
     Ks = _check_Ks(Ks)
     rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
     if rows.size:
         w = max(model.V.shape[0] if model.V is not None else 1, int(cols.max()) + 1)
         rows, cols = np.divmod(np.unique(rows * w + cols), w)           # duplicates merged
-    rank, cand, _ = model.rank_of(rows, cols, features=features)
+    allowed, kw = _item_filter(model, cols, items, filter_items, "allow_items")
+    rank, cand, _ = model.rank_of(rows, cols, features=features, **kw)
     if rows.size == 0:
         return _empty_rank_metrics(Ks, 0, 0)
-    keep = ~model._seen_pairs(rows, cols) & (rank >= 0)
+    keep = ~model._seen_pairs(rows, cols) & (rank >= 0) & allowed
     _, ub = np.unique(rows[keep], return_inverse=True)
     return _rank_metrics(ub, rank[keep], cand[keep], int((~keep).sum()), Ks)
 
 
 def fold_in_rank_metrics(model: ALS, known, held_out, *, Ks: Sequence[int] = (10, 100),
                          min_rating: Optional[float] = None, features: Optional[Dict[str, np.ndarray]] = None,
-                         n_sweeps: Optional[int] = None) -> Dict[str, Any]:
+                         n_sweeps: Optional[int] = None, items=None, filter_items=None) -> Dict[str, Any]:
     """`rank_metrics` for users outside the fit (strong generalisation), with the conventions of
     `fold_in_ranking_at_k`: every user of `held_out` is folded in from its `known` ratings (`model.rank_of_new`,
     the known items are no candidates) and its held-out items are ranked.  A held-out pair whose item is among the
-    user's known items is dropped and counted, as is one with a NaN score."""
+    user's known items is dropped and counted, as is one with a NaN score - and, with `items` / `filter_items`
+    (as in `rank_metrics`), one whose item is not allowed."""
     Ks = _check_Ks(Ks)
     if len(known) != 3:
         raise ValueError("known must be (rows, cols, vals)")
@@ -330,9 +364,10 @@ def fold_in_rank_metrics(model: ALS, known, held_out, *, Ks: Sequence[int] = (10
     np.cumsum(np.bincount(pos, minlength=users.size), out=indptr[1:])
     tptr = np.zeros(users.size + 1, dtype=np.int64)
     np.cumsum(np.bincount(ub, minlength=users.size), out=tptr[1:])
+    allowed, kw = _item_filter(model, cols, items, filter_items, "allow_items")
     rank, cand, _ = model.rank_of_new((indptr, kc[order], kv[order]), (tptr, cols), features=features,
-                                      n_sweeps=n_sweeps)
-    keep = ~np.isin(ub * w + cols, pos * w + kc) & (rank >= 0)
+                                      n_sweeps=n_sweeps, **kw)
+    keep = ~np.isin(ub * w + cols, pos * w + kc) & (rank >= 0) & allowed
     _, ubk = np.unique(ub[keep], return_inverse=True)
     return _rank_metrics(ubk, rank[keep], cand[keep], int((~keep).sum()), Ks)
 

@@ -71,6 +71,17 @@ def concat_features(features, names) -> np.ndarray:
     return np.concatenate([np.asarray(features[f], dtype=np.float32) for f in names], axis=1)
 
 
+def pack_bitmap(mask: torch.Tensor) -> torch.Tensor:
+    """The allow bitmap of als_recommend_topk_masked / als_rank_count_masked from a bool tensor [n] (any device):
+    int32 [ceil(n / 32)], item i = bit i & 31 of word i >> 5 (bit 31 is the sign bit), the bits beyond n zero."""
+    n = mask.numel()
+    nw = (n + 31) // 32
+    bits = torch.zeros(nw * 32, dtype=torch.int64, device=mask.device)
+    bits[:n] = mask
+    words = (bits.view(nw, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(dim=1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
 def _raise_unless_solved(status: torch.Tensor, what: str, row_name=lambda r: f"row {r}") -> None:
     """`status` is the one-word result of a solve kernel: 0, or 1 + the first row whose system failed."""
     bad = int(status.item())
@@ -124,6 +135,23 @@ class _Serving:
             idx, val = np.zeros(1, np.int32), np.zeros(1, np.float32)
         return tuple(a if torch.is_tensor(a) else torch.from_numpy(a).to(self.dev) for a in (ptr, idx, val))
 
+    def allow_bitmap(self, filters, n_total: int) -> Optional[torch.Tensor]:
+        """Device bitmap (`pack_bitmap`) of a validated (items, filter_items) pair (validate.item_filters) over
+        n_total items: `items` minus `filter_items`, scattered and packed on the device, once per call.  None for
+        None: the unfiltered path."""
+        if filters is None:
+            return None
+        allow, block = filters
+        mask = torch.ones(n_total, dtype=torch.bool, device=self.dev)
+        for a, keep in ((allow, True), (block, False)):
+            if a is None:
+                continue
+            a = torch.from_numpy(a).to(self.dev)
+            if a.dtype != torch.bool:                                    # ids -> mask (duplicates write the same value)
+                a = torch.zeros(n_total, dtype=torch.bool, device=self.dev).index_fill_(0, a, True)
+            mask = a if keep else mask & ~a
+        return pack_bitmap(mask)
+
     def _fitted_rows(self, users: torch.Tensor, exclude_seen: bool):
         """Chunk source of the drivers below for users of the fit: the ids index the resident tables, the seen
         items are the training CSR."""
@@ -145,9 +173,11 @@ class _Serving:
             return users[:nb], U[b0:], b_u[b0:], seen_ptr, seen_idx
         return rows
 
-    def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False):
+    def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False,
+                     allow: Optional[torch.Tensor] = None):
         """als_recommend_topk over B batch rows in REC_BATCH chunks.  rows(b0, nb) -> (users int32 [nb], U, b_u,
-        seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu).  Returns host
+        seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu); `allow`: the
+        bitmap of the call (`allow_bitmap`) - every chunk then goes through als_recommend_topk_masked.  Returns host
         (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk, or with `on_device` the kernel's own
         (top_val fp32 [B, N], top_idx int32 [B, N])."""
         if on_device:
@@ -166,16 +196,22 @@ class _Serving:
                 tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
                 ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
                 tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            self.be.recommend_topk(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
-                                   top_val=tv, top_idx=ti, top_cnt=tc, **items)
+            if allow is None:
+                self.be.recommend_topk(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
+                                       top_val=tv, top_idx=ti, top_cnt=tc, **items)
+            else:
+                self.be.recommend_topk_masked(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                                              allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
             if not on_device:
                 out_items[b0: b0 + nb] = ti.cpu().numpy()
                 out_scores[b0: b0 + nb] = tv.cpu().numpy()
         return (top_val, top_idx) if on_device else (out_items, out_scores)
 
-    def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, Z):
+    def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, Z,
+                     allow: Optional[torch.Tensor] = None):
         """als_rank_count over the batch rows of the prefix sum `t_ptr` (device; `t_ptr_h` its host copy) in
-        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows` as in `_topk_chunks`.
+        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows` and `allow` as in
+        `_topk_chunks` (als_rank_count_masked).
         Returns device (above int32 [P], n_cand int32 [rows], score fp32 [P])."""
         B, P = t_ptr_h.size - 1, q_items.numel()
         above = torch.empty(P, dtype=torch.int32, device=self.dev)
@@ -185,10 +221,13 @@ class _Serving:
             nb = min(self.REC_BATCH, B - b0)
             users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
             t0, t1 = int(t_ptr_h[b0]), int(t_ptr_h[b0 + nb])
-            self.be.rank_count(U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users,
-                               q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
-                               t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb],
-                               **self._item_side(Z))
+            kw = dict(U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users,
+                      q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
+                      t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb], **self._item_side(Z))
+            if allow is None:
+                self.be.rank_count(**kw)
+            else:
+                self.be.rank_count_masked(allow=allow, **kw)
         return above, ncand, score
 
     def _group_by_user(self, us: torch.Tensor):
@@ -226,11 +265,13 @@ class _Serving:
         return out
 
     # ----------------------------------------------------- users of the fit
-    def recommend(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool):
+    def recommend(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool, filters=None):
         """Top-N items of the users in `users_t` (int32, device): (items int64 [B, N], scores float64 [B, N]),
-        unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit."""
+        unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit.
+        `filters`: here and below the validated (items, filter_items) pair of the call, or None."""
         Z = self._compose_for(features)
-        return self._topk_chunks(users_t.numel(), N, self._fitted_rows(users_t, exclude_seen), self._item_side(Z))
+        return self._topk_chunks(users_t.numel(), N, self._fitted_rows(users_t, exclude_seen), self._item_side(Z),
+                                 allow=self.allow_bitmap(filters, self.n))
 
     def _rank_outputs(self, above, ncand_rows, counts, score, inv=None):
         rank = above.to(torch.int64)
@@ -239,14 +280,14 @@ class _Serving:
             rank, cand, score = rank[inv], cand[inv], score[inv]
         return rank.cpu().numpy(), cand.cpu().numpy(), score.cpu().numpy()
 
-    def rank_of(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool):
+    def rank_of(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool, filters=None):
         """Ranks of the pairs (us[p], is_[p]) (int32, device): the pairs are grouped by user on the device, every
         user of a REC_BATCH chunk is scored once (als_rank_count), and the outputs go back to the pairs' order:
         (rank int64 [P], n_candidates int64 [P], scores float32 [P]).  Z and the seen items as in `recommend`."""
         Z = self._compose_for(features)
         order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
         above, ncand, score = self._rank_chunks(self._fitted_rows(uniq, exclude_seen), ptr, ptr_h,
-                                                is_[order].contiguous(), Z)
+                                                is_[order].contiguous(), Z, self.allow_bitmap(filters, self.n))
         return self._rank_outputs(above, ncand, counts, score, inv)
 
     def explain(self, us: torch.Tensor, is_: torch.Tensor, M: int, features, n_sweeps: int, largest: bool):
@@ -301,21 +342,24 @@ class _Serving:
         U, b, _, _ = self._fold_in_dev(indptr, indices, vals, self._compose_for(features), n_sweeps)
         return U, b
 
-    def recommend_new(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool):
+    def recommend_new(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
+                      filters=None):
         """Fold in, then als_recommend_topk on the folded table in REC_BATCH chunks: (items int64 [B, N], scores
         float64 [B, N])."""
         Z = self._compose_for(features)
         rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
-        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z))
+        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z),
+                                 allow=self.allow_bitmap(filters, self.n))
 
     def rank_of_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, features, n_sweeps: int,
-                    exclude_seen: bool):
+                    exclude_seen: bool, filters=None):
         """Fold in, then als_rank_count on the folded table (as `recommend_new` composes it) for the targets
         titems[tptr[b]:tptr[b + 1]], in REC_BATCH chunks."""
         Z = self._compose_for(features)
         rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
         tptr_d = torch.from_numpy(tptr).to(self.dev)
-        above, ncand, score = self._rank_chunks(rows, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z)
+        above, ncand, score = self._rank_chunks(rows, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z,
+                                                self.allow_bitmap(filters, self.n))
         return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
 
     def explain_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, M: int, features,
@@ -437,11 +481,11 @@ class _Serving:
         return out
 
     def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
-                             folded: "FoldedItems"):
+                             folded: "FoldedItems", filters=None):
         """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
         concatenated Z / b_i tables; the batch's user rows are gathered (batch row r = user users_t[r]) and their
         seen lists are the training row followed by the folded items they rated - ascending, as the new ids come
-        last."""
+        last.  The bitmap of `filters` spans the n + B ids of the concatenated table."""
         Z_fit = self._compose_for(features)
         Z_new, b_new = self._folded_dev(folded)
         side = dict(k=self.k, ld=self.ld, n=self.n + folded.n_items, Z=torch.cat([Z_fit, Z_new]),
@@ -460,7 +504,7 @@ class _Serving:
             seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d) if exclude_seen else (None, None)
             return (torch.arange(nb, dtype=torch.int32, device=self.dev), self.U.index_select(0, us),
                     self.b_u.index_select(0, us), seen_ptr, seen_idx)
-        return self._topk_chunks(users_t.numel(), N, rows, side)
+        return self._topk_chunks(users_t.numel(), N, rows, side, allow=self.allow_bitmap(filters, side["n"]))
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items

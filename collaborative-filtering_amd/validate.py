@@ -1,10 +1,10 @@
 """Input checks of the `ALS` facade (als.py), as plain functions: everything a public method verifies about its
-arguments before any device work - fitted-ness, features, list lengths, id arrays, `targets`, `n_sweeps`, and the
-host CSR forms of new users' / new items' ratings and graph rows.  Exception types and messages are part of the
-public behaviour (the reference's where it has one: scripts/als.py:554-565)."""
+arguments before any device work - fitted-ness, features, list lengths, id arrays, `targets`, `n_sweeps`, the item
+allow / block lists, and the host CSR forms of new users' / new items' ratings and graph rows.  Exception types and
+messages are part of the public behaviour (the reference's where it has one: scripts/als.py:554-565)."""
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -96,6 +96,54 @@ def target_lists(targets, B: int, n: int):
     if tptr[0] != 0 or tptr[-1] != ti.size or (np.diff(tptr) < 0).any():
         raise ValueError("targets indptr must start at 0, be non-decreasing and end at len(items)")
     return tptr, ti.astype(np.int64)
+
+
+def item_filter(x, n_total: int, name: str) -> Optional[np.ndarray]:
+    """One of `items=` / `filter_items=` (`name`) over a catalogue of n_total items -> None (not given), a bool mask
+    [n_total], or int64 item ids in [0, n_total) (any order, duplicates kept).  Raises ValueError otherwise."""
+    if x is None:
+        return None
+    a = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be a 1-D array of integer item ids or a boolean mask of length {n_total}")
+    if a.dtype == np.bool_:
+        if a.size != n_total:
+            raise ValueError(f"{name} as a boolean mask has {a.size} entries. Expected number of items: {n_total}.")
+        return a
+    if a.size == 0:                                          # an empty list, whatever dtype numpy gave it
+        return np.empty(0, dtype=np.int64)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must hold integer item ids or booleans, got dtype {a.dtype}")
+    if a.min() < 0 or a.max() >= n_total:
+        raise ValueError(f"{name}: item ids must lie in [0, {n_total})")
+    return a.astype(np.int64)
+
+
+def item_filters(items, filter_items, n_total: int):
+    """The allow-list `items=` and the block-list `filter_items=` of a serving call: None when neither is given
+    (the call then takes the unfiltered path), else the pair of `item_filter` results."""
+    if items is None and filter_items is None:
+        return None
+    return item_filter(items, n_total, "items"), item_filter(filter_items, n_total, "filter_items")
+
+
+def allowed_mask(filters, n_total: int) -> np.ndarray:
+    """bool [n_total] of an `item_filters` pair: `items` (every item when None) minus `filter_items`.  The host
+    definition of what serving._Serving.allow_bitmap packs on the device."""
+    allow, block = filters
+    mask = np.ones(n_total, dtype=bool)
+    if allow is not None:
+        if allow.dtype == np.bool_:
+            mask = allow.copy()
+        else:
+            mask[:] = False
+            mask[allow] = True
+    if block is not None:
+        if block.dtype == np.bool_:
+            mask &= ~block
+        else:
+            mask[block] = False
+    return mask
 
 
 def folded_items(model, folded) -> None:

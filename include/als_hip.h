@@ -410,6 +410,21 @@ int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int6
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Top-N recommendation over a restricted catalogue: als_recommend_topk with the items limited to an allow bitmap.
+ *   allow: device bitmap of ceil(n / 32) words; item i is allowed iff bit (i & 31) of word (i >> 5) is set; bits at
+ *   positions >= n are ignored.  A disallowed item is never returned, exactly like a seen one; everything else -
+ *   scores, order, ties, unused slots, top_cnt, nslices, the workspace (als_recommend_workspace_bytes) - is
+ *   als_recommend_topk's, and the result does not depend on the slice count.  An all-zero bitmap gives empty lists
+ *   (top_cnt 0).  allow == NULL allows every item: the call is then als_recommend_topk (which forwards here).
+ * The items are walked in chunks of 32; a chunk whose word is 0 is neither loaded nor scored, only scanned past.
+ * ------------------------------------------------------------------------- */
+int als_recommend_topk_masked(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                              const float* Z, const float* b_u, const float* b_i, const double* mu,
+                              const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, int topn,
+                              int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Exact full-catalogue ranks (evaluation).  Model arguments as als_recommend_topk: score(u, j) is bitwise the fp32
  * value als_predict_dense writes; seen_ptr / seen_idx a CSR by USER ID, ascending (both NULL = exclude nothing).
  * For user u the candidates are C(u) = { j < n : j not in u's seen row, score(u, j) is not NaN }.
@@ -434,6 +449,22 @@ int als_rank_count(int k, int ld, int64_t n, const float* U, const float* Z, con
                    const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items, int64_t nt, int nslices,
                    float* t_score, int32_t* above, int32_t* n_cand, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Exact ranks within a restricted catalogue: als_rank_count with the candidates limited to an allow bitmap (the
+ * bitmap of als_recommend_topk_masked: ceil(n / 32) words, bit (i & 31) of word (i >> 5), bits >= n ignored):
+ *   C(u) = { j < n : j allowed, j not in u's seen row, score(u, j) is not NaN };
+ *   above[p] and n_cand[b] count within this C(u); t_score[p] is unchanged.  As for a seen target, above[p] is
+ *   defined whether or not t itself is allowed (the position t would take), so an item that
+ *   als_recommend_topk_masked returns at position j has above == j under the same bitmap and seen rows.
+ * allow == NULL allows every item: the call is then als_rank_count (which forwards here).  Workspace:
+ *   als_rank_count_workspace_bytes.
+ * ------------------------------------------------------------------------- */
+int als_rank_count_masked(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
+                          const float* b_i, const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
+                          const uint32_t* allow, int64_t nq, const int32_t* q_users, const int64_t* q_ptr,
+                          const int32_t* q_items, int64_t nt, int nslices, float* t_score, int32_t* above,
+                          int32_t* n_cand, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user

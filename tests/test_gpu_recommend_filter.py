@@ -1,0 +1,323 @@
+"""Item allow / block lists on the GPU: als_recommend_topk_masked / als_rank_count_masked (csrc/recommend.hip,
+csrc/rank_eval.hip) and `items=` / `filter_items=` of ALS.recommend*, rank_of*.
+
+The oracle is exact, as in test_gpu_recommend.py: every score is bitwise the fp32 value als_predict_dense writes, so
+the expected lists are the predict_dense rows with the seen AND the disallowed columns removed, sorted by (score
+descending, item ascending); ranks are counts over the same rows.  Everything is compared with ==."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from tests.synth import make_ratings
+from tests.test_gpu_recommend import _assert_same, _dense, _env, _factors, _run, _seen_csr
+
+SLICES = (1, 2, 7, 64)
+
+
+def _masks(n, seed):
+    """name -> bool [n]: what the issue lists - dense, sparse (scattered and one contiguous run), one item, none."""
+    rng = np.random.default_rng(seed)
+    run = np.zeros(n, bool)
+    w = max(n // 100, 1)
+    a = int(rng.integers(0, n - w + 1))
+    run[a: a + w] = True
+    one = np.zeros(n, bool)
+    one[int(rng.integers(0, n))] = True
+    last = np.zeros(n, bool)
+    last[n - 1] = True                                                     # the last bit of the last word
+    return {"dense": rng.random(n) < 0.9, "scattered": rng.random(n) < 0.01, "run": run, "one": one, "last": last,
+            "empty": np.zeros(n, bool), "all": np.ones(n, bool)}
+
+
+def _bitmap(torch, mask, dev):
+    """The C ABI's bitmap, packed here with numpy: item i = bit i & 31 of word i >> 5 (little-endian bit order)."""
+    bits = np.zeros((mask.size + 31) // 32 * 32, np.uint8)
+    bits[: mask.size] = mask
+    words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+    return torch.from_numpy(words.view(np.int32).copy()).to(dev)
+
+
+def _expected_masked(dense_rows, seen_rows, ok, N):
+    B, n = dense_rows.shape
+    tv = np.full((B, N), -np.inf, np.float32)
+    ti = np.full((B, N), -1, np.int32)
+    tc = np.zeros(B, np.int32)
+    for b in range(B):
+        keep = ok.copy()
+        keep[seen_rows[b]] = False
+        items = np.nonzero(keep)[0]
+        sc = dense_rows[b, items]
+        order = np.lexsort((items, -sc))[:N]
+        tv[b, : order.size] = sc[order]
+        ti[b, : order.size] = items[order]
+        tc[b] = order.size
+    return tv, ti, tc
+
+
+def _run_masked(torch, be, f, users, n, seen_ptr, seen_idx, allow, N, dev):
+    us = torch.from_numpy(np.asarray(users, np.int32)).to(dev)
+    B = us.numel()
+    tv = torch.empty(B, N, dtype=torch.float32, device=dev)
+    ti = torch.empty(B, N, dtype=torch.int32, device=dev)
+    tc = torch.empty(B, dtype=torch.int32, device=dev)
+    sp = None if seen_ptr is None else torch.from_numpy(seen_ptr).to(dev)
+    si = None if seen_idx is None else torch.from_numpy(seen_idx).to(dev)
+    be.recommend_topk_masked(k=f["k"], ld=f["ld"], users=us, n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"],
+                             mu=f["mu"], seen_ptr=sp, seen_idx=si, allow=allow, topn=N, top_val=tv, top_idx=ti,
+                             top_cnt=tc)
+    return tv.cpu().numpy(), ti.cpu().numpy(), tc.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ kernel level
+@pytest.mark.parametrize("k,n", [(16, 1003), (64, 4099), (160, 2051)])     # n never a multiple of 32
+def test_masked_kernel_equals_masked_dense_sort(k, n, monkeypatch):
+    torch, layout, be, dev = _env()
+    m = 40
+    f = _factors(torch, layout, dev, m, n, k, seed=10 * k + n)
+    ptr, idx, rows = _seen_csr(m, n, seed=k + n)
+    dense = _dense(torch, be, f, m, n, dev)
+    users = np.concatenate([np.arange(m), [3, 1, 3, 0]])[::-1].copy()
+    seen = [rows[u] for u in users]
+    for name, ok in _masks(n, seed=n).items():
+        allow = _bitmap(torch, ok, dev)
+        for N in (10, 128):
+            exp = _expected_masked(dense[users], seen, ok, N)
+            for s in SLICES:
+                monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
+                got = _run_masked(torch, be, f, users, n, ptr, idx, allow, N, dev)
+                for g, e in zip(got, exp):
+                    assert (g == e).all(), (name, N, s, np.argwhere(g != e)[:5])
+            monkeypatch.delenv("ALS_RECOMMEND_SLICES")
+            _assert_same(_run_masked(torch, be, f, users, n, ptr, idx, allow, N, dev), exp)      # automatic
+        if name == "empty":
+            assert (exp[2] == 0).all()
+        # no seen rows at all
+        _assert_same(_run_masked(torch, be, f, users, n, None, None, allow, 10, dev),
+                     _expected_masked(dense[users], [np.empty(0, np.int64)] * users.size, ok, 10))
+
+
+@pytest.mark.parametrize("B,N", [(1, 10), (3000, 10), (3000, 128)])
+def test_all_ones_mask_equals_the_unmasked_call_bitwise(B, N, monkeypatch):
+    torch, layout, be, dev = _env()
+    m, n, k = 3000, 5003, 64
+    f = _factors(torch, layout, dev, m, n, k, seed=B + N)
+    ptr, idx, rows = _seen_csr(m, n, seed=B)
+    users = np.random.default_rng(B).permutation(m)[:B]
+    ones = _bitmap(torch, np.ones(n, bool), dev)
+    ones.view(torch.int32)[-1] = -1                                        # bits at positions >= n are ignored
+    for s in (0, 1, 7):
+        monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
+        _assert_same(_run_masked(torch, be, f, users, n, ptr, idx, ones, N, dev),
+                     _run(torch, be, f, users, n, ptr, idx, N, dev))
+
+
+def _rank_run(torch, be, f, n, seen, q_users, q_ptr, q_items, dev, allow=None):
+    t = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(dev)
+    nq, nt = len(q_users), len(q_items)
+    score = torch.empty(nt, dtype=torch.float32, device=dev)
+    above = torch.empty(nt, dtype=torch.int32, device=dev)
+    ncand = torch.empty(nq, dtype=torch.int32, device=dev)
+    kw = dict(k=f["k"], ld=f["ld"], n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"], mu=f["mu"],
+              seen_ptr=None if seen is None else t(seen[0], np.int64),
+              seen_idx=None if seen is None else t(seen[1], np.int32), q_users=t(q_users, np.int32),
+              q_ptr=t(q_ptr, np.int64), q_items=t(q_items, np.int32), t_score=score, above=above, n_cand=ncand)
+    if allow is None:
+        be.rank_count(**kw)
+    else:
+        be.rank_count_masked(allow=allow, **kw)
+    return above.cpu().numpy(), ncand.cpu().numpy(), score.cpu().numpy()
+
+
+@pytest.mark.parametrize("k,n", [(16, 1003), (64, 4099), (160, 2051)])
+def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
+    torch, layout, be, dev = _env()
+    m = 40
+    f = _factors(torch, layout, dev, m, n, k, seed=7 * k + n)
+    ptr, idx, rows = _seen_csr(m, n, seed=k + n + 1)
+    dense = _dense(torch, be, f, m, n, dev)
+    rng = np.random.default_rng(k)
+    q_users = np.concatenate([np.arange(m), [5, 5]])
+    counts = rng.integers(0, 6, q_users.size)
+    counts[7] = 40                                                         # more than one pass of 16 targets
+    q_ptr = np.concatenate([[0], np.cumsum(counts)])
+    q_items = rng.integers(0, n, q_ptr[-1])
+    j = np.arange(n)
+    for name, ok in _masks(n, seed=n + 1).items():
+        allow = _bitmap(torch, ok, dev)
+        exp_above, exp_cand = np.zeros(q_items.size, np.int32), np.zeros(q_users.size, np.int32)
+        for b, u in enumerate(q_users):
+            cand = ok.copy()
+            cand[rows[u]] = False
+            exp_cand[b] = cand.sum()
+            for p in range(q_ptr[b], q_ptr[b + 1]):
+                t = q_items[p]
+                exp_above[p] = (cand & ((dense[u] > dense[u, t]) | ((dense[u] == dense[u, t]) & (j < t)))).sum()
+        for s in SLICES + (0,):
+            monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
+            above, ncand, score = _rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev, allow)
+            assert (above == exp_above).all(), (name, s)
+            assert (ncand == exp_cand).all(), (name, s)
+            assert (score == dense[np.repeat(q_users, counts), q_items]).all()
+        if name == "all":                                                  # all ones == the unmasked call
+            monkeypatch.setenv("ALS_RECOMMEND_SLICES", "0")
+            for g, e in zip(_rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev),
+                            (above, ncand, score)):
+                assert (g == e).all()
+
+
+# ------------------------------------------------------------------------------------------------ model level
+M, N_ITEMS, K = 300, 1003, 24
+
+
+@pytest.fixture(scope="module")
+def fitted():
+    _env()
+    from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig
+    r, c, v = make_ratings(M, N_ITEMS, 12000, seed=5, empty_users=(4,))
+    cfg = ALSConfig(core=CoreConfig(n_factors=K, n_iters=3, lambda_u=3.0, lambda_v=3.0),
+                    biases=BiasesConfig(lambda_bu=2.0, lambda_bi=2.0))
+    model = ALS(cfg, device="cuda:0").fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
+    seen = [np.unique(c[r == u]) for u in range(M)]
+    return model, seen, model.predict().astype(np.float32)
+
+
+def _allowed(kw, n):
+    """bool [n]: `items` (ids or mask; all when absent) minus `filter_items`, restated here."""
+    def as_mask(x):
+        x = np.asarray(x)
+        if x.dtype == np.bool_:
+            return x.copy()
+        out = np.zeros(n, bool)
+        out[x.astype(np.int64)] = True
+        return out
+    ok = as_mask(kw["items"]) if "items" in kw else np.ones(n, bool)
+    return ok & ~as_mask(kw["filter_items"]) if "filter_items" in kw else ok
+
+
+def _filter_cases(n, seed):
+    rng = np.random.default_rng(seed)
+    allow = rng.permutation(n)[: n // 3]
+    block = rng.random(n) < 0.25
+    return [dict(items=allow), dict(items=np.isin(np.arange(n), allow)), dict(filter_items=np.nonzero(block)[0]),
+            dict(filter_items=block), dict(items=np.concatenate([allow, allow[:9]]), filter_items=block),
+            dict(items=np.arange(n // 2, n // 2 + 11)), dict(items=[n - 1]), dict(items=[])]
+
+
+def test_model_recommend_with_filters_equals_the_masked_oracle(fitted, monkeypatch):
+    model, seen, P = fitted
+    monkeypatch.setattr(model._eng, "REC_BATCH", 128, raising=False)      # 300 users: three chunks
+    for kw in _filter_cases(N_ITEMS, 1):
+        ok = _allowed(kw, N_ITEMS)
+        for N in (10, 128):
+            items, scores = model.recommend(None, N, **kw)
+            tv, ti, _ = _expected_masked(P, seen, ok, N)
+            assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
+        items, scores = model.recommend([7, 0, 7], 10, exclude_seen=False, **kw)
+        tv, ti, _ = _expected_masked(P[[7, 0, 7]], [np.empty(0, np.int64)] * 3, ok, 10)
+        assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
+    items, scores = model.recommend([1, 2], 5, items=[])
+    assert (items == -1).all() and np.isneginf(scores).all()
+
+
+def test_all_items_allowed_equals_the_unfiltered_calls_bitwise(fitted):
+    model, seen, P = fitted
+    base = model.recommend(None, 128)
+    for kw in (dict(items=np.arange(N_ITEMS)), dict(items=np.ones(N_ITEMS, bool)),
+               dict(filter_items=np.zeros(N_ITEMS, bool)), dict(filter_items=[])):
+        got = model.recommend(None, 128, **kw)
+        assert (got[0] == base[0]).all() and (got[1] == base[1]).all()
+    rng = np.random.default_rng(0)
+    us, ts = rng.integers(0, M, 500), rng.integers(0, N_ITEMS, 500)
+    base = model.rank_of(us, ts)
+    for kw in (dict(allow_items=np.arange(N_ITEMS)), dict(allow_items=np.ones(N_ITEMS, bool)),
+               dict(filter_items=np.zeros(N_ITEMS, bool))):
+        for g, e in zip(model.rank_of(us, ts, **kw), base):
+            assert (g == e).all()
+
+
+def test_block_list_equals_the_unfiltered_list_with_the_blocked_items_removed(fitted):
+    model, seen, P = fitted
+    full_i, full_s = model.recommend(None, 128)
+    block = np.random.default_rng(3).random(N_ITEMS) < 0.5
+    survive = (full_i >= 0) & ~block[np.maximum(full_i, 0)]
+    assert (survive.sum(axis=1) >= 10).all()                               # the precondition, for every row
+    items, scores = model.recommend(None, 10, filter_items=block)
+    for u in range(M):
+        assert (items[u] == full_i[u][survive[u]][:10]).all()
+        assert (scores[u] == full_s[u][survive[u]][:10]).all()
+
+
+def test_rank_of_is_consistent_with_filtered_recommend(fitted):
+    model, seen, P = fitted
+    j = np.arange(N_ITEMS)
+    for kw in _filter_cases(N_ITEMS, 2)[:6]:
+        rkw = {("allow_items" if a == "items" else a): v for a, v in kw.items()}
+        ok = _allowed(kw, N_ITEMS)
+        items, scores = model.recommend(None, 20, **kw)
+        valid = items >= 0
+        us = np.repeat(np.arange(M), 20).reshape(M, 20)[valid]
+        rank, cand, sc = model.rank_of(us, items[valid], **rkw)
+        assert (rank == np.tile(np.arange(20), (M, 1))[valid]).all()      # position j <-> rank j
+        assert (sc.astype(np.float64) == scores[valid]).all()
+        ncand = np.array([np.setdiff1d(np.nonzero(ok)[0], seen[u]).size for u in range(M)])
+        assert (cand == ncand[us]).all()
+        # targets that are themselves not allowed (or seen): the position they would take
+        rng = np.random.default_rng(4)
+        tu, tt = rng.integers(0, M, 400), rng.integers(0, N_ITEMS, 400)
+        assert (~ok[tt]).sum() > 50
+        rank, cand, _ = model.rank_of(tu, tt, **rkw)
+        for p, (u, t) in enumerate(zip(tu, tt)):
+            cset = ok.copy()
+            cset[seen[u]] = False
+            assert rank[p] == (cset & ((P[u] > P[u, t]) | ((P[u] == P[u, t]) & (j < t)))).sum()
+            assert cand[p] == cset.sum()
+
+
+def test_new_user_entry_points_with_filters(fitted):
+    model, seen, P = fitted
+    rng = np.random.default_rng(8)
+    B = 50
+    R_new = np.full((B, N_ITEMS), np.nan)
+    for b in range(B - 1):                                                 # the last row: no ratings
+        R_new[b, rng.permutation(N_ITEMS)[:30]] = rng.integers(1, 6, 30)
+    full_i, full_s = model.recommend_new(R_new, 128)
+    block = rng.random(N_ITEMS) < 0.5
+    survive = (full_i >= 0) & ~block[np.maximum(full_i, 0)]
+    assert (survive.sum(axis=1) >= 10).all()
+    for kw in (dict(filter_items=block), dict(items=~block), dict(items=np.nonzero(~block)[0])):
+        items, scores = model.recommend_new(R_new, 10, **kw)
+        for b in range(B):
+            assert (items[b] == full_i[b][survive[b]][:10]).all() and (scores[b] == full_s[b][survive[b]][:10]).all()
+        tptr = np.arange(0, 10 * B + 1, 10)
+        rank, cand, sc = model.rank_of_new(R_new, (tptr, items.ravel()), **kw)
+        assert (rank.reshape(B, 10) == np.arange(10)).all()
+        assert (sc.astype(np.float64).reshape(B, 10) == scores).all()
+        assert (cand.reshape(B, 10) == ((~block)[None, :] & np.isnan(R_new)).sum(axis=1)[:, None]).all()
+
+
+def test_recommend_with_folded_items_and_a_mask_over_the_joint_catalogue(fitted):
+    model, seen, P = fitted
+    rng = np.random.default_rng(9)
+    B = 45
+    C_new = np.full((B, M), np.nan)
+    for b in range(B):
+        C_new[b, rng.permutation(M)[:25]] = rng.integers(1, 6, 25)
+    folded = model.fold_in_items(C_new)
+    nt = N_ITEMS + B
+    Pj = np.concatenate([P, model.predict_new_items(folded).astype(np.float32)], axis=1)
+    seen_j = [np.concatenate([seen[u], N_ITEMS + np.nonzero(~np.isnan(C_new[:, u]))[0]]) for u in range(M)]
+    base = model.recommend(None, 10, new_items=folded)
+    tv, ti, _ = _expected_masked(Pj, seen_j, np.ones(nt, bool), 10)
+    assert (base[0] == ti).all() and (base[1] == tv.astype(np.float64)).all()
+    mask = rng.random(nt) < 0.3
+    mask[N_ITEMS: N_ITEMS + 20] = True                                     # folded ids inside ...
+    mask[N_ITEMS + 20:] = False                                            # ... and outside the mask
+    for kw in (dict(items=mask), dict(items=np.nonzero(mask)[0]), dict(filter_items=~mask),
+               dict(items=np.arange(N_ITEMS, nt)), dict(filter_items=np.arange(N_ITEMS, nt))):
+        ok = _allowed(kw, nt)
+        items, scores = model.recommend(None, 10, new_items=folded, **kw)
+        tv, ti, _ = _expected_masked(Pj, seen_j, ok, 10)
+        assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
+    items, _ = model.recommend(None, 10, new_items=folded, items=mask)
+    assert (items >= N_ITEMS).any() and not (items >= N_ITEMS + 20).any()
