@@ -307,14 +307,18 @@ __device__ __forceinline__ void lower_block(int q, int& I, int& J) {
 // items: the tile's contributing items (w != 0) are compacted, in item order, into an LDS list, and the
 // list is consumed four items at a time so that 4 NACC independent loads are in flight per thread (a
 // serial `if (w == 0) continue` loop pays one dependent-load latency per item).  Fixed summation order.
+// T = float: w_i is the fp32 product (that mode's precision).  T = double (als_w_params::f64): the list keeps both
+// fp32 factors and w_i is their exact fp64 product, so that A is assembled as consistently as B; which items
+// contribute is decided by the fp32 product in both.
 template <int KB, typename T>
 __global__ __launch_bounds__(256)
 void k_w_accumulate(int64_t i0, int64_t i1, int nchunks, const T* __restrict__ gram, int D, int foff, int d,
                     const float* __restrict__ X, const T* __restrict__ Hf, double* __restrict__ partA,
                     double* __restrict__ partB) {
     constexpr int KP = KCfg<KB>::KP, NACC = KCfg<KB>::NACC;
+    constexpr bool W64 = sizeof(T) == sizeof(double);
     __shared__ int l_item[256];
-    __shared__ float l_w[256], l_xa[256];
+    __shared__ float l_w[256], l_xa[256];         // l_w: x_ia x_ia' (float) / x_ia' (double)
     __shared__ int l_cnt[4];
     int pair = blockIdx.x, a = 0;
     while (pair >= d - a) { pair -= d - a; ++a; }
@@ -338,10 +342,11 @@ void k_w_accumulate(int64_t i0, int64_t i1, int nchunks, const T* __restrict__ g
     const bool want_b = (a == a2) && t < KP;
     for (int64_t tile = cb; tile < ce; tile += 256) {
         const int64_t i = tile + t;
-        float xa = 0.f, w = 0.f;
+        float xa = 0.f, xa2 = 0.f, w = 0.f;
         if (i < ce) {
             xa = X[i * D + foff + a];
-            w = xa * X[i * D + foff + a2];
+            xa2 = X[i * D + foff + a2];
+            w = xa * xa2;
         }
         const unsigned long long m = __ballot(w != 0.f);
         if (lane == 0) l_cnt[wv] = __popcll(m);
@@ -352,7 +357,7 @@ void k_w_accumulate(int64_t i0, int64_t i1, int nchunks, const T* __restrict__ g
         if (w != 0.f) {
             const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
             l_item[pos] = (int)(i - tile);
-            l_w[pos] = w;
+            l_w[pos] = W64 ? xa2 : w;
             l_xa[pos] = xa;
         }
         __syncthreads();
@@ -369,7 +374,7 @@ void k_w_accumulate(int64_t i0, int64_t i1, int nchunks, const T* __restrict__ g
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const double w64 = (double)l_w[n + u];
+                const double w64 = W64 ? (double)l_xa[n + u] * (double)l_w[n + u] : (double)l_w[n + u];
 #pragma unroll
                 for (int q = 0; q < NACC; ++q) acc[q] += w64 * (double)g[u][q];
                 accb += (double)l_xa[n + u] * (double)h[u];
@@ -378,7 +383,7 @@ void k_w_accumulate(int64_t i0, int64_t i1, int nchunks, const T* __restrict__ g
         for (; n < total; ++n) {
             const int64_t it = tile + l_item[n];
             const T* G = gram + it * KP * KP;
-            const double w64 = (double)l_w[n];
+            const double w64 = W64 ? (double)l_xa[n] * (double)l_w[n] : (double)l_w[n];
 #pragma unroll
             for (int q = 0; q < NACC; ++q) acc[q] += w64 * (double)G[offT[q]];
             if (want_b) accb += (double)l_xa[n] * (double)Hf[it * KP + t];

@@ -1,6 +1,8 @@
 """T3 (GPU): each C-ABI entry point against numpy on random CSR, incl. degenerate
 rows (nnz = 1, < k, >> k, > ALS_SPLIT_CHUNK so the split/finish path runs) and
-k in {1, 16, 32, 50, 64, 128}.  Calls go through ctypes -> libals_hip.so."""
+k in {1, 16, 32, 50, 64, 128}.  Calls go through ctypes -> libals_hip.so.  The W-step entry points
+(als_w_normal_equations, als_item_stats, als_item_stats_f64) have their own file, tests/test_gpu_w_step.py, with
+its reference in tests/w_step_ref.py (validated without a device by tests/test_w_step_ref_cpu.py)."""
 import os
 
 import numpy as np
