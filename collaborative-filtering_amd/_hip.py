@@ -23,7 +23,7 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
            "als_recommend_workspace_bytes", "als_recommend_topk", "als_rank_count_workspace_bytes", "als_rank_count",
            "als_recommend_topk_masked", "als_rank_count_masked",
-           "als_fold_in", "als_fold_in_items", "als_explain")
+           "als_fold_in", "als_fold_in_items", "als_explain", "als_mmr_rerank", "als_list_diversity")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -171,6 +171,9 @@ def load():
     lib.als_fold_in.argtypes = [C.POINTER(FoldInParams), _vp]
     lib.als_fold_in_items.argtypes = [C.POINTER(FoldInItemsParams), _vp]
     lib.als_explain.argtypes = [C.POINTER(ExplainParams), _vp]
+    lib.als_mmr_rerank.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, C.c_int, _vp, _vp, _f32, C.c_int, _vp, _vp, _vp,
+                                   _vp, _vp]
+    lib.als_list_diversity.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, C.c_int, _vp, _vp, _vp]
     lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]

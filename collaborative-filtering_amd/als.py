@@ -496,6 +496,86 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen, filters)
 
+    # ------------------------------------------------------------ diversity
+    def recommend_diverse(self, users=None, N: int = 10, *, diversity: float = 0.3, pool: Optional[int] = None,
+                          features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                          new_items: Optional[FoldedItems] = None, items=None, filter_items=None):
+        """Diversified top-N: greedy maximal marginal relevance (MMR) over each user's `pool` best items.  Returns
+        (items int64 [B, N], scores float64 [B, N]) in pick order, unused slots -1 / -inf.
+
+        The pool of a user is `recommend(users, pool, ...)` with the same `features`, `exclude_seen`, `new_items`,
+        `items` and `filter_items` - M <= pool entries with scores s, in that call's order.  With lambda =
+        `diversity` in [0, 1], in fp32 against the Z the pool was scored with:
+
+          sim(j, l) = z_j.z_l / sqrt(|z_j|^2 |z_l|^2), 0 when either norm is 0 (one value per unordered pair);
+          rel_j     = (s_j - s_min) / (s_max - s_min) over the pool, every rel_j = 0 when s_max - s_min is 0 or not
+                      finite;
+          step t = 0 .. N-1 picks, among the pool entries not yet chosen, the one maximising
+                      (1 - lambda) rel_j - lambda max_{l chosen} sim(j, l)    (the maximum over no item is 0),
+                      ties to the lower pool position.
+
+        The scores returned are the pool's (copied, `recommend`'s contract holds for them); min(N, M) slots are
+        filled.  `diversity=0` returns `recommend(users, N, ...)` bit for bit; with `diversity=1` the first pick is
+        still the user's best item.  `pool`: None = min(128, 4 N), else N <= pool <= 128.  The pool never leaves the
+        device: one kernel forms its Gram on the matrix cores and runs the greedy selection (als_mmr_rerank)."""
+        out = self._recommend_diverse(users, N, diversity, pool, features, exclude_seen, new_items, items,
+                                      filter_items, False)
+        return out[0], out[1]
+
+    def _recommend_diverse(self, users, N, diversity, pool, features, exclude_seen, new_items, items, filter_items,
+                           with_ild: bool):
+        """`recommend_diverse` returning (items, scores, ild float64 [B] or None): the intra-list diversity of every
+        returned list comes from the same kernel (cv.diversity_at_k reads it)."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        N = validate.top_count(N, "N")
+        lam, pool = validate.diversity_args(diversity, N, pool)
+        u = validate.user_ids(users, self.U.shape[0])
+        filters = validate.item_filters(items, filter_items,
+                                        self.V.shape[0] + (new_items.n_items if new_items is not None else 0))
+        if u.size == 0:
+            return (np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64),
+                    np.empty(0, dtype=np.float64) if with_ild else None)
+        with _on(self._eng.dev):
+            return self._eng.recommend_diverse(self._dev_i32(u), N, pool, lam, features, exclude_seen, new_items,
+                                               filters, with_ild)
+
+    def recommend_new_diverse(self, R_new, N: int = 10, *, diversity: float = 0.3, pool: Optional[int] = None,
+                              features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                              exclude_seen: bool = True, items=None, filter_items=None):
+        """`recommend_diverse` for users outside the fit: the pool is `recommend_new(R_new, pool, ...)`; everything
+        else as there.  Returns (items int64 [B, N], scores float64 [B, N])."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        lam, pool = validate.diversity_args(diversity, N, pool)
+        T = validate.sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        filters = validate.item_filters(items, filter_items, self.V.shape[0])
+        if indptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_new_diverse(indptr, indices, vals, N, pool, lam, features, T, exclude_seen,
+                                                   filters)[:2]
+
+    def list_diversity(self, item_lists, *, features: Optional[Dict[str, np.ndarray]] = None,
+                       new_items: Optional[FoldedItems] = None) -> np.ndarray:
+        """Intra-list diversity of id lists: float64 [B], the mean over the unordered pairs of a list of
+        1 - sim(j, l) with `recommend_diverse`'s sim; NaN for a list of fewer than two items.
+
+        `item_lists`: an integer array [B, L <= 128]; a list ends at its first -1 (the padding of `recommend*`).
+        Ids are items of the fit, or of the joint catalogue with `new_items`; `features` decides Z as in `predict`.
+        On the lists `recommend_diverse` returns, the value is bitwise the one its kernel computes for them
+        (als_list_diversity)."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        lists = validate.item_lists(item_lists, self.V.shape[0] + (new_items.n_items if new_items is not None else 0))
+        if lists.shape[0] == 0:
+            return np.empty(0, dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.list_diversity(torch.from_numpy(lists).to(self._eng.dev), features, new_items)
+
     # ---------------------------------------------------------- evaluation
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
                 allow_items=None, filter_items=None):

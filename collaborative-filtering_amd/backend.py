@@ -386,3 +386,21 @@ class HipBackend:
         p.top_item, p.top_contrib, p.top_weight, p.top_cnt = _p(top_item), _p(top_contrib), _p(top_weight), _p(top_cnt)
         p.b_u_out, p.status = _p(b_u_out), _p(status)
         self._check(self.lib.als_explain(C.byref(p), self._stream()), "als_explain")
+
+    # -- K12 -------------------------------------------------------------------
+    def mmr_rerank(self, *, k, ld, n, Z, cand_val, cand_idx, lam, topn, top_val, top_idx, top_cnt, top_ild=None):
+        """Greedy MMR re-ranking of the pools cand_val fp32 / cand_idx int32 [B, pool] (the outputs of
+        `recommend_topk` with topn = pool) against Z: top_val / top_idx [B, topn], top_cnt [B], top_ild fp32 [B] or
+        None: als_mmr_rerank."""
+        B, pool = cand_idx.shape
+        assert cand_val.shape == (B, pool) and cand_val.is_contiguous() and cand_idx.is_contiguous()
+        self._check(self.lib.als_mmr_rerank(k, ld, B, n, _p(Z), pool, _p(cand_val), _p(cand_idx), float(lam), topn,
+                                            _p(top_val), _p(top_idx), _p(top_cnt), _p(top_ild), self._stream()),
+                    "als_mmr_rerank")
+
+    def list_diversity(self, *, k, ld, n, Z, idx, ild):
+        """ild fp32 [B] = intra-list diversity of the id lists idx int32 [B, L] (-1 padded): als_list_diversity."""
+        B, L = idx.shape
+        assert idx.is_contiguous()
+        self._check(self.lib.als_list_diversity(k, ld, B, n, _p(Z), L, _p(idx), _p(ild), self._stream()),
+                    "als_list_diversity")

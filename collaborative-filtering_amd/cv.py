@@ -155,23 +155,50 @@ def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: 
     `items` / `filter_items` (as `ALS.recommend`): the measures within the restricted catalogue - top(u) is taken
     among the allowed items, held-out pairs whose item is not allowed are left out of rel(u), and the result gains
     "filtered_out", their number (after `min_rating`)."""
-    rows = np.asarray(rows, dtype=np.int64).ravel()
-    cols = np.asarray(cols, dtype=np.int64).ravel()
-    if rows.shape != cols.shape:
-        raise ValueError("rows and cols must have the same length")
-    if min_rating is not None:
-        if vals is None:
-            raise ValueError("min_rating needs the held-out ratings (vals)")
-        keep = np.asarray(vals, dtype=np.float64).ravel() >= min_rating
-        rows, cols = rows[keep], cols[keep]
-    allowed, kw = _item_filter(model, cols, items, filter_items)
-    extra = {"filtered_out": int((~allowed).sum())} if kw else {}
-    rows, cols = rows[allowed], cols[allowed]
-    users, ub = np.unique(rows, return_inverse=True)
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
     if users.size == 0:
         return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan"), **extra}
     top, _ = model.recommend(users, K, features=features, **kw)
     return {**_ranking_metrics(top, ub, cols, model.V.shape[0], K), **extra}
+
+
+def diversity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, diversity: float = 0.0,
+                   pool: Optional[int] = None, min_rating: Optional[float] = None,
+                   features: Optional[Dict[str, np.ndarray]] = None, items=None, filter_items=None) -> Dict[str, Any]:
+    """Accuracy and beyond-accuracy measures of `model.recommend_diverse(users, K, diversity=diversity, pool=pool)`
+    on held-out (user, item) pairs: {"users", "recall@K", "ndcg@K", "ild@K", "coverage@K"}.
+
+    users, rel(u), recall@K and NDCG@K are `ranking_at_k`'s (same arguments, same held-out pairs left out); with
+    `diversity=0.0` the lists are `recommend`'s and the two values equal `ranking_at_k`'s exactly.
+      ild@K       mean, over the users whose list holds at least two items, of the list's intra-list diversity
+                  (`ALS.list_diversity`; NaN when there is no such user)
+      coverage@K  distinct items over all the lists / size of the allowed catalogue (n, or what `items` /
+                  `filter_items` leave of it; NaN when nothing is allowed)
+    With `items` / `filter_items` the result also holds "filtered_out" as in `ranking_at_k`."""
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
+    if users.size == 0:
+        nan = float("nan")
+        return {"users": 0, "recall@K": nan, "ndcg@K": nan, "ild@K": nan, "coverage@K": nan, **extra}
+    top, _, ild = model._recommend_diverse(users, K, diversity, pool, features, True, None, kw.get("items"),
+                                           kw.get("filter_items"), True)
+    n = model.V.shape[0]
+    n_allowed = int(validate.allowed_mask(validate.item_filters(items, filter_items, n), n).sum()) if kw else n
+    two = (top >= 0).sum(axis=1) >= 2
+    return {**_ranking_metrics(top, ub, cols, n, K),
+            "ild@K": float(np.mean(ild[two])) if two.any() else float("nan"),
+            "coverage@K": np.unique(top[top >= 0]).size / n_allowed if n_allowed else float("nan"), **extra}
+
+
+def _users_at_k(model, rows, cols, vals, min_rating, items, filter_items):
+    """The users scored by ranking_at_k / diversity_at_k: (users, ub, cols, kw, extra) - the distinct users of the
+    held-out pairs that survive `min_rating` and the item filter, the position `ub` of every surviving pair's user,
+    its item, the filter keywords of the model's call and the "filtered_out" entry of the result."""
+    rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
+    allowed, kw = _item_filter(model, cols, items, filter_items)
+    extra = {"filtered_out": int((~allowed).sum())} if kw else {}
+    rows, cols = rows[allowed], cols[allowed]
+    users, ub = np.unique(rows, return_inverse=True)
+    return users, ub, cols, kw, extra
 
 
 def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int) -> Dict[str, Any]:

@@ -1,5 +1,5 @@
-"""Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in` and
-`fold_in_items`.
+"""Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
+`fold_in_items`, `recommend*_diverse` and `list_diversity`.
 
 `_Serving` is the part of the engine (als._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -480,16 +480,16 @@ class _Serving:
                               Z=Z, b_u=self.b_u.index_select(0, us), b_i=b_new, mu=self.mu, out=out)
         return out
 
-    def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
-                             folded: "FoldedItems", filters=None):
-        """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
-        concatenated Z / b_i tables; the batch's user rows are gathered (batch row r = user users_t[r]) and their
-        seen lists are the training row followed by the folded items they rated - ascending, as the new ids come
-        last.  The bitmap of `filters` spans the n + B ids of the concatenated table."""
-        Z_fit = self._compose_for(features)
+    def _joint_side(self, features, folded: "FoldedItems") -> dict:
+        """The item tables of the n fitted items followed by the folded ones (ids n + b)."""
         Z_new, b_new = self._folded_dev(folded)
-        side = dict(k=self.k, ld=self.ld, n=self.n + folded.n_items, Z=torch.cat([Z_fit, Z_new]),
+        return dict(k=self.k, ld=self.ld, n=self.n + folded.n_items, Z=torch.cat([self._compose_for(features), Z_new]),
                     b_i=torch.cat([self.b_i, b_new]), mu=self.mu)
+
+    def _joint_rows(self, users_t: torch.Tensor, exclude_seen: bool, folded: "FoldedItems"):
+        """Chunk source over the joint catalogue: the batch's user rows are gathered (batch row r = user
+        users_t[r]) and their seen lists are the training row followed by the folded items they rated - ascending,
+        as the new ids come last."""
         if exclude_seen:
             # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item
             rp, ri = folded.ratings[0], folded.ratings[1]
@@ -504,7 +504,74 @@ class _Serving:
             seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d) if exclude_seen else (None, None)
             return (torch.arange(nb, dtype=torch.int32, device=self.dev), self.U.index_select(0, us),
                     self.b_u.index_select(0, us), seen_ptr, seen_idx)
-        return self._topk_chunks(users_t.numel(), N, rows, side, allow=self.allow_bitmap(filters, side["n"]))
+        return rows
+
+    def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
+                             folded: "FoldedItems", filters=None):
+        """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
+        concatenated Z / b_i tables (`_joint_side`) with the gathered user rows and merged seen lists of
+        `_joint_rows`.  The bitmap of `filters` spans the n + B ids of the concatenated table."""
+        side = self._joint_side(features, folded)
+        return self._topk_chunks(users_t.numel(), N, self._joint_rows(users_t, exclude_seen, folded), side,
+                                 allow=self.allow_bitmap(filters, side["n"]))
+
+    # ------------------------------------------------------------ diversity
+    def _rerank_chunks(self, B: int, N: int, pool: int, lam: float, rows, items: dict, allow, with_ild: bool):
+        """The pool - `_topk_chunks` with N = pool, kept on the device - re-ranked by als_mmr_rerank against the Z it
+        was scored with, in REC_BATCH chunks; only the [B, N] results come back: (items int64, scores float64, and
+        ild float64 [B] or None)."""
+        pool_val, pool_idx = self._topk_chunks(B, pool, rows, items, on_device=True, allow=allow)
+        out_items = np.empty((B, N), dtype=np.int64)
+        out_scores = np.empty((B, N), dtype=np.float64)
+        out_ild = np.empty(B, dtype=np.float64) if with_ild else None
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            ild = torch.empty(nb, dtype=torch.float32, device=self.dev) if with_ild else None
+            self.be.mmr_rerank(k=items["k"], ld=items["ld"], n=items["n"], Z=items["Z"],
+                               cand_val=pool_val[b0: b0 + nb], cand_idx=pool_idx[b0: b0 + nb], lam=lam, topn=N,
+                               top_val=tv, top_idx=ti, top_cnt=tc, top_ild=ild)
+            out_items[b0: b0 + nb] = ti.cpu().numpy()
+            out_scores[b0: b0 + nb] = tv.cpu().numpy()
+            if with_ild:
+                out_ild[b0: b0 + nb] = ild.cpu().numpy()
+        return out_items, out_scores, out_ild
+
+    def recommend_diverse(self, users_t: torch.Tensor, N: int, pool: int, lam: float, features, exclude_seen: bool,
+                          folded: Optional["FoldedItems"] = None, filters=None, with_ild: bool = False):
+        """`recommend(N=pool)` (or `recommend_with_items` with `folded`) on the device, then the MMR re-rank."""
+        if folded is None:
+            side = self._item_side(self._compose_for(features))
+            rows = self._fitted_rows(users_t, exclude_seen)
+        else:
+            side = self._joint_side(features, folded)
+            rows = self._joint_rows(users_t, exclude_seen, folded)
+        return self._rerank_chunks(users_t.numel(), N, pool, lam, rows, side, self.allow_bitmap(filters, side["n"]),
+                                   with_ild)
+
+    def recommend_new_diverse(self, indptr, indices, vals, N: int, pool: int, lam: float, features, n_sweeps: int,
+                              exclude_seen: bool, filters=None, with_ild: bool = False):
+        """`recommend_new(N=pool)` on the device, then the MMR re-rank."""
+        Z = self._compose_for(features)
+        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        return self._rerank_chunks(indptr.size - 1, N, pool, lam, rows, self._item_side(Z),
+                                   self.allow_bitmap(filters, self.n), with_ild)
+
+    def list_diversity(self, lists: torch.Tensor, features, folded: Optional["FoldedItems"] = None) -> np.ndarray:
+        """ILD float64 [B] of the id lists `lists` (int32 [B, L], -1 padded, device): als_list_diversity in
+        REC_BATCH chunks against the Z of `recommend` (the joint table with `folded`)."""
+        side = self._item_side(self._compose_for(features)) if folded is None else self._joint_side(features, folded)
+        B = lists.shape[0]
+        out = np.empty(B, dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            ild = torch.empty(nb, dtype=torch.float32, device=self.dev)
+            self.be.list_diversity(k=side["k"], ld=side["ld"], n=side["n"], Z=side["Z"], idx=lists[b0: b0 + nb],
+                                   ild=ild)
+            out[b0: b0 + nb] = ild.cpu().numpy()
+        return out
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items

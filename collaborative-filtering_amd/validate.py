@@ -45,6 +45,30 @@ def top_count(x, name: str) -> int:
     return int(x)
 
 
+def diversity_args(diversity, N: int, pool):
+    """(lambda, pool) of `recommend_diverse`: `diversity` a real number in [0, 1]; `pool` None = min(128, 4 N), else
+    an integer with N <= pool <= 128."""
+    if (isinstance(diversity, (bool, np.bool_)) or not isinstance(diversity, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(diversity) <= 1.0):                       # NaN fails the comparison
+        raise ValueError(f"diversity must be a real number in [0, 1], got {diversity!r}")
+    if pool is None:
+        pool = min(RECOMMEND_MAX_N, 4 * N)
+    elif isinstance(pool, bool) or not isinstance(pool, (int, np.integer)) or not N <= pool <= RECOMMEND_MAX_N:
+        raise ValueError(f"pool must be an integer in [N, {RECOMMEND_MAX_N}] = [{N}, {RECOMMEND_MAX_N}], got {pool!r}")
+    return float(diversity), int(pool)
+
+
+def item_lists(lists, n_total: int) -> np.ndarray:
+    """Id lists of `list_diversity`: an integer array [B, L], 1 <= L <= 128, entries -1 (padding) or item ids in
+    [0, n_total) -> int32 [B, L]."""
+    a = np.asarray(lists.detach().cpu().numpy() if torch.is_tensor(lists) else lists)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer) or not 1 <= a.shape[1] <= RECOMMEND_MAX_N:
+        raise ValueError(f"item_lists must be an integer array [B, L] with 1 <= L <= {RECOMMEND_MAX_N}")
+    if a.size and (a.min() < -1 or a.max() >= n_total):
+        raise ValueError(f"item_lists: entries must be -1 (padding) or item ids in [0, {n_total})")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def sweeps(n_sweeps) -> int:
     if n_sweeps is None:
         return 0

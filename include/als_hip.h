@@ -589,6 +589,32 @@ typedef struct als_explain_params {
 int als_explain(const als_explain_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Diversified top-N.  A list is a row of item ids; it ends at the first -1 or at the first
+ * id outside [0, n) (never dereferenced) or at its full width.  For two positions of a list, in fp32 from Z [n][ld]:
+ *   G_jl = z_j . z_l (the matrix-core chain of als_predict_dense),  sim(j, l) = G_jl / sqrt(G_jj G_ll), 0 when either
+ *   norm is 0; one value per unordered pair, so sim(j, l) == sim(l, j) bitwise;
+ *   ILD = mean over the unordered pairs of the list of 1 - sim (fp64 sum in list order), NaN for fewer than 2 items.
+ *
+ * als_mmr_rerank: greedy maximal marginal relevance over a candidate pool per row.  cand_idx / cand_val
+ *   [nrows][pool]: the pool in als_recommend_topk's output form (its top_idx / top_val with topn = pool).  With
+ *   rel_j = (s_j - s_min) / (s_max - s_min) over the pool's entries (every rel_j = 0 when s_max - s_min is 0 or
+ *   not finite), step t = 0 .. topn-1 picks, among the candidates not yet chosen, the one maximising
+ *   (1 - lambda) rel_j - lambda max_{l chosen} sim(j, l)   (the maximum over the empty set is 0),
+ *   ties to the lower pool position.  top_idx / top_val [nrows][topn]: the picks in pick order with their cand_val
+ *   (copied), unused slots -1 / -inf; top_cnt [nrows] = min(topn, entries of the pool); top_ild [nrows] (nullable):
+ *   the ILD of the returned list.  lambda = 0 returns the first topn pool entries of a pool ordered by score.
+ * als_list_diversity: ild [nrows] = the ILD of the lists idx [nrows][len]; on a list als_mmr_rerank returned it is
+ *   bitwise that call's top_ild.
+ * Both: 1 <= pool, len <= ALS_TOPK_MAX, 1 <= topn <= pool, 0 <= lambda <= 1, n < 2^31, ld = als_padded_k(k);
+ * asynchronous on the stream, no workspace; nrows == 0 is a no-op.
+ * ------------------------------------------------------------------------- */
+int als_mmr_rerank(int k, int ld, int64_t nrows, int64_t n, const float* Z, int pool, const float* cand_val,
+                   const int32_t* cand_idx, float lambda, int topn, float* top_val, int32_t* top_idx,
+                   int32_t* top_cnt, float* top_ild, void* stream);
+int als_list_diversity(int k, int ld, int64_t nrows, int64_t n, const float* Z, int len, const int32_t* idx,
+                       float* ild, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
