@@ -23,6 +23,7 @@
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "row_f64_common.hpp"
+#include "slot_fold.hpp"
 
 namespace {
 
@@ -280,18 +281,25 @@ void k_row_tasks_f64(const als_row_solve_params P) {
     finish_row_f64<KB>(P, row, img, rhs_p, cs_p, sumr, sumr2, lane);
 }
 
-// partial slots of a split row summed into its first slot, one thread per element, slots in ascending order
+// partial slots of a split row summed into its first slot, slots in ascending order: k_sum_slots (row_solve.hip)
+// on doubles, one thread per f64x2
 template <int KB>
-__global__ __launch_bounds__(256)
+struct SumSlotsF64 {
+    static_assert(F64Cfg<KB>::SLOT % 2 == 0, "a slot is a whole number of f64x2");
+    static constexpr int NV = F64Cfg<KB>::SLOT / 2;
+    static constexpr int GROUPS = (NV + 63) / 64;
+};
+
+template <int KB>
+__global__ __launch_bounds__(64)
 void k_sum_slots_f64(const als_long_row* __restrict__ long_rows, double* __restrict__ workspace) {
-    constexpr int N = F64Cfg<KB>::SLOT;
-    const als_long_row lr = long_rows[blockIdx.x];
-    const int e = blockIdx.y * 256 + threadIdx.x;
-    if (e >= N || lr.nslots < 2) return;
-    double* w0 = workspace + (size_t)lr.slot0 * N + e;
-    double acc = w0[0];
-    for (int s = 1; s < lr.nslots; ++s) acc += w0[(size_t)s * N];
-    w0[0] = acc;
+    using slot_fold::f64x2;
+    constexpr int NV = SumSlotsF64<KB>::NV, G = SumSlotsF64<KB>::GROUPS;
+    const als_long_row lr = long_rows[blockIdx.x / G];
+    const int e = (blockIdx.x % G) * 64 + threadIdx.x;
+    if (e >= NV || lr.nslots < 2) return;
+    f64x2* w0 = reinterpret_cast<f64x2*>(workspace) + (size_t)lr.slot0 * NV + e;
+    w0[0] = slot_fold::fold<false>(w0, (size_t)NV, lr.nslots);
 }
 
 template <int KB>
@@ -371,7 +379,8 @@ int launch_row_solve_f64(const als_row_solve_params* p, hipStream_t st) {
     if (p->ntasks > 0)
         hipLaunchKernelGGL(k_row_tasks_f64<KB>, dim3((unsigned)p->ntasks), dim3(64), 0, st, *p);
     if (p->nlong > 0) {
-        hipLaunchKernelGGL(k_sum_slots_f64<KB>, dim3((unsigned)p->nlong, (C::SLOT + 255) / 256), dim3(256), 0, st,
+        if (p->nlong * SumSlotsF64<KB>::GROUPS > (int64_t)0x7FFFFFFF) return ALS_E_BADARG;
+        hipLaunchKernelGGL(k_sum_slots_f64<KB>, dim3((unsigned)(p->nlong * SumSlotsF64<KB>::GROUPS)), dim3(64), 0, st,
                            p->long_rows, (double*)p->workspace);
         hipLaunchKernelGGL(k_row_long_f64<KB>, dim3((unsigned)p->nlong), dim3(64), 0, st, *p);
     }
