@@ -17,6 +17,19 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define ALS_EPS 1e-10f
 
+// Host side, the one dispatch over the model width: ALS_DISPATCH_KB(ld / 16, rc = launch<KB>(args)) runs the statement
+// with KB a constant expression, 1 ... 10 (k <= ALS_MAX_K = 160), and goes on behind it (unless the statement
+// returns); for any other width the calling function returns ALS_E_BADK.
+#define ALS_KB_CASE_(N, ...) case N: { constexpr int KB = N; __VA_ARGS__; } break;
+#define ALS_DISPATCH_KB(kb, ...)                                                                           \
+    switch (kb) {                                                                                          \
+        ALS_KB_CASE_(1, __VA_ARGS__) ALS_KB_CASE_(2, __VA_ARGS__) ALS_KB_CASE_(3, __VA_ARGS__)             \
+        ALS_KB_CASE_(4, __VA_ARGS__) ALS_KB_CASE_(5, __VA_ARGS__) ALS_KB_CASE_(6, __VA_ARGS__)             \
+        ALS_KB_CASE_(7, __VA_ARGS__) ALS_KB_CASE_(8, __VA_ARGS__) ALS_KB_CASE_(9, __VA_ARGS__)             \
+        ALS_KB_CASE_(10, __VA_ARGS__)                                                                      \
+        default: return ALS_E_BADK;                                                                        \
+    }
+
 __device__ __forceinline__ float readlane_f(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
 }

@@ -263,15 +263,8 @@ extern "C" int als_mmr_rerank(int k, int ld, int64_t nrows, int64_t n, const flo
     if (nrows == 0) return 0;
     if (!Z || !cand_val || !cand_idx || !top_val || !top_idx || !top_cnt) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_DV_CASE(KB) \
-    case KB: return launch_mmr<KB>(ld, nrows, n, Z, pool, cand_val, cand_idx, lambda, topn, top_val, top_idx, \
-                                   top_cnt, top_ild, st);
-    switch (ld / 16) {
-        ALS_DV_CASE(1) ALS_DV_CASE(2) ALS_DV_CASE(3) ALS_DV_CASE(4) ALS_DV_CASE(5)
-        ALS_DV_CASE(6) ALS_DV_CASE(7) ALS_DV_CASE(8) ALS_DV_CASE(9) ALS_DV_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_DV_CASE
+    ALS_DISPATCH_KB(ld / 16, return launch_mmr<KB>(ld, nrows, n, Z, pool, cand_val, cand_idx, lambda, topn, top_val, top_idx,
+                                                   top_cnt, top_ild, st));
 }
 
 extern "C" int als_list_diversity(int k, int ld, int64_t nrows, int64_t n, const float* Z, int len,
@@ -284,11 +277,5 @@ extern "C" int als_list_diversity(int k, int ld, int64_t nrows, int64_t n, const
     if (nrows == 0) return 0;
     if (!Z || !idx || !ild) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_DV_CASE(KB) case KB: return launch_ild<KB>(ld, nrows, n, Z, len, idx, ild, st);
-    switch (ld / 16) {
-        ALS_DV_CASE(1) ALS_DV_CASE(2) ALS_DV_CASE(3) ALS_DV_CASE(4) ALS_DV_CASE(5)
-        ALS_DV_CASE(6) ALS_DV_CASE(7) ALS_DV_CASE(8) ALS_DV_CASE(9) ALS_DV_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_DV_CASE
+    ALS_DISPATCH_KB(ld / 16, return launch_ild<KB>(ld, nrows, n, Z, len, idx, ild, st));
 }

@@ -273,13 +273,6 @@ extern "C" int als_explain(const als_explain_params* p, void* stream) {
         return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p->nrows);
-#define ALS_EX_CASE(KB) \
-    case KB: hipLaunchKernelGGL(k_explain<KB>, grid, dim3(64), 0, st, *p); break;
-    switch (kp / 16) {
-        ALS_EX_CASE(1) ALS_EX_CASE(2) ALS_EX_CASE(3) ALS_EX_CASE(4) ALS_EX_CASE(5)
-        ALS_EX_CASE(6) ALS_EX_CASE(7) ALS_EX_CASE(8) ALS_EX_CASE(9) ALS_EX_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_EX_CASE
+    ALS_DISPATCH_KB(kp / 16, hipLaunchKernelGGL(k_explain<KB>, grid, dim3(64), 0, st, *p));
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }

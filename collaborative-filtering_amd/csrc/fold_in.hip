@@ -111,13 +111,6 @@ extern "C" int als_fold_in(const als_fold_in_params* p, void* stream) {
         return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p->nrows);
-#define ALS_FI_CASE(KB) \
-    case KB: hipLaunchKernelGGL(k_fold_in<KB>, grid, dim3(64), 0, st, *p); break;
-    switch (kp / 16) {
-        ALS_FI_CASE(1) ALS_FI_CASE(2) ALS_FI_CASE(3) ALS_FI_CASE(4) ALS_FI_CASE(5)
-        ALS_FI_CASE(6) ALS_FI_CASE(7) ALS_FI_CASE(8) ALS_FI_CASE(9) ALS_FI_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_FI_CASE
+    ALS_DISPATCH_KB(kp / 16, hipLaunchKernelGGL(k_fold_in<KB>, grid, dim3(64), 0, st, *p));
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }

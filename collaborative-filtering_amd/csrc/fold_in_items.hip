@@ -173,13 +173,6 @@ extern "C" int als_fold_in_items(const als_fold_in_items_params* p, void* stream
     if (graph && (!p->S_ptr || !p->S_idx || !p->S_val || !p->V || p->n < 1)) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)p->nrows);
-#define ALS_FII_CASE(KB) \
-    case KB: hipLaunchKernelGGL(k_fold_in_items<KB>, grid, dim3(64), 0, st, *p); break;
-    switch (kp / 16) {
-        ALS_FII_CASE(1) ALS_FII_CASE(2) ALS_FII_CASE(3) ALS_FII_CASE(4) ALS_FII_CASE(5)
-        ALS_FII_CASE(6) ALS_FII_CASE(7) ALS_FII_CASE(8) ALS_FII_CASE(9) ALS_FII_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_FII_CASE
+    ALS_DISPATCH_KB(kp / 16, hipLaunchKernelGGL(k_fold_in_items<KB>, grid, dim3(64), 0, st, *p));
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }

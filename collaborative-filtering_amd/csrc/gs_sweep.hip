@@ -714,19 +714,7 @@ extern "C" int als_gs_sweep_dataflow(const als_gs_sweep_params* p, const int32_t
         hipLaunchKernelGGL(k_fill_words, dim3(grid > 0 ? grid : 1), dim3(256), 0, st, (uint32_t*)publish, nwords,
                            (uint32_t)GS_SENTINEL);
     }
-    switch (ld / 16) {
-        case 1: return launch_gs_dataflow<1>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 2: return launch_gs_dataflow<2>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 3: return launch_gs_dataflow<3>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 4: return launch_gs_dataflow<4>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 5: return launch_gs_dataflow<5>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 6: return launch_gs_dataflow<6>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 7: return launch_gs_dataflow<7>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 8: return launch_gs_dataflow<8>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 9: return launch_gs_dataflow<9>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-        case 10: return launch_gs_dataflow<10>(p, S_idx_wait, publish, err, p->nitems, st, nondep);
-    }
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_gs_dataflow<KB>(p, S_idx_wait, publish, err, p->nitems, st, nondep));
 }
 
 #ifdef ALS_GS_STAMPS
@@ -761,17 +749,5 @@ extern "C" int als_gs_sweep(const als_gs_sweep_params* p, void* stream) {
     if (p->nitems > 0 && !p->items) return ALS_E_BADARG;
     if (p->stat_out && (!p->sumr2 || !p->lambda_eff || (ld > 64 && !p->f64))) return ALS_E_BADARG;   // fused stats: k <= 64 (fp32 form)
     hipStream_t st = (hipStream_t)stream;
-    switch (ld / 16) {
-        case 1: return launch_gs<1>(p, st);
-        case 2: return launch_gs<2>(p, st);
-        case 3: return launch_gs<3>(p, st);
-        case 4: return launch_gs<4>(p, st);
-        case 5: return launch_gs<5>(p, st);
-        case 6: return launch_gs<6>(p, st);
-        case 7: return launch_gs<7>(p, st);
-        case 8: return launch_gs<8>(p, st);
-        case 9: return launch_gs<9>(p, st);
-        case 10: return launch_gs<10>(p, st);
-    }
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_gs<KB>(p, st));
 }

@@ -6,6 +6,7 @@
 //   als_predict_dense U Z^T + mu + b_u + b_i      (scripts/als.py:574)
 #include "als_device.hpp"
 #include "als_hip.h"
+#include "catalogue_walk.hpp"
 
 namespace {
 
@@ -44,7 +45,7 @@ void k_predict_at(int ld, int64_t npairs, const int32_t* __restrict__ us, const 
         dot += __shfl_xor(dot, 2, 64);
         dot += __shfl_xor(dot, 4, 64);
         dot += __shfl_xor(dot, 8, 64);
-        if (ok && c == 0) out[t] = dot + mu + b_u[u] + b_i[i];
+        if (ok && c == 0) out[t] = walk::score(dot, mu, b_u[u], b_i[i]);
     }
 }
 
@@ -82,7 +83,7 @@ void k_predict_dense(int ld, int64_t m, int64_t n, const float* __restrict__ U, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t rr = row0 + 4 * q + r;
-                if (rr < m) out[rr * n + col0 + c] = acc[r] + mu + bu[r] + bi;
+                if (rr < m) out[rr * n + col0 + c] = walk::score(acc[r], mu, bu[r], bi);
             }
         }
     }
@@ -110,14 +111,8 @@ extern "C" int als_predict_at(int k, int ld, int64_t npairs, const int32_t* us, 
     int64_t nblk = (npairs + 15) / 16;
     if (nblk > 8192) nblk = 8192;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_PA_CASE(KB) \
-    case KB: hipLaunchKernelGGL(k_predict_at<KB>, dim3((unsigned)nblk), dim3(256), 0, st, ld, npairs, us, is, U, Z, b_u, b_i, mu, out); break;
-    switch (ld / 16) {
-        ALS_PA_CASE(1) ALS_PA_CASE(2) ALS_PA_CASE(3) ALS_PA_CASE(4) ALS_PA_CASE(5)
-        ALS_PA_CASE(6) ALS_PA_CASE(7) ALS_PA_CASE(8) ALS_PA_CASE(9) ALS_PA_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_PA_CASE
+    ALS_DISPATCH_KB(ld / 16, hipLaunchKernelGGL(k_predict_at<KB>, dim3((unsigned)nblk), dim3(256), 0, st, ld, npairs, us,
+                                                is, U, Z, b_u, b_i, mu, out));
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
@@ -130,13 +125,7 @@ extern "C" int als_predict_dense(int k, int ld, int64_t m, int64_t n, const floa
     const dim3 grid((unsigned)((n + 16 * 16 - 1) / (16 * 16)), (unsigned)((m + 15) / 16));
     if (grid.y > 65535u * 32u) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_PD_CASE(KB) \
-    case KB: hipLaunchKernelGGL(k_predict_dense<KB>, grid, dim3(256), 0, st, ld, m, n, U, Z, b_u, b_i, mu, out); break;
-    switch (ld / 16) {
-        ALS_PD_CASE(1) ALS_PD_CASE(2) ALS_PD_CASE(3) ALS_PD_CASE(4) ALS_PD_CASE(5)
-        ALS_PD_CASE(6) ALS_PD_CASE(7) ALS_PD_CASE(8) ALS_PD_CASE(9) ALS_PD_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_PD_CASE
+    ALS_DISPATCH_KB(ld / 16, hipLaunchKernelGGL(k_predict_dense<KB>, grid, dim3(256), 0, st, ld, m, n, U, Z, b_u, b_i, mu,
+                                                out));
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }

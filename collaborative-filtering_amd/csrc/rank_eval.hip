@@ -24,18 +24,22 @@
 // ANDed into the candidate test - so into `above` and `n_cand` alike -, chunks whose word is 0 skipped by the whole
 // workgroup, the prefetch aimed at the next chunk with a set bit.  Target scores are formed whether or not the
 // target is allowed.  The unmasked instantiations contain none of this.
+//
+// "k_recommend's" above means a second copy of that code in this file, not a shared implementation: only the chunk and
+// slice arithmetic and the score epilogue are shared (catalogue_walk.hpp, which says why the rest is not).  An edit
+// to the walk in recommend.hip belongs here too.
 #include "als_device.hpp"
 #include "als_hip.h"
+#include "catalogue_walk.hpp"
 #include "topk_common.hpp"
 
 namespace {
 
 using topk::make_key;
 
-constexpr int RK_CHUNK = 32;        // items per staged chunk: two 16-item score tiles per wave
+constexpr int RK_CHUNK = walk::CHUNK;
 constexpr int RK_TP = 16;           // targets per row and pass (4 * RK_TP counters per lane)
 constexpr int RK_TG = 8;            // targets per skip group
-constexpr int RK_MIN_SLICE = 2048;  // automatic slicing keeps at least this many items per slice
 constexpr unsigned long long RK_NONE = ~0ull;   // target key of a NaN score / an unused slot: nothing is above it
 
 template <int KB, int NW, bool MASKED>
@@ -46,7 +50,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
                   const double* __restrict__ mu_p, const int64_t* __restrict__ seen_ptr,
                   const int32_t* __restrict__ seen_idx, float* __restrict__ t_score, int32_t* __restrict__ above,
                   int32_t* __restrict__ n_cand, int64_t slice_stride, const uint32_t* __restrict__ allow) {
-    constexpr int E = 4 * KB, LD = 16 * KB, ZS = LD + 4;        // LDS row stride: +16 B spreads lanes c over the banks
+    constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int NT = NW * 64, NV = RK_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     __shared__ unsigned long long tks[NW * 16][RK_TP];
     __shared__ __attribute__((aligned(16))) float zs[RK_CHUNK][ZS];
@@ -147,7 +151,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             float a = 0.f, bur = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { a = ((c & 3) == r) ? acc[r] : a; bur = ((c & 3) == r) ? bu[r] : bur; }
-            const float score = a + mu + bur + b_i[item];
+            const float score = walk::score(a, mu, bur, b_i[item]);
             if ((c >> 2) == q) {                                         // lane (c, c / 4) holds row c, column c
                 tw[c][t] = (has && score == score) ? make_key(score, (unsigned)item) : RK_NONE;
                 if (has && blockIdx.y == 0) t_score[ctp + t0 + t] = score;
@@ -223,7 +227,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             const float bi = b_i[min(col, n - 1)];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float score = acc[r] + mu + bu[r] + bi;
+                const float score = walk::score(acc[r], mu, bu[r], bi);
                 const bool cand = col < hi && valid[r] && !((msk[r] >> c) & 1u) && score == score;
                 key[r] = cand ? make_key(score, (unsigned)col) : 0ull;
                 ncand[r] += cand ? 1 : 0;
@@ -331,16 +335,7 @@ void k_rank_reduce(int64_t nt, int64_t nq, int nslices, const int32_t* __restric
 constexpr int rk_waves(int KB) { return KB <= 4 ? 8 : 4; }      // 16-row tiles per workgroup (VGPR budget: DESIGN 15)
 
 int rank_slices(int ld, int64_t nq, int64_t n, int nslices) {
-    const int64_t ub = rk_waves(ld / 16) * 16;
-    const int64_t ublocks = (nq + ub - 1) / ub;
-    int64_t s = nslices;
-    if (s == 0) {                                        // aim at two workgroups per CU, >= RK_MIN_SLICE items each
-        s = (512 + ublocks - 1) / ublocks;
-        s = min(s, (n + RK_MIN_SLICE - 1) / RK_MIN_SLICE);
-    }
-    s = min(s, (int64_t)ALS_RECOMMEND_MAX_SLICES);
-    s = min(s, (n + RK_CHUNK - 1) / RK_CHUNK);            // every slice at least one chunk
-    return (int)max(s, (int64_t)1);
+    return walk::plan_slices(nq, rk_waves(ld / 16) * 16, n, nslices, ALS_RECOMMEND_MAX_SLICES);
 }
 
 template <int KB>
@@ -349,8 +344,7 @@ int launch_rank(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, 
                 const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, float* t_score, int32_t* above,
                 int32_t* n_cand, int64_t slice_stride, hipStream_t st) {
     constexpr int NW = rk_waves(KB);
-    const int64_t nchunks = (n + RK_CHUNK - 1) / RK_CHUNK;
-    const int64_t slice = (nchunks + nsl - 1) / nsl * RK_CHUNK;
+    const int64_t slice = walk::slice_items(n, nsl);
     const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
     auto kern = allow ? k_rank_count<KB, NW, true> : k_rank_count<KB, NW, false>;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n, slice, U, Z, b_u, b_i, mu,
@@ -389,16 +383,9 @@ extern "C" int als_rank_count_masked(int k, int ld, int64_t n, const float* U, c
     // sliced: slice s writes its counts to part[s][0 .. nt) and part[s][nt .. nt + nq)
     int32_t* part = nsl > 1 ? (int32_t*)workspace : nullptr;
     int rc;
-#define ALS_RK_CASE(KB) \
-    case KB: rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, \
-                                  allow, t_score, part ? part : above, part ? part + nt : n_cand, part ? nt + nq : 0, \
-                                  st); break;
-    switch (ld / 16) {
-        ALS_RK_CASE(1) ALS_RK_CASE(2) ALS_RK_CASE(3) ALS_RK_CASE(4) ALS_RK_CASE(5)
-        ALS_RK_CASE(6) ALS_RK_CASE(7) ALS_RK_CASE(8) ALS_RK_CASE(9) ALS_RK_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_RK_CASE
+    ALS_DISPATCH_KB(ld / 16, rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
+                                                  seen_idx, allow, t_score, part ? part : above,
+                                                  part ? part + nt : n_cand, part ? nt + nq : 0, st));
     if (rc != 0 || nsl == 1) return rc;
     hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
                        above, n_cand);

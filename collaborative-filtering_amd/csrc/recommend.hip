@@ -27,8 +27,14 @@
 // so the workgroup's barriers stay matched and the prefetch goes to the chunk that is scored next.  The seen cursors
 // catch up on their own: the exclusion walk consumes every entry below the block it is asked about.  The unmasked
 // instantiations contain none of this: they are the code they were before the bitmap existed.
+//
+// The walk is written a second time in rank_eval.hip (k_rank_count), character for character apart from the RC_ / RK_
+// prefix: fetch / stage, next_chunk / window / after, the cursor set-up, the exclusion walk, the score tiles, the
+// candidate test, the chunk loop.  Only the chunk and slice arithmetic and the score epilogue are one copy
+// (catalogue_walk.hpp, which says why the rest is not): an edit to the walk here belongs there too.
 #include "als_device.hpp"
 #include "als_hip.h"
+#include "catalogue_walk.hpp"
 #include "topk_common.hpp"
 
 namespace {
@@ -37,10 +43,9 @@ using topk::key_index;
 using topk::key_score;
 using topk::make_key;
 
-constexpr int RC_CHUNK = 32;        // items per staged chunk: two 16-item score tiles per wave
+constexpr int RC_CHUNK = walk::CHUNK;
 constexpr int RC_WIDE = 64;         // users per workgroup, topn > 32: 4 waves, 256 keys per user (list 128)
 constexpr int RC_NARROW = 128;      // users per workgroup, topn <= 32: 8 waves, 128 keys per user (list 32)
-constexpr int RC_MIN_SLICE = 2048;  // automatic slicing keeps at least this many items per slice
 
 __device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 
@@ -53,7 +58,7 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
                  const int64_t* __restrict__ seen_ptr, const int32_t* __restrict__ seen_idx, int topn,
                  float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt,
                  unsigned long long* __restrict__ part, const uint32_t* __restrict__ allow) {
-    constexpr int E = 4 * KB, LD = 16 * KB, ZS = LD + 4;        // LDS row stride: +16 B spreads lanes c over the banks
+    constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
     constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     static_assert(L >= 32 && BUF >= 64, "a chunk appends up to 32 keys per row");
@@ -162,7 +167,7 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         const float bi = b_i[min(col, n - 1)];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float score = acc[r] + mu + bu[r] + bi;
+            const float score = walk::score(acc[r], mu, bu[r], bi);
             const unsigned long long key = make_key(score, (unsigned)col);
             const bool pass = col < hi && valid[r] && !((msk[r] >> c) & 1u) && score == score && key > thr[r];
             const unsigned long long m = __ballot(pass);
@@ -322,16 +327,7 @@ void k_recommend_merge(int64_t nusers, int nslices, int topn, const unsigned lon
 }
 
 int rec_slices(int64_t nusers, int64_t n, int topn, int nslices) {
-    const int64_t ub = topn <= 32 ? RC_NARROW : RC_WIDE;
-    const int64_t ublocks = (nusers + ub - 1) / ub;
-    int64_t s = nslices;
-    if (s == 0) {                                        // aim at two workgroups per CU, >= RC_MIN_SLICE items each
-        s = (512 + ublocks - 1) / ublocks;
-        s = min(s, (n + RC_MIN_SLICE - 1) / RC_MIN_SLICE);
-    }
-    s = min(s, (int64_t)ALS_RECOMMEND_MAX_SLICES);
-    s = min(s, (n + RC_CHUNK - 1) / RC_CHUNK);            // every slice at least one chunk
-    return (int)max(s, (int64_t)1);
+    return walk::plan_slices(nusers, topn <= 32 ? RC_NARROW : RC_WIDE, n, nslices, ALS_RECOMMEND_MAX_SLICES);
 }
 
 template <int KB>
@@ -339,9 +335,7 @@ int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, in
                      const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
                      const int32_t* seen_idx, const uint32_t* allow, int topn, float* tv, int32_t* ti, int32_t* tc,
                      unsigned long long* part, hipStream_t st) {
-    // slice length: a whole number of chunks, so every slice but the last is full
-    const int64_t nchunks = (n + RC_CHUNK - 1) / RC_CHUNK;
-    const int64_t slice = (nchunks + nsl - 1) / nsl * RC_CHUNK;
+    const int64_t slice = walk::slice_items(n, nsl);
     if (topn <= 32) {
         const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
         auto kern = allow ? k_recommend<KB, RC_NARROW / 16, 128, true> : k_recommend<KB, RC_NARROW / 16, 128, false>;
@@ -384,15 +378,8 @@ extern "C" int als_recommend_topk_masked(int k, int ld, int64_t nusers, const in
     unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-#define ALS_RC_CASE(KB) \
-    case KB: rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, \
-                                       topn, top_val, top_idx, top_cnt, part, st); break;
-    switch (ld / 16) {
-        ALS_RC_CASE(1) ALS_RC_CASE(2) ALS_RC_CASE(3) ALS_RC_CASE(4) ALS_RC_CASE(5)
-        ALS_RC_CASE(6) ALS_RC_CASE(7) ALS_RC_CASE(8) ALS_RC_CASE(9) ALS_RC_CASE(10)
-        default: return ALS_E_BADK;
-    }
-#undef ALS_RC_CASE
+    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx,
+                                                       allow, topn, top_val, top_idx, top_cnt, part, st));
     if (rc != 0 || nsl == 1) return rc;
     hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
                        top_val, top_idx, top_cnt);

@@ -1205,18 +1205,7 @@ extern "C" int als_row_solve(const als_row_solve_params* p, void* stream) {
 #ifdef ALS_KB_ONLY      // development builds (profiles/ab_builds.sh): one model width only, a tenth of the compile time
     if (ld / 16 == ALS_KB_ONLY) rc = launch_row_solve<ALS_KB_ONLY>(p, st);
 #else
-    switch (ld / 16) {
-        case 1: rc = launch_row_solve<1>(p, st); break;
-        case 2: rc = launch_row_solve<2>(p, st); break;
-        case 3: rc = launch_row_solve<3>(p, st); break;
-        case 4: rc = launch_row_solve<4>(p, st); break;
-        case 5: rc = launch_row_solve<5>(p, st); break;
-        case 6: rc = launch_row_solve<6>(p, st); break;
-        case 7: rc = launch_row_solve<7>(p, st); break;
-        case 8: rc = launch_row_solve<8>(p, st); break;
-        case 9: rc = launch_row_solve<9>(p, st); break;
-        case 10: rc = launch_row_solve<10>(p, st); break;
-    }
+    ALS_DISPATCH_KB(ld / 16, rc = launch_row_solve<KB>(p, st));
 #endif
     // rows the fp32 kernels flagged (condition estimate above the limit, or a broken-down factorisation): fp64
     if (rc == 0 && redo) rc = als_row_redo_f64_dispatch(p, st);

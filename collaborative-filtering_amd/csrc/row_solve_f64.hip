@@ -398,34 +398,10 @@ extern "C" int64_t als_partial_slot_bytes_f64(int k) {
 
 // called by als_row_solve (row_solve.hip) after the fp32 launches of a call with cond_limit > 0
 int als_row_redo_f64_dispatch(const als_row_solve_params* p, hipStream_t st) {
-    switch (p->ld / 16) {
-        case 1: return launch_row_redo_f64<1>(p, st);
-        case 2: return launch_row_redo_f64<2>(p, st);
-        case 3: return launch_row_redo_f64<3>(p, st);
-        case 4: return launch_row_redo_f64<4>(p, st);
-        case 5: return launch_row_redo_f64<5>(p, st);
-        case 6: return launch_row_redo_f64<6>(p, st);
-        case 7: return launch_row_redo_f64<7>(p, st);
-        case 8: return launch_row_redo_f64<8>(p, st);
-        case 9: return launch_row_redo_f64<9>(p, st);
-        case 10: return launch_row_redo_f64<10>(p, st);
-    }
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(p->ld / 16, return launch_row_redo_f64<KB>(p, st));
 }
 
 // called by als_row_solve (row_solve.hip) after its argument checks when gram_mode == ALS_GRAM_F64
 int als_row_solve_f64_dispatch(const als_row_solve_params* p, hipStream_t st) {
-    switch (p->ld / 16) {
-        case 1: return launch_row_solve_f64<1>(p, st);
-        case 2: return launch_row_solve_f64<2>(p, st);
-        case 3: return launch_row_solve_f64<3>(p, st);
-        case 4: return launch_row_solve_f64<4>(p, st);
-        case 5: return launch_row_solve_f64<5>(p, st);
-        case 6: return launch_row_solve_f64<6>(p, st);
-        case 7: return launch_row_solve_f64<7>(p, st);
-        case 8: return launch_row_solve_f64<8>(p, st);
-        case 9: return launch_row_solve_f64<9>(p, st);
-        case 10: return launch_row_solve_f64<10>(p, st);
-    }
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(p->ld / 16, return launch_row_solve_f64<KB>(p, st));
 }

@@ -228,14 +228,8 @@ extern "C" int als_residual_stats(int k, int ld, const int64_t* indptr, const in
         ntasks <= 0 || !partials || !out)
         return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_STATS_CASE(KB) \
-    case KB: return launch_stats<KB>(ld, indptr, indices, vals, U, Z, b_u, b_i, mu, tasks, ntasks, partials, out, st);
-    switch (ld / 16) {
-        ALS_STATS_CASE(1) ALS_STATS_CASE(2) ALS_STATS_CASE(3) ALS_STATS_CASE(4) ALS_STATS_CASE(5)
-        ALS_STATS_CASE(6) ALS_STATS_CASE(7) ALS_STATS_CASE(8) ALS_STATS_CASE(9) ALS_STATS_CASE(10)
-    }
-#undef ALS_STATS_CASE
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_stats<KB>(ld, indptr, indices, vals, U, Z, b_u, b_i, mu, tasks, ntasks, partials,
+                                                     out, st));
 }
 
 extern "C" int als_sum_pairs(const float* x, int64_t npairs, double* partials, double* out, void* stream) {

@@ -1,5 +1,6 @@
-// Per-row top-k selection under a total order, shared by k_topk_sim (graph_build.hip) and the recommendation
-// kernels (recommend.hip).
+// Keys and sorts for per-row top-k selection under a total order: the 64-bit keys for k_recommend /
+// k_recommend_merge (recommend.hip), k_rank_count (rank_eval.hip: it compares keys and never sorts), explain.hip and
+// diversify.hip; the float encoding and the bitonic sorts also for k_topk_sim (graph_build.hip).
 //
 // A candidate is one 64-bit key: the high word is enc_f32(score) - an unsigned encoding whose integer order is the
 // float order, with -0.0 folded onto +0.0 - and the low word is 0xFFFFFFFF - index, so that among equal scores the

@@ -489,19 +489,7 @@ extern "C" int als_w_normal_equations(const als_w_params* p, void* stream) {
         return ALS_E_BADARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    switch (ld / 16) {
-        case 1: return launch_w<1>(p, st);
-        case 2: return launch_w<2>(p, st);
-        case 3: return launch_w<3>(p, st);
-        case 4: return launch_w<4>(p, st);
-        case 5: return launch_w<5>(p, st);
-        case 6: return launch_w<6>(p, st);
-        case 7: return launch_w<7>(p, st);
-        case 8: return launch_w<8>(p, st);
-        case 9: return launch_w<9>(p, st);
-        case 10: return launch_w<10>(p, st);
-    }
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_w<KB>(p, st));
 }
 
 namespace {
@@ -537,14 +525,8 @@ extern "C" int als_item_stats_f64(int k, int ld, int64_t item_begin, int64_t ite
         return ALS_E_BADARG;
     if (item_end == item_begin) return 0;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_IS64(KBV) case KBV: return launch_item_stats_f64<KBV>(item_begin, item_end, ld, gram, rhs, colsum, sumr, \
-                                                                 sumr2, indptr, Z, b_new, b_old, stat_out, st)
-    switch (ld / 16) {
-        ALS_IS64(1); ALS_IS64(2); ALS_IS64(3); ALS_IS64(4); ALS_IS64(5); ALS_IS64(6); ALS_IS64(7); ALS_IS64(8); ALS_IS64(9);
-        ALS_IS64(10);
-    }
-#undef ALS_IS64
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_item_stats_f64<KB>(item_begin, item_end, ld, gram, rhs, colsum, sumr, sumr2,
+                                                              indptr, Z, b_new, b_old, stat_out, st));
 }
 
 extern "C" int als_item_stats(int k, int ld, int64_t item_begin, int64_t item_end, const float* gram,
@@ -558,11 +540,6 @@ extern "C" int als_item_stats(int k, int ld, int64_t item_begin, int64_t item_en
         return ALS_E_BADARG;
     if (item_end == item_begin) return 0;
     hipStream_t st = (hipStream_t)stream;
-#define ALS_IS(KBV) case KBV: return launch_item_stats<KBV>(item_begin, item_end, ld, gram, rhs, colsum, sumr, sumr2, \
-                                                           indptr, Z, b_new, b_old, stat_out, st)
-    switch (ld / 16) {
-        ALS_IS(1); ALS_IS(2); ALS_IS(3); ALS_IS(4); ALS_IS(5); ALS_IS(6); ALS_IS(7); ALS_IS(8); ALS_IS(9); ALS_IS(10);
-    }
-#undef ALS_IS
-    return ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, return launch_item_stats<KB>(item_begin, item_end, ld, gram, rhs, colsum, sumr, sumr2, indptr,
+                                                          Z, b_new, b_old, stat_out, st));
 }

@@ -129,6 +129,20 @@ def _rank_run(torch, be, f, n, seen, q_users, q_ptr, q_items, dev, allow=None):
     return above.cpu().numpy(), ncand.cpu().numpy(), score.cpu().numpy()
 
 
+def _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items):
+    """above[p]: allowed unseen items ahead of target p in (score descending, item ascending); cand[b]: their number."""
+    j = np.arange(dense.shape[1])
+    exp_above, exp_cand = np.zeros(len(q_items), np.int32), np.zeros(len(q_users), np.int32)
+    for b, u in enumerate(q_users):
+        cand = ok.copy()
+        cand[rows[u]] = False
+        exp_cand[b] = cand.sum()
+        for p in range(q_ptr[b], q_ptr[b + 1]):
+            t = q_items[p]
+            exp_above[p] = (cand & ((dense[u] > dense[u, t]) | ((dense[u] == dense[u, t]) & (j < t)))).sum()
+    return exp_above, exp_cand
+
+
 @pytest.mark.parametrize("k,n", [(16, 1003), (64, 4099), (160, 2051)])
 def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
     torch, layout, be, dev = _env()
@@ -142,17 +156,9 @@ def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
     counts[7] = 40                                                         # more than one pass of 16 targets
     q_ptr = np.concatenate([[0], np.cumsum(counts)])
     q_items = rng.integers(0, n, q_ptr[-1])
-    j = np.arange(n)
     for name, ok in _masks(n, seed=n + 1).items():
         allow = _bitmap(torch, ok, dev)
-        exp_above, exp_cand = np.zeros(q_items.size, np.int32), np.zeros(q_users.size, np.int32)
-        for b, u in enumerate(q_users):
-            cand = ok.copy()
-            cand[rows[u]] = False
-            exp_cand[b] = cand.sum()
-            for p in range(q_ptr[b], q_ptr[b + 1]):
-                t = q_items[p]
-                exp_above[p] = (cand & ((dense[u] > dense[u, t]) | ((dense[u] == dense[u, t]) & (j < t)))).sum()
+        exp_above, exp_cand = _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items)
         for s in SLICES + (0,):
             monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
             above, ncand, score = _rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev, allow)
@@ -164,6 +170,74 @@ def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
             for g, e in zip(_rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev),
                             (above, ncand, score)):
                 assert (g == e).all()
+
+
+# The seen cursor behind skipped chunks, at the smallest shape that has it: n = 131 is four chunks of 32 and 3 items,
+# the bitmap has no bit in chunk 1 and none in the low half of chunk 2, and the "walled" and "saturated" rows have seen
+# every item of both - so at chunk 2, the first one scored after the gap, their cursors pass the 32 entries of the
+# skipped chunk and the 16 of the denied half (steps of 16) before the block's own.  17 rows: one full tile and one row of the next.
+SKIP_N, SKIP_K, SKIP_TOPN = 131, 16, 10
+
+
+def _skip_case():
+    n, B = SKIP_N, 17
+    ok = np.ones(n, bool)
+    ok[5:32:4] = False                                                     # chunk 0: partly
+    ok[32:80] = False                                                      # chunk 1, low half of chunk 2
+    ok[80:96:3] = False                                                    # high half of chunk 2: partly
+    ok[129] = False
+    kinds = np.array(["unseen", "walled", "saturated"])[np.arange(B) % 3]
+    rows = []
+    for u in range(B):
+        if kinds[u] == "unseen":
+            rows.append(np.empty(0, np.int64))
+        elif kinds[u] == "walled":                                         # chunks 1 and 2, and a few either side
+            rows.append(np.concatenate([[1 + u, 30], np.arange(32, 96), [96 + u, 130]]))
+        else:                                                              # all but seven, four of them allowed
+            rows.append(np.setdiff1d(np.arange(n), [0, 2, 9, 13, 100 + u, 128, 129]))
+    ptr = np.zeros(B + 1, np.int64)
+    ptr[1:] = np.cumsum([len(r) for r in rows])
+    ncand = np.array([np.setdiff1d(np.nonzero(ok)[0], r).size for r in rows])
+    assert (ncand[kinds != "saturated"] >= SKIP_TOPN).all() and (ncand[kinds == "saturated"] == 4).all()
+    return ok, kinds, rows, ptr, np.concatenate(rows).astype(np.int32)
+
+
+@pytest.mark.parametrize("slices", [1, 2])
+def test_masked_topk_seen_cursor_passes_skipped_chunks(slices, monkeypatch):
+    torch, layout, be, dev = _env()
+    ok, kinds, rows, ptr, idx = _skip_case()
+    B = len(rows)
+    f = _factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
+    dense = _dense(torch, be, f, B, SKIP_N, dev)
+    users = np.arange(B)[::-1].copy()
+    exp = _expected_masked(dense[users], [rows[u] for u in users], ok, SKIP_TOPN)
+    assert (exp[2][kinds[users] != "saturated"] == SKIP_TOPN).all()       # full lists ...
+    assert (exp[2][kinds[users] == "saturated"] == 4).all()               # ... and short ones, padded
+    monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(slices))
+    _assert_same(_run_masked(torch, be, f, users, SKIP_N, ptr, idx, _bitmap(torch, ok, dev), SKIP_TOPN, dev), exp)
+
+
+@pytest.mark.parametrize("slices", [1, 2])
+def test_masked_rank_count_seen_cursor_passes_skipped_chunks(slices, monkeypatch):
+    torch, layout, be, dev = _env()
+    ok, kinds, rows, ptr, idx = _skip_case()
+    B = len(rows)
+    f = _factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
+    dense = _dense(torch, be, f, B, SKIP_N, dev)
+    q_users = np.arange(B)[::-1].copy()
+    # targets in front of, inside and behind the gap; allowed, denied, seen: 0 ... 5 per row
+    pool = np.array([0, 31, 40, 64, 81, 95, 96, 130])
+    counts = np.arange(B) % 6
+    q_ptr = np.concatenate([[0], np.cumsum(counts)])
+    q_items = np.concatenate([pool[(b + np.arange(c)) % pool.size] for b, c in enumerate(counts)])
+    exp_above, exp_cand = _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items)
+    assert (exp_cand[kinds[q_users] == "saturated"] == 4).all()
+    monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(slices))
+    above, ncand, score = _rank_run(torch, be, f, SKIP_N, (ptr, idx), q_users, q_ptr, q_items, dev,
+                                    _bitmap(torch, ok, dev))
+    assert (above == exp_above).all()
+    assert (ncand == exp_cand).all()
+    assert (score == dense[np.repeat(q_users, counts), q_items]).all()
 
 
 # ------------------------------------------------------------------------------------------------ model level
