@@ -2,7 +2,7 @@
 
 torch is used for what it is good at here - device memory, streams, and the
 process group.  All arithmetic of the per-rating / per-row hot path happens in
-the hand-written kernels behind the C ABI.  The engine (als.py) talks to this
+the hand-written kernels behind the C ABI.  The engine (engine.py) talks to this
 object only through the methods below, so that the sharding / collective logic
 can be exercised on CPU under gloo with a stand-in solver living in tests/.
 """
@@ -106,8 +106,8 @@ class HipBackend:
         p.rhs_out, p.colsum_out, p.sumr_out, p.status = _p(rhs_out), _p(colsum_out), _p(sumr_out), _p(status)
         p.sumr2_out, p.stat_out = _p(sumr2_out), _p(stat_out)
         p.tasks, p.ntasks = _p(tasks.tasks), tasks.ntasks
-        p.ndual_tail = int(getattr(tasks, "ndual", 0))      # honoured by the library for plain solves
-        p.ndual_mid = int(getattr(tasks, "nmid", 0))
+        p.ndual_tail = int(tasks.ndual)      # honoured by the library for plain solves
+        p.ndual_mid = int(tasks.nmid)
         p.long_rows, p.nlong = _p(tasks.long_rows), tasks.nlong
         p.workspace = _p(workspace)
         p.F_scale, p.F_scale_ready = _p(self._fscale), 0
@@ -238,7 +238,7 @@ class HipBackend:
 
     def sum_pairs(self, x: torch.Tensor, out: torch.Tensor):
         """out[0:2] = column sums of x viewed as [n, 2] (fp64, deterministic)."""
-        x = getattr(x, "base", x)           # a rank-local by-product array (als._RowShift): reduce what exists
+        x = getattr(x, "base", x)           # a rank-local by-product array (containers._RowShift): reduce what exists
         if getattr(self, "_pair_partials", None) is None:
             self._pair_partials = torch.empty(2 * self._sumsq_partials.numel(), dtype=torch.float64, device=self.device)
         part = self._pair_partials

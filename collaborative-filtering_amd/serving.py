@@ -1,7 +1,7 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse` and `list_diversity`.
 
-`_Serving` is the part of the engine (als._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
+`_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
 of the fit every rank holds the full tables and the training CSR, so nothing here issues a collective.  The
 arithmetic is in the HIP kernels behind the backend (`self.be`); what lives here is the host orchestration: which

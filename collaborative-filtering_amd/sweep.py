@@ -10,7 +10,7 @@ was per-fit host set-up and upload.  This driver removes that part:
     out of them ON THE DEVICE with a keep mask over the resident entries (no COO -> CSR rebuild, no upload);
   * validation (user, item) index tensors and their true values stay on the device per fold;
   * features, the similarity graph of every distinct (feature, top-k, eps), its level schedule per fold, the task
-    lists per (fold, k class) and the (seed, shape, k)-determined initial factors are built once (`als.FitCache`);
+    lists per (fold, k class) and the (seed, shape, k)-determined initial factors are built once (`containers.FitCache`);
   * a fit is then engine allocation + iterations + one prediction launch.
 
 Per-fold scores are those of `cv.eval_variant_cv` (same train entries in the same order, same kernels): identical
@@ -31,7 +31,8 @@ import numpy as np
 import torch
 
 from . import _hip, layout
-from .als import ALS, FitCache, _SideDev
+from .als import ALS
+from .containers import FitCache, _SideDev
 from .cv import CooRatings, rmse_at
 from .helpers import DEFAULT_RANDOM_STATE, ES_MIN_ITERS, ES_TOL, make_config, normalize_params
 

@@ -1,6 +1,7 @@
 """Input checks of the `ALS` facade (als.py), as plain functions: everything a public method verifies about its
 arguments before any device work - fitted-ness, features, list lengths, id arrays, `targets`, `n_sweeps`, the item
-allow / block lists, and the host CSR forms of new users' / new items' ratings and graph rows.  Exception types and
+allow / block lists, the host CSR forms of new users' / new items' ratings and graph rows, and the structure of
+caller-supplied ratings CSR and similarity graphs (`_check_csr`, `_as_side`, `_validate_graph`).  Exception types and
 messages are part of the public behaviour (the reference's where it has one: scripts/als.py:554-565)."""
 from __future__ import annotations
 
@@ -9,6 +10,8 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import layout
+from .containers import _SideDev
 from .serving import RECOMMEND_MAX_N, FoldedItems
 
 
@@ -282,3 +285,53 @@ def new_item_graph_csr(S_new, B: int, n: int):
     if fault == "range":
         raise ValueError(f"S_new: item indices must lie in [0, {n}) (fitted items)")
     return ptr, idx.astype(np.int32), _finite_f32(val, "S_new contains non-finite weights")
+
+
+def _check_csr(indptr: torch.Tensor, indices: torch.Tensor, nrows: int, ncols: int, what: str):
+    """Structural validation of a caller-supplied CSR (one device reduction each): an index outside
+    [0, ncols) would be an out-of-bounds gather inside the kernels."""
+    if indptr.numel() != nrows + 1:
+        raise ValueError(f"{what}: indptr has {indptr.numel()} entries, expected {nrows + 1}")
+    nnz = indices.numel()
+    if int(indptr[0]) != 0 or int(indptr[-1]) != nnz or (nrows and bool((indptr[1:] < indptr[:-1]).any())):
+        raise ValueError(f"{what}: indptr must rise monotonically from 0 to nnz = {nnz}")
+    if nnz and (int(indices.min()) < 0 or int(indices.max()) >= ncols):
+        raise ValueError(f"{what}: index outside [0, {ncols})")
+
+
+def _as_side(triple, nrows: int, ncols: int):
+    indptr, indices, vals = triple
+    if isinstance(indptr, torch.Tensor):
+        if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or vals.dtype != torch.float32:
+            raise ValueError("device CSR needs int64 indptr, int32 indices, float32 vals")
+        if indptr.numel() != nrows + 1 or indices.numel() != vals.numel():
+            raise ValueError("inconsistent CSR sizes")
+        _check_csr(indptr, indices, nrows, ncols, "ratings CSR")
+        return _SideDev(nrows, ncols, indptr.contiguous(), indices.contiguous(), vals.contiguous())
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    _check_csr(torch.from_numpy(indptr), torch.from_numpy(indices), nrows, ncols, "ratings CSR")
+    return layout.SparseSide(nrows, ncols, indptr, indices, np.ascontiguousarray(vals, dtype=np.float32))
+
+
+def _validate_graph(ptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, n: int):
+    """A caller-supplied similarity graph must be what the reference would have built (scripts/als.py:224-240):
+    indices inside [0, n), ascending inside every row, no diagonal, and SYMMETRIC in pattern and value
+    (S = max(S, S^T)).  The level schedule of the Gauss-Seidel sweep relies on the symmetry: a neighbour
+    j > i must sit on a later level so that it still holds its previous value when i is solved."""
+    _check_csr(ptr, idx, n, n, "similarity graph S")
+    if val.numel() != idx.numel():
+        raise ValueError("similarity graph S: values and indices differ in length")
+    if idx.numel() == 0:
+        return
+    rows = torch.repeat_interleave(torch.arange(n, device=ptr.device), ptr[1:] - ptr[:-1])
+    cols = idx.to(torch.int64)
+    key = rows * n + cols
+    if bool((key[1:] <= key[:-1]).any()):
+        raise ValueError("similarity graph S: column indices must be strictly ascending inside every row")
+    if bool((rows == cols).any()):
+        raise ValueError("similarity graph S: diagonal entries are not allowed (the reference zeroes them)")
+    tkey, order = torch.sort(cols * n + rows)
+    if not torch.equal(tkey, key) or not torch.equal(val[order], val):
+        raise ValueError("similarity graph S must be symmetric in pattern and value (S == S^T); "
+                         "symmetrise with max(S, S^T) as the reference does")
