@@ -211,9 +211,15 @@ class NumpyBackend:
         else:
             Z.copy_(V + X @ W)
 
+    @staticmethod
+    def _score(dot, mu, bu, bi):
+        """The epilogue of every prediction (walk::score, csrc/catalogue_walk.hpp): fp32, ((dot + mu) + b_u) + b_i."""
+        mu32 = torch.tensor(float(mu.item()), dtype=torch.float64).float()
+        return ((dot.float() + mu32) + bu.float()) + bi.float()
+
     def predict_at(self, *, k, ld, us, is_, U, Z, b_u, b_i, mu, out):
         u, i = us.long(), is_.long()
-        out.copy_(((U[u] * Z[i]).sum(1).double() + mu.item() + b_u[u] + b_i[i]).float())
+        out.copy_(self._score((U[u].double() * Z[i].double()).sum(1), mu, b_u[u], b_i[i]))
 
     def predict_dense(self, *, k, ld, m, n, U, Z, b_u, b_i, mu, out):
-        out.copy_((U[:m].double() @ Z[:n].double().T + mu.item() + b_u[:m, None] + b_i[None, :n]).float())
+        out.copy_(self._score(U[:m].double() @ Z[:n].double().T, mu, b_u[:m, None], b_i[None, :n]))

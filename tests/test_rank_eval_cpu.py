@@ -14,7 +14,7 @@ class RankNumpyBackend(RecommendNumpyBackend):
     def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above,
                    n_cand):
         u = q_users.long()
-        S = (U[u].double() @ Z[:n].double().T + mu.item() + b_u[u][:, None] + b_i[None, :n]).float().numpy()
+        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
         ptr = q_ptr.numpy()
         for b, uu in enumerate(u.tolist()):
             cand = ~np.isnan(S[b])

@@ -13,7 +13,7 @@ class RecommendNumpyBackend(NumpyBackend):
     def recommend_topk(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx,
                        top_cnt):
         u = users.long()
-        S = (U[u].double() @ Z[:n].double().T + mu.item() + b_u[u][:, None] + b_i[None, :n]).float().numpy()
+        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
         top_val.fill_(-np.inf)
         top_idx.fill_(-1)
         for b, uu in enumerate(u.tolist()):

@@ -54,7 +54,7 @@ class MaskedNumpyBackend(RankNumpyBackend):
         self.calls.append(("recommend_topk_masked", users.numel(), allow.data_ptr()))
         ok = unpack(allow, n)
         u = users.long()
-        S = (U[u].double() @ Z[:n].double().T + mu.item() + b_u[u][:, None] + b_i[None, :n]).float().numpy()
+        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
         top_val.fill_(-np.inf)
         top_idx.fill_(-1)
         for b, uu in enumerate(u.tolist()):
@@ -73,7 +73,7 @@ class MaskedNumpyBackend(RankNumpyBackend):
         self.calls.append(("rank_count_masked", q_users.numel(), allow.data_ptr()))
         ok = unpack(allow, n)
         u = q_users.long()
-        S = (U[u].double() @ Z[:n].double().T + mu.item() + b_u[u][:, None] + b_i[None, :n]).float().numpy()
+        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
         ptr = q_ptr.numpy()
         j = np.arange(n)
         for b, uu in enumerate(u.tolist()):
