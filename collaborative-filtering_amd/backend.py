@@ -59,12 +59,16 @@ class HipBackend:
         self.planes_max_floats = 0 if os.environ.get("ALS_PLANES", "1") == "0" else self.PLANES_MAX_FLOATS
         self.planes_max_floats_k128 = self.PLANES_MAX_FLOATS_K128 if os.environ.get("ALS_PLANES_K128") == "1" else 0
         # solve_dtype="auto": rows whose condition estimate (two lower bounds of cond_2 from their own fp32
-        # factorisation: the pivot ratio (max L_ii / min L_ii)^2 and (trace(G) / rank + lambda) / min L_ii^2) exceeds
+        # factorisation: the pivot ratio (max L_ii / min L_ii)^2 and (trace(G) / rank + lambda) / min L_ii^2, both over
+        # the pivots of the real system - the padding of k to a multiple of 16 has no say) exceeds
         # COND_LIMIT are redone in fp64 by the same call, as are rows whose closed-form residual statistics cancel to
         # fewer than three digits.  Calibration (profiles/r03_cond_estimates.txt): rows of cfg 4 / cfg 3 stay below
         # 5, of cfg 5 (k = 128, |z| up to 3) below 170 - no row of the BASELINE workloads is redone -, the
         # lambda = 1e-2 fixture 14 ... 1300, lambda = 1e-4 10^3 ... 3 10^5.  A row that stays fp32 has a relative
-        # error of at most about COND_LIMIT * 3e-7 = 1e-4 (typically 1e-5).  ALS_COND_LIMIT overrides.
+        # error (max norm) of up to about 55 * estimate * 2^-24 - measured: 3.3e-4 at an estimate of 100, a low-rank
+        # row of 4100 ratings, so about 1e-3 at COND_LIMIT; 1e-5 on well-conditioned rows
+        # (tests/test_gpu_row_auto.py, profiles/row_auto_kernel_test_margins.json).
+        # ALS_COND_LIMIT overrides.
         self.cond_limit = float(os.environ.get("ALS_COND_LIMIT", self.COND_LIMIT)) if solve_dtype == "auto" else 0.0
         self._redo_count = torch.zeros(1, dtype=torch.int32, device=device)
         self._redo_rows: dict = {}         # rows of the orientation -> int32 list buffer

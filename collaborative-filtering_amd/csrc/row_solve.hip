@@ -496,20 +496,26 @@ __device__ __forceinline__ void chol_panels(RowAcc<KB>& A, Chol<KB>& S, float* _
 
 // ---------------------------------------------------------------------------
 // Conditioning-driven precision (als_row_solve_params::cond_limit).  After the fp32 factorisation the lanes hold
-// 1 / L_ii; kappa = (max L_ii / min L_ii)^2 is a lower bound of cond_2(A) (L_ii^2 are Schur-complement diagonals:
-// max_i L_ii^2 <= lambda_max, min_i L_ii^2 >= lambda_min) and within a small factor of it for the matrices met here
-// (G + lambda I with rank-deficient or low-rank G: the last pivots sit at ~lambda).  The fp32 rounding of the Gram
-// (~3e-7 |G|) reaches the solution amplified by cond(A); a row whose kappa exceeds the limit - or whose fp32
-// factorisation broke down - is handed to the fp64 kernel instead of being finished here.  14 + 3 vector
-// instructions per row.  Returns true when the row is to be redone (nothing of it may be stored then).
+// 1 / L_ii; kappa = (max L_ii / min L_ii)^2 over the REAL positions is a lower bound of cond_2(A) (L_ii^2 are
+// Schur-complement diagonals: max_i L_ii^2 <= lambda_max, min_i L_ii^2 >= lambda_min) and within a small factor of it
+// for the matrices met here (G + lambda I with rank-deficient or low-rank G: the last pivots sit at ~lambda).  The
+// padding positions (columns >= k of the primal system, ratings >= len of the dual one) are left out: they carry a
+// unit diagonal that is decoupled from A, so their pivots are exactly 1 and say nothing about A - with them a
+// well-conditioned row of 4000 ratings at k = 50 (pivots ~ 19) had an "estimate" of 370 and went to fp64.  `nreal` is
+// k for the primal system (position i is real when its storage column perm_to_col(i) < k) and the row length for the
+// dual one (DUAL: position i is rating i).  The fp32 rounding of the Gram (~3e-7 |G|) reaches the solution amplified
+// by cond(A); a row whose kappa exceeds the limit - or whose fp32 factorisation broke down - is handed to the fp64
+// kernel instead of being finished here.  About 20 vector instructions per row.  Returns true when the row is to be
+// redone (nothing of it may be stored then).  tests/test_gpu_row_auto.py holds kappa to its fp64 restatement.
 // ---------------------------------------------------------------------------
-template <int KB>
+template <int KB, bool DUAL = false>
 __device__ __forceinline__ bool row_needs_f64(const Chol<KB>& S, const als_row_solve_params& P, int row, bool spd,
-                                              float mean_eig, float short_row_bound, int lane) {
-    float dmx = 0.f, dmn = 0.f;          // max of 1 / L_ii and of L_ii over the lane's rows
+                                              float mean_eig, float short_row_bound, int nreal, int lane) {
+    float dmx = 0.f, dmn = 0.f;          // max of 1 / L_ii and of L_ii over the lane's real rows
 #pragma unroll
     for (int rr = 0; rr < KCfg<KB>::NR; ++rr) {
-        const bool in = lane + 64 * rr < KCfg<KB>::KP;
+        const int i = lane + 64 * rr;
+        const bool in = i < KCfg<KB>::KP && (DUAL ? i : perm_to_col<KB>(i)) < nreal;
         const float d = in ? S.di[rr] : 0.f;
         dmx = fmaxf(dmx, d);
         dmn = fmaxf(dmn, in ? __builtin_amdgcn_rcpf(d) : 0.f);
@@ -635,7 +641,7 @@ __device__ __forceinline__ void finish_row(RowAcc<KB>& A, const als_row_solve_pa
         chol_panels<KB, 0, false>(A, S, Ls, lane);
         const bool spd = chol_spd<KB>(S, lane);
         if (P.cond_limit > 0.f) {
-            if (row_needs_f64<KB>(S, P, row, spd, mean_eig, short_row_bound, lane)) return;
+            if (row_needs_f64<KB>(S, P, row, spd, mean_eig, short_row_bound, P.k, lane)) return;
         } else if (!spd && lane == 0) atomicMax(P.status, row + 1);
         // symmetric completion of L with 1/L_ii on the diagonal, perm space:
         // M[p][i] = L[i][p] (p < i), L[p][i] (p > i)
@@ -671,7 +677,7 @@ __device__ __forceinline__ void finish_row(RowAcc<KB>& A, const als_row_solve_pa
         chol_panels<KB, 0, true>(A, S, Ls, lane);
         const bool spd = chol_spd<KB>(S, lane);
         if (P.cond_limit > 0.f) {
-            if (row_needs_f64<KB>(S, P, row, spd, mean_eig, short_row_bound, lane)) return;
+            if (row_needs_f64<KB>(S, P, row, spd, mean_eig, short_row_bound, P.k, lane)) return;
         } else if (!spd && lane == 0) atomicMax(P.status, row + 1);
     }
     float x[NR];
@@ -870,7 +876,7 @@ __device__ __forceinline__ void row_dual(const als_row_solve_params& P, int row,
         // (F F^T + l I and F^T F + l I share their spectrum up to the multiplicity of l: the same condition estimate)
         const bool spd = chol_spd<NB>(S, lane);
         if (P.cond_limit > 0.f) {
-            if (row_needs_f64<NB>(S, P, row, spd, dual_mean_eig, dual_mean_eig / lam, lane)) return;
+            if (row_needs_f64<NB, true>(S, P, row, spd, dual_mean_eig, dual_mean_eig / lam, len, lane)) return;
         } else if (!spd && lane == 0) atomicMax(P.status, row + 1);
     }
     float w[NS];
