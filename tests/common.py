@@ -1,4 +1,4 @@
-"""Helpers shared by the test modules: golden-fixture loading and oracle runs."""
+"""Helpers shared by the test modules: golden-fixture loading, oracle runs and the model of a fixture."""
 from __future__ import annotations
 
 import glob
@@ -16,6 +16,20 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def golden_names():
     """ALS fit fixtures (g1 ... g9); other .npz files in the directory are fold-file fixtures."""
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "g[0-9]*.npz")))
+
+
+def model_for(g: "Golden", **kw):
+    """The product model configured as fixture g was written (kw: device, backend, solve_dtype, ... of ALS)."""
+    from collaborative_filtering_amd import (ALS, ALSConfig, BiasesConfig, CoreConfig, GraphConfig,
+                                             GraphSimConfig)
+    c = g.cfg
+    cfg = ALSConfig(
+        core=CoreConfig(n_factors=c["n_factors"], n_iters=c["n_iters"], lambda_u=c["lambda_u"],
+                        lambda_v=c["lambda_v"], pop_reg_mode=c["pop_reg_mode"], random_state=42,
+                        update_w_every=c["update_w_every"]),
+        biases=BiasesConfig(lambda_bu=c["lambda_bu"], lambda_bi=c["lambda_bi"]),
+        graph=GraphConfig(alpha=c["alpha"], sim=GraphSimConfig(**c["sim"]) if c["sim"] else None))
+    return ALS(config=cfg, lambda_w=c["lambda_w"], **kw)
 
 
 class Golden:

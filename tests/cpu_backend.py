@@ -6,6 +6,10 @@ conventions as the C ABI (perm space, lower-block Gram, factor completion).
 It exists so that the host-side logic - sharding, all-gathers, the Gauss-Seidel
 level schedule, the W-step algebra, early stopping - can be tested without a
 GPU (world_size-2 gloo tests).  It is never imported by the product package.
+
+The serving methods (recommend_topk[_masked], rank_count[_masked], fold_in, explain, mmr_rerank, list_diversity) are
+adapters from the engine's tensors to the kernels' contracts in tests/serving_ref.py and tests/mmr_ref.py - the same
+text the GPU tests hold the kernels to.  There is no fold_in_items: no CPU test runs that kernel's host path.
 """
 from __future__ import annotations
 
@@ -13,6 +17,8 @@ import numpy as np
 import torch
 
 from collaborative_filtering_amd import layout
+from tests import mmr_ref
+from tests import serving_ref as ref
 
 EPS = 1e-10
 CHUNK = layout.SPLIT_CHUNK
@@ -27,6 +33,8 @@ class NumpyBackend:
 
     def __init__(self, dtype=np.float64):
         self.dtype = dtype
+        self.calls = []         # one tuple per top-N / rank / re-rank / diversity call: (name, rows, ...)
+        self.launches = []      # one (work rows, targets, Z) per explain call
 
     def slot_bytes(self, k):
         kb = layout.padded_k(k) // 16
@@ -223,3 +231,88 @@ class NumpyBackend:
 
     def predict_dense(self, *, k, ld, m, n, U, Z, b_u, b_i, mu, out):
         out.copy_(self._score(U[:m].double() @ Z[:n].double().T, mu, b_u[:m, None], b_i[None, :n]))
+
+    # -- serving: thin adapters to tests/serving_ref.py and tests/mmr_ref.py; `calls` and `launches` record them ------
+    def _serving_rows(self, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx):
+        """fp32 epilogue scores [B, n] of the batch rows and each row's seen items."""
+        u = users.long()
+        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
+        none = np.zeros(0, np.int64)
+        seen = [none if seen_ptr is None else seen_idx[seen_ptr[uu]: seen_ptr[uu + 1]].numpy() for uu in u.tolist()]
+        return S, seen
+
+    def recommend_topk(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx,
+                       top_cnt, allow=None):
+        self.calls.append(("recommend_topk", users.numel()) if allow is None else
+                          ("recommend_topk_masked", users.numel(), allow.data_ptr()))
+        S, seen = self._serving_rows(users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx)
+        ok = None if allow is None else ref.unpack_bitmap(allow.numpy(), n)
+        for out, a in zip((top_val, top_idx, top_cnt), ref.topn_batch(S, seen, ok, topn)):
+            out[: a.shape[0]] = torch.from_numpy(a)         # the engine's buffers may hold more rows than the batch
+
+    def recommend_topk_masked(self, *, allow, **kw):
+        self.recommend_topk(allow=allow, **kw)
+
+    def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above,
+                   n_cand, allow=None):
+        self.calls.append(("rank_count", q_users.numel()) if allow is None else
+                          ("rank_count_masked", q_users.numel(), allow.data_ptr()))
+        S, seen = self._serving_rows(q_users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx)
+        ok = None if allow is None else ref.unpack_bitmap(allow.numpy(), n)
+        counts = ref.rank_counts_batch(S, seen, ok, q_ptr.numpy(), q_items.numpy())
+        for out, a in zip((t_score, above, n_cand), counts):
+            out[: a.shape[0]] = torch.from_numpy(a)         # the engine's buffers may hold more rows than the batch
+
+    def rank_count_masked(self, *, allow, **kw):
+        self.rank_count(allow=allow, **kw)
+
+    def fold_in(self, *, k, ld, indptr, indices, vals, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, U_out, b_u_out,
+                status):
+        ptr = indptr.numpy()
+        U_out.zero_()
+        for r in range(ptr.size - 1):
+            s = slice(ptr[r], ptr[r + 1])
+            u, b = ref.fold_in_user(Z.numpy(), b_i.numpy(), mu.item(), lam_u, lam_bu, indices[s].numpy(),
+                                    vals[s].numpy(), k, n_sweeps)
+            U_out[r, :k] = torch.from_numpy(u).to(U_out.dtype)
+            b_u_out[r] = float(b)
+
+    def explain(self, *, k, ld, indptr, indices, vals, rows, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, t_ptr, t_items,
+                topm, largest, score, latent, leverage, top_item, top_contrib, top_weight, top_cnt, b_u_out, status):
+        W = t_ptr.numel() - 1
+        self.launches.append((W, t_items.numel(), Z))
+        assert int(t_ptr[0]) == 0 and int(t_ptr[-1]) == t_items.numel()
+        assert score.numel() == t_items.numel() and b_u_out.numel() == W and tuple(top_item.shape) == (score.numel(), topm)
+        Zn, bn, ptr = Z.numpy(), b_i.numpy(), indptr.numpy()
+        top_item.fill_(-1)
+        top_contrib.zero_()
+        top_weight.zero_()
+        for w in range(W):
+            r = w if rows is None else int(rows[w])
+            idx = indices[ptr[r]: ptr[r + 1]].numpy()
+            assert (np.diff(idx) > 0).all()
+            vv = vals[ptr[r]: ptr[r + 1]].numpy()
+            for p in range(int(t_ptr[w]), int(t_ptr[w + 1])):
+                e = ref.explain_pair(Zn, bn, mu.item(), lam_u, lam_bu, idx, vv, k, n_sweeps, int(t_items[p]), topm,
+                                     largest)
+                c = e["items"].size
+                score[p], latent[p], leverage[p], top_cnt[p] = e["score"], e["latent"], e["leverage"], c
+                b_u_out[w] = e["b_u"]
+                top_item[p, :c] = torch.from_numpy(e["items"].astype(np.int32))
+                top_contrib[p, :c] = torch.from_numpy(e["contributions"])
+                top_weight[p, :c] = torch.from_numpy(e["weights"])
+
+    def mmr_rerank(self, *, k, ld, n, Z, cand_val, cand_idx, lam, topn, top_val, top_idx, top_cnt, top_ild=None):
+        self.calls.append(("mmr_rerank", cand_idx.shape[0], cand_idx.shape[1], topn, lam, n))
+        assert cand_val.dtype == torch.float32 and cand_idx.dtype == torch.int32 and Z.shape[0] >= n
+        tv, ti, tc, ild, _ = mmr_ref.rerank(Z.numpy(), n, cand_val.numpy(), cand_idx.numpy(), lam, topn)
+        top_val.copy_(torch.from_numpy(tv))
+        top_idx.copy_(torch.from_numpy(ti))
+        top_cnt.copy_(torch.from_numpy(tc))
+        if top_ild is not None:
+            top_ild.copy_(torch.from_numpy(ild.astype(np.float32)))
+
+    def list_diversity(self, *, k, ld, n, Z, idx, ild):
+        self.calls.append(("list_diversity", idx.shape[0], idx.shape[1], n))
+        assert idx.dtype == torch.int32
+        ild.copy_(torch.from_numpy(mmr_ref.list_diversity(Z.numpy(), n, idx.numpy()).astype(np.float32)))

@@ -4,7 +4,6 @@ W-step normal equations, block / exact Gauss-Seidel modes.  The per-row arithmet
 supplied by the test-only numpy stand-in (tests/cpu_backend.py); what is under test is
 the host logic that the 2/4/8-GPU runs execute unchanged with the HIP backend."""
 import os
-import socket
 import sys
 import tempfile
 
@@ -14,54 +13,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, name, gs_mode, outdir):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tests.common import Golden
-        from tests.cpu_backend import NumpyBackend
-        from tests.test_gpu_parity import _model_for
-        g = Golden(name)
-        r, c, v = g.train
-        model = _model_for(g, device="cpu", backend=NumpyBackend(), gs_mode=gs_mode, process_group="world")
-        model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
-                      min_iters=g.cfg["min_iters"], verbose=0)
-        np.savez(os.path.join(outdir, f"rank{rank}.npz"), U=model.U, V=model.V, b_u=model.b_u,
-                 b_i=model.b_i, mu=model.mu, rmse=np.asarray(model.history["train_rmse"]),
-                 **{"W_" + f: model.W[f] for f in g.cfg["feats"]})
-    finally:
-        dist.destroy_process_group()
-
-
-def _run(name, gs_mode=None, world=2):
-    with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_worker, args=(world, _free_port(), name, gs_mode, d), nprocs=world, join=True)
-        return [np.load(os.path.join(d, f"rank{r}.npz")) for r in range(world)]
-
-
-def _single(name):
-    from tests.common import Golden
-    from tests.cpu_backend import NumpyBackend
-    from tests.test_gpu_parity import _model_for
-    g = Golden(name)
-    r, c, v = g.train
-    model = _model_for(g, device="cpu", backend=NumpyBackend())
-    model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
-                  min_iters=g.cfg["min_iters"], verbose=0)
-    return g, model
+from tests.dist_common import ROOT, fit_worker, free_port, join_group, spawn
+from tests.dist_common import sharded_fit as _run
+from tests.dist_common import single_fit as _single
 
 
 @pytest.mark.parametrize("name", ["g2_bias_pop", "g3_empty", "g4_feat_uw2"])
@@ -144,11 +98,8 @@ def _skewed_problem():
 
 
 def _skewed_worker(rank, world, port, graph, outdir):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+        join_group(rank, world, port)
     try:
         from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, GraphConfig, GraphSimConfig
         from tests.cpu_backend import NumpyBackend
@@ -175,7 +126,7 @@ def test_four_ranks_rating_balanced_shards_on_a_skewed_input(graph):
     with tempfile.TemporaryDirectory() as d1, tempfile.TemporaryDirectory() as d4:
         _skewed_worker(0, 1, 0, graph, d1)
         ref = np.load(os.path.join(d1, "rank0.npz"))
-        mp.spawn(_skewed_worker, args=(4, _free_port(), graph, d4), nprocs=4, join=True)
+        mp.spawn(_skewed_worker, args=(4, free_port(), graph, d4), nprocs=4, join=True)
         outs = [np.load(os.path.join(d4, f"rank{r}.npz")) for r in range(4)]
     ub = outs[0]["ubounds"]
     rows = ub[:, 1] - ub[:, 0]
@@ -192,16 +143,15 @@ def test_four_ranks_rating_balanced_shards_on_a_skewed_input(graph):
 def test_fused_statistics_closed_form_on_cpu():
     """Graph on, no features: the engine takes mu / RMSE from the per-item closed form (stand-in
     implements the same formula as the sweep kernel) - must equal the standalone residual pass."""
-    from tests.common import Golden
+    from tests.common import Golden, model_for
     from tests.cpu_backend import NumpyBackend
-    from tests.test_gpu_parity import _model_for
 
     NoFuse = type("NoFuse", (object,), {k: v for k, v in NumpyBackend.__dict__.items() if k != "sum_pairs"})
 
     g = Golden("g5_graph_a0.5")
     r, c, v = g.train
-    a = _model_for(g, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0, S=g.S_csr())
-    b = _model_for(g, device="cpu", backend=NoFuse()).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0, S=g.S_csr())
+    a = model_for(g, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0, S=g.S_csr())
+    b = model_for(g, device="cpu", backend=NoFuse()).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0, S=g.S_csr())
     assert a._eng.fused_stats and not b._eng.fused_stats
     np.testing.assert_allclose(a.history["train_rmse"], b.history["train_rmse"], rtol=1e-6)
     np.testing.assert_allclose(a.V, b.V, rtol=1e-5, atol=1e-7)
@@ -209,7 +159,7 @@ def test_fused_statistics_closed_form_on_cpu():
 
 def _forced_worker(rank, world, port, name, gs_mode, outdir):
     os.environ["ALS_FORCE_COLLECTIVES"] = "1"
-    _worker(rank, world, port, name, gs_mode, outdir)
+    fit_worker(rank, world, port, name, gs_mode, False, outdir)
 
 
 @pytest.mark.parametrize("gs_mode", ["block", "exact", "levels"])
@@ -218,9 +168,7 @@ def test_forced_collectives_on_one_rank(gs_mode):
     per-level exchange in exact mode) on a one-rank group - the rehearsal mode `bench.py` uses to
     exercise the RCCL calls on a single GPU.  Results must equal the plain single-process run."""
     g, ref = _single("g5_graph_a0.5")
-    with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_forced_worker, args=(1, _free_port(), "g5_graph_a0.5", gs_mode, d), nprocs=1, join=True)
-        out = np.load(os.path.join(d, "rank0.npz"))
+    out, = spawn(_forced_worker, 1, "g5_graph_a0.5", gs_mode)
     np.testing.assert_array_equal(out["U"], ref.U)
     np.testing.assert_array_equal(out["V"], ref.V)
     np.testing.assert_array_equal(out["rmse"], ref.history["train_rmse"])
@@ -257,15 +205,11 @@ def test_four_rank_shards_are_balanced_by_predicted_cost():
 def _status_worker(rank, world, port, outdir):
     """Rank 1's sweep raises the error word once (as a timed-out dependency wait would); the status words are
     reduced over the group, so BOTH ranks must see SweepNotResident in the same iteration and refit together."""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    join_group(rank, world, port)
     try:
         import collaborative_filtering_amd.als as A
-        from tests.common import Golden
+        from tests.common import Golden, model_for
         from tests.cpu_backend import NumpyBackend
-        from tests.test_gpu_parity import _model_for
 
         class FlakyDataflow(NumpyBackend):
             """Stand-in with a `gs_dataflow` entry (level by level underneath)."""
@@ -282,7 +226,7 @@ def _status_worker(rank, world, port, outdir):
         g = Golden("g5_graph_a0.5")
         r, c, v = g.train
         be = FlakyDataflow()
-        model = _model_for(g, device="cpu", backend=be, process_group="world")
+        model = model_for(g, device="cpu", backend=be, process_group="world")
         be.engine = lambda: model._eng
         raised = []
         orig_init = A._Engine.__init__
@@ -301,9 +245,7 @@ def _status_worker(rank, world, port, outdir):
 
 def test_sweep_error_on_one_rank_makes_every_rank_refit():
     g, ref = _single("g5_graph_a0.5")
-    with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_status_worker, args=(2, _free_port(), d), nprocs=2, join=True)
-        outs = [np.load(os.path.join(d, f"rank{r}.npz")) for r in range(2)]
+    outs = spawn(_status_worker, 2)
     for o in outs:
         assert int(o["engines"]) == 2 and int(o["dataflow"]) == 0        # both ranks built a second engine
         np.testing.assert_array_equal(o["V"], ref.V)
@@ -335,8 +277,8 @@ def test_bench_torchrun_path_end_to_end_on_four_cpu_ranks():
     argument or shape bug surfaces here, not on the 8-GPU node.  The history equals the one-rank run bitwise."""
     import json
     with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_bench_worker, args=(4, _free_port(), d), nprocs=4, join=True)
-        mp.spawn(_bench_worker, args=(1, _free_port(), d), nprocs=1, join=True)
+        mp.spawn(_bench_worker, args=(4, free_port(), d), nprocs=4, join=True)
+        mp.spawn(_bench_worker, args=(1, free_port(), d), nprocs=1, join=True)
         o4 = json.load(open(os.path.join(d, "bench_w4.json")))
         o1 = json.load(open(os.path.join(d, "bench_w1.json")))
     assert o4["n_gpus"] == 4 and o4["steps"] == 2 and o4["value"] > 0 and o4["scaling"] == "strong"

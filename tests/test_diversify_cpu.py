@@ -1,5 +1,5 @@
 """Diversified top-N (ALS.recommend_diverse / recommend_new_diverse / list_diversity, cv.diversity_at_k) without a
-GPU: validation, the host orchestration over a numpy stand-in backend whose mmr_rerank / list_diversity restate the
+GPU: validation, the host orchestration over the numpy stand-in backend, whose mmr_rerank / list_diversity are the
 contract of als_mmr_rerank / als_list_diversity in float64 (tests/mmr_ref.py), the cv measure on a hand-made
 example, and the presence of the new symbols in the built library."""
 import ctypes
@@ -7,35 +7,15 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, cv, validate
 from collaborative_filtering_amd.serving import FoldedItems
 from tests import mmr_ref
+from tests.cpu_backend import NumpyBackend
 from tests.synth import make_ratings
-from tests.test_recommend_filter_cpu import MaskedNumpyBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "collaborative-filtering_amd", "csrc", "libals_hip.so")
-
-
-class DiverseNumpyBackend(MaskedNumpyBackend):
-    """mmr_rerank / list_diversity = tests/mmr_ref.py on the tensors the engine passes; every call is recorded."""
-
-    def mmr_rerank(self, *, k, ld, n, Z, cand_val, cand_idx, lam, topn, top_val, top_idx, top_cnt, top_ild=None):
-        self.calls.append(("mmr_rerank", cand_idx.shape[0], cand_idx.shape[1], topn, lam, n))
-        assert cand_val.dtype == torch.float32 and cand_idx.dtype == torch.int32 and Z.shape[0] >= n
-        tv, ti, tc, ild, _ = mmr_ref.rerank(Z.numpy(), n, cand_val.numpy(), cand_idx.numpy(), lam, topn)
-        top_val.copy_(torch.from_numpy(tv))
-        top_idx.copy_(torch.from_numpy(ti))
-        top_cnt.copy_(torch.from_numpy(tc))
-        if top_ild is not None:
-            top_ild.copy_(torch.from_numpy(ild.astype(np.float32)))
-
-    def list_diversity(self, *, k, ld, n, Z, idx, ild):
-        self.calls.append(("list_diversity", idx.shape[0], idx.shape[1], n))
-        assert idx.dtype == torch.int32
-        ild.copy_(torch.from_numpy(mmr_ref.list_diversity(Z.numpy(), n, idx.numpy()).astype(np.float32)))
 
 
 M, N_ITEMS = 30, 70
@@ -46,7 +26,7 @@ def fitted():
     r, c, v = make_ratings(M, N_ITEMS, 500, seed=3, empty_users=(4,))
     cfg = ALSConfig(core=CoreConfig(n_factors=5, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    model = ALS(cfg, device="cpu", backend=DiverseNumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
+    model = ALS(cfg, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
     return model, r, c
 
 

@@ -3,8 +3,7 @@ method reads exists on every path (None / False where it does not apply) - with 
 statistics, on the numpy stand-in and on the HIP backend, eagerly and under captured-graph replay."""
 import pytest
 
-from tests.common import Golden
-from tests.test_gpu_parity import _model_for
+from tests.common import Golden, model_for
 
 FIXTURES = ["g1_plain", "g4_feat_uw5", "g5_graph_a0.5", "g10_full_k64"]
 # what reads of the form getattr(eng, name, default) / hasattr(eng, name) used to ask for
@@ -22,7 +21,7 @@ def _engine(name, **kw):
     g = Golden(name)
     r, c, v = g.train
     csr, csc = layout.coo_to_sides(r, c, v, (g.m, g.n))
-    model = _model_for(g, **kw)
+    model = model_for(g, **kw)
     eng = model.prepare_csr((csr.indptr, csr.indices, csr.vals), (csc.indptr, csc.indices, csc.vals), (g.m, g.n),
                             features=g.features or None)
     return model, eng                   # (the engine holds the model weakly)

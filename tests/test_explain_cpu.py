@@ -1,6 +1,6 @@
-"""ALS.explain / explain_new and cv.leverage_calibration without a GPU: the C struct mirror, the algebra of the
-contract (the half-step user's latent score splits over the rated items), and the host logic of the engine on a
-numpy stand-in backend whose `explain` restates the contract of als_explain in float64."""
+"""ALS.explain / explain_new and cv.leverage_calibration without a GPU: the C struct mirror and the host logic of the
+engine on the numpy stand-in backend, whose `explain` is the contract of als_explain in float64
+(`explain_pair` of tests/serving_ref.py; its algebra is checked in tests/test_serving_ref_cpu.py)."""
 import os
 
 import numpy as np
@@ -8,9 +8,10 @@ import pytest
 import torch
 
 from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, Explanation, cv
-from oracle.als_oracle import EPS, OracleALS, OracleConfig, ratings_from_coo
+from tests import serving_ref as ref
+from tests.cpu_backend import NumpyBackend
+from tests.serving_ref import EPS
 from tests.synth import make_features, make_ratings
-from tests.test_rank_eval_cpu import RankNumpyBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("score", "latent", "leverage", "b_u", "items", "contributions", "weights", "counts")
@@ -39,116 +40,7 @@ def test_struct_layout_matches_header(tmp_path):
     assert hasattr(lib, "als_explain") and lib.als_version() == 103
 
 
-# ------------------------------------------------------------------------------------------ algebra
-@pytest.mark.parametrize("T", [None, 1, 3])
-@pytest.mark.parametrize("lam_u", [5.0, 1e-4])
-@pytest.mark.parametrize("k", [8, 64])
-def test_contributions_sum_to_the_half_step_users_latent_score(k, lam_u, T):
-    """(u, b_u) from OracleALS.user_step iterated T times (None: the bordered solve); with bprev the bias u was
-    solved with, sum_j (z_i^T A^-1 z_j)(r_j - mu - b_i[j] - bprev) = u.z_i and 0 < z_i^T A^-1 z_i <= |z_i|^2 / lambda.
-    Both sides are float64 solves against A, so they differ by a few cond(A) * 2^-52 (measured when the feature was
-    specified: 2e-15 at lambda_u = 5, 2e-11 at lambda_u = 1e-4 with cond(A) ~ 1e5); the bound is 100 cond(A) 2^-52."""
-    n = 6 * k
-    rng = np.random.default_rng(k + (0 if T is None else T))
-    Z = (rng.standard_normal((n, k)) * 0.3).astype(np.float32).astype(np.float64)
-    b_i = (rng.standard_normal(n) * 0.2).astype(np.float32).astype(np.float64)
-    mu, lam_bu = 3.4, 3.0
-    lam = lam_u + EPS
-    for nr in (0, 1, k // 2, k, 5 * k):
-        cols = np.sort(rng.permutation(n)[:nr])
-        vals = rng.integers(1, 11, nr) * 0.5
-        targets = rng.permutation(n)[:6]
-        if nr == 0:                                           # no ratings: u = 0, leverage |z_i|^2 / lambda
-            for i in targets:
-                assert np.isclose(Z[i] @ np.linalg.solve(lam * np.eye(k), Z[i]), Z[i] @ Z[i] / lam, rtol=1e-14)
-            continue
-        Zs = Z[cols]
-        res = vals - mu - b_i[cols]
-        A = Zs.T @ Zs + lam * np.eye(k)
-        if T is None:
-            h = Zs.sum(axis=0)
-            Mb = np.block([[A, h[:, None]], [h[None, :], np.array([[nr + lam_bu + EPS]])]])
-            x = np.linalg.solve(Mb, np.append(Zs.T @ res, res.sum()))
-            u, bprev = x[:k], x[k]
-        else:
-            o = OracleALS(OracleConfig(n_factors=k, n_iters=1, lambda_u=lam_u, lambda_v=1.0, lambda_bu=lam_bu,
-                                       lambda_bi=1.0))
-            o.mu, o.b_i = mu, b_i
-            o.U, o.b_u = np.zeros((1, k)), np.zeros(1)
-            rt = ratings_from_coo(np.zeros(nr, np.int64), cols, vals, (1, n))
-            for _ in range(T):
-                bprev = o.b_u[0]
-                o.user_step(rt, Z)
-            u = o.U[0]
-        rho = res - bprev
-        bound = 100 * np.linalg.cond(A) * 2.0 ** -52
-        for i in targets:
-            w = np.linalg.solve(A, Z[i])
-            contrib = (Zs @ w) * rho
-            assert abs(contrib.sum() - u @ Z[i]) <= bound * max(1.0, abs(u @ Z[i])), (nr, i)
-            lev = w @ Z[i]
-            assert 0 < lev <= Z[i] @ Z[i] / lam * (1 + bound)
-
-
 # ------------------------------------------------------------------------------------------ stand-in backend
-def explain_reference(Z, b_i, mu, lam_u, lam_bu, idx, vals, k, T, target, M, largest):
-    """The contract of als_explain for one (row, target) in float64 numpy (Z, b_i: the fp32 tables)."""
-    lam = float(np.float32(lam_u)) + EPS
-    Zs = Z[idx, :k].astype(np.float64)
-    res = vals.astype(np.float64) - mu - b_i[idx].astype(np.float64)
-    A = Zs.T @ Zs + lam * np.eye(k)
-    b = bprev = 0.0
-    if idx.size:
-        g, h, s, d = Zs.T @ res, Zs.sum(axis=0), res.sum(), idx.size + float(np.float32(lam_bu)) + EPS
-        p, q = np.linalg.solve(A, g), np.linalg.solve(A, h)
-        if T == 0:
-            b = bprev = (s - h @ p) / (d - h @ q)
-        else:
-            for _ in range(T):
-                bprev = b
-                b = (s - h @ p + b * (h @ q)) / d
-    zi = Z[target, :k].astype(np.float64)
-    w = np.linalg.solve(A, zi)
-    weight = Zs @ w
-    contrib = weight * (res - bprev)
-    latent = float(contrib.sum())
-    key = (contrib if largest else -contrib).astype(np.float32) + np.float32(0.0)
-    order = np.lexsort((idx, -key))[:M]
-    return dict(score=mu + b + float(b_i[target]) + latent, latent=latent, leverage=float(w @ zi), b_u=b,
-                items=idx[order], contributions=contrib[order], weights=weight[order])
-
-
-class ExplainNumpyBackend(RankNumpyBackend):
-    def __init__(self):
-        super().__init__()
-        self.launches = []
-
-    def explain(self, *, k, ld, indptr, indices, vals, rows, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, t_ptr, t_items,
-                topm, largest, score, latent, leverage, top_item, top_contrib, top_weight, top_cnt, b_u_out, status):
-        W = t_ptr.numel() - 1
-        self.launches.append((W, t_items.numel(), Z))
-        assert int(t_ptr[0]) == 0 and int(t_ptr[-1]) == t_items.numel()
-        assert score.numel() == t_items.numel() and b_u_out.numel() == W and tuple(top_item.shape) == (score.numel(), topm)
-        Zn, bn, ptr = Z.numpy(), b_i.numpy(), indptr.numpy()
-        top_item.fill_(-1)
-        top_contrib.zero_()
-        top_weight.zero_()
-        for w in range(W):
-            r = w if rows is None else int(rows[w])
-            idx = indices[ptr[r]: ptr[r + 1]].numpy()
-            assert (np.diff(idx) > 0).all()
-            vv = vals[ptr[r]: ptr[r + 1]].numpy()
-            for p in range(int(t_ptr[w]), int(t_ptr[w + 1])):
-                e = explain_reference(Zn, bn, mu.item(), lam_u, lam_bu, idx, vv, k, n_sweeps, int(t_items[p]), topm,
-                                      largest)
-                c = e["items"].size
-                score[p], latent[p], leverage[p], top_cnt[p] = e["score"], e["latent"], e["leverage"], c
-                b_u_out[w] = e["b_u"]
-                top_item[p, :c] = torch.from_numpy(e["items"].astype(np.int32))
-                top_contrib[p, :c] = torch.from_numpy(e["contributions"])
-                top_weight[p, :c] = torch.from_numpy(e["weights"])
-
-
 M_USERS, N_ITEMS, K = 30, 25, 5
 
 
@@ -159,7 +51,7 @@ def fitted():
     feats = {"genres": G, "years": y}
     cfg = ALSConfig(core=CoreConfig(n_factors=K, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    be = ExplainNumpyBackend()
+    be = NumpyBackend()
     model = ALS(cfg, lambda_w={"genres": 1.0, "years": 1.0}, device="cpu", backend=be)
     model.fit_coo(r, c, v, (M_USERS, N_ITEMS), features=feats, tol=None, verbose=0)
     return model, be, feats, r, c, v
@@ -168,8 +60,8 @@ def fitted():
 def _expected(model, Zfeat, r, c, v, u, i, M, T, largest):
     eng = model._eng
     sel = r == u
-    return explain_reference(Zfeat, eng.b_i.numpy(), eng.mu.item(), model.lambda_u, model.lambda_bu,
-                             c[sel].astype(np.int32), v[sel].astype(np.float32), K, T, int(i), M, largest)
+    return ref.explain_pair(Zfeat, eng.b_i.numpy(), eng.mu.item(), model.lambda_u, model.lambda_bu,
+                            c[sel].astype(np.int32), v[sel].astype(np.float32), K, T, int(i), M, largest)
 
 
 def _assert_pair(ex, p, e, M):
@@ -280,7 +172,7 @@ def test_explain_argument_errors(fitted):
     model = fitted[0]
     cfg = ALSConfig(core=CoreConfig(n_factors=3, n_iters=1, lambda_u=1.0, lambda_v=1.0))
     with pytest.raises(RuntimeError, match="Model must be fitted before prediction."):
-        ALS(cfg, device="cpu", backend=ExplainNumpyBackend()).explain([0], [0])
+        ALS(cfg, device="cpu", backend=NumpyBackend()).explain([0], [0])
     for M in (0, 129, 2.0, True, None):
         with pytest.raises(ValueError, match="M must be an integer"):
             model.explain([0], [0], M)

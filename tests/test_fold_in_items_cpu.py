@@ -1,12 +1,12 @@
-"""Item fold-in without a GPU: the C struct mirror, the one-factorisation reformulation of the fit's item half-step
-for a new column, the input validation of ALS.fold_in_items, and the torch formulation of the new items' graph
-rows."""
+"""Item fold-in without a GPU: the C struct mirror, the zero-rating closed form of the contract (`fold_in_item` of
+tests/serving_ref.py; its equivalence to the fit's item half-step is checked in tests/test_serving_ref_cpu.py), the
+input validation of ALS.fold_in_items, and the torch formulation of the new items' graph rows."""
 import os
 
 import numpy as np
 import pytest
 
-from oracle.als_oracle import EPS, OracleALS, OracleConfig, ratings_from_coo
+from tests.serving_ref import EPS, fold_in_item
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,75 +31,6 @@ def test_struct_layout_matches_header(tmp_path):
     assert "als_fold_in_items" in _hip.EXPORTS
 
 
-def fold_item_reference(U, b_u, mu, V, raters, r, nb_idx, nb_val, lam_v, pop_reg, lam_bi, alpha, T):
-    """The contract of als_fold_in_items for one item, in float64: T >= 1 alternations from b = 0 through the
-    recurrence on p = A^-1 g, q = A^-1 h, or (T = 0) the bordered fixed point."""
-    k = U.shape[1]
-    n_i = raters.size
-    lv = lam_v / np.sqrt(n_i + 1.0) if pop_reg else lam_v
-    lam = lv + EPS + alpha * nb_val.sum()
-    Us = U[raters]
-    res = r - mu - b_u[raters]
-    A = Us.T @ Us + lam * np.eye(k)
-    g = Us.T @ res + alpha * (nb_val @ V[nb_idx])
-    h, s, d = Us.sum(axis=0), res.sum(), n_i + lam_bi + EPS
-    p, q = np.linalg.solve(A, g), np.linalg.solve(A, h)
-    if T == 0:
-        b = (s - h @ p) / (d - h @ q)
-        return p - b * q, b
-    b = bp = 0.0
-    for _ in range(T):
-        bp, b = b, (s - h @ p + b * (h @ q)) / d
-    return p - bp * q, b
-
-
-@pytest.mark.parametrize("pop_reg", [None, "inverse_sqrt"])
-@pytest.mark.parametrize("alpha", [0.0, 0.5])
-@pytest.mark.parametrize("n_rated", [4, 30])
-def test_recurrence_and_fixed_point_equal_the_item_half_step(pop_reg, alpha, n_rated):
-    """T applications of OracleALS.item_step to a new column (its graph row, lambda_v_i and lambda_bi_i set as the
-    fit would) equal the recurrence, and their limit is the bordered solve."""
-    k, m, n = 6, 50, 20                                  # n fitted items + the new column n
-    rng = np.random.default_rng(n_rated + int(alpha * 10) + (pop_reg is not None))
-    raters = np.sort(rng.permutation(m)[:n_rated])
-    vals = rng.integers(1, 11, n_rated) * 0.5
-    rt = ratings_from_coo(raters, np.full(n_rated, n), vals, (m, n + 1))
-    o = OracleALS(OracleConfig(n_factors=k, n_iters=1, lambda_u=1.0, lambda_v=3.0, pop_reg_mode=pop_reg,
-                               lambda_bu=1.0, lambda_bi=2.0, alpha=alpha, sim={"feature_name": "x", "topk": 5}))
-    o.U, o.b_u, o.mu = rng.normal(size=(m, k)), rng.normal(scale=0.3, size=m), 3.2
-    o.V = np.vstack([rng.normal(size=(n, k)), np.zeros((1, k))])
-    o.b_i = np.zeros(n + 1)
-    nb_idx = np.array([2, 5, 11, 17])
-    nb_val = np.array([0.9, 0.4, 0.7, 0.05])
-    ptr = np.zeros(n + 2, np.int64)
-    ptr[n + 1] = nb_idx.size
-    o.S_csr, o.use_graph = (ptr, nb_idx, nb_val), alpha > 0
-    o.D = np.zeros(n + 1)
-    o.D[n] = nb_val.sum()
-    o.lambda_v_i = o.item_reg(np.full(n + 1, float(n_rated)))
-    o.lambda_bi_i = np.full(n + 1, o.lambda_bi)
-    args = (o.U, o.b_u, o.mu, o.V[:n], raters, vals, nb_idx, nb_val, 3.0, pop_reg is not None, 2.0, alpha)
-    for T in range(1, 6):
-        o.item_step(rt, cols=[n])
-        v, b = fold_item_reference(*args, T)
-        np.testing.assert_allclose(v, o.V[n], rtol=1e-10, atol=1e-12)
-        np.testing.assert_allclose(b, o.b_i[n], rtol=1e-10, atol=1e-12)
-    v, b = fold_item_reference(*args, 0)
-    lam = o.lambda_v_i[n] + EPS + alpha * o.D[n]
-    Us = o.U[raters]
-    M = np.block([[Us.T @ Us + lam * np.eye(k), Us.sum(axis=0)[:, None]],
-                  [Us.sum(axis=0)[None, :], np.array([[n_rated + 2.0 + EPS]])]])
-    rhs = np.append(Us.T @ (vals - o.mu - o.b_u[raters]) + alpha * (nb_val @ o.V[nb_idx]),
-                    (vals - o.mu - o.b_u[raters]).sum())
-    x = np.linalg.solve(M, rhs)
-    np.testing.assert_allclose(v, x[:k], rtol=1e-10, atol=1e-12)
-    np.testing.assert_allclose(b, x[k], rtol=1e-10, atol=1e-12)
-    for _ in range(300):
-        o.item_step(rt, cols=[n])
-    np.testing.assert_allclose(o.V[n], x[:k], rtol=1e-8, atol=1e-10)
-    np.testing.assert_allclose(o.b_i[n], x[k], rtol=1e-8, atol=1e-10)
-
-
 @pytest.mark.parametrize("pop_reg", [False, True])
 @pytest.mark.parametrize("alpha", [0.0, 0.5])
 def test_zero_rating_item_is_the_graph_mean(pop_reg, alpha):
@@ -110,8 +41,8 @@ def test_zero_rating_item_is_the_graph_mean(pop_reg, alpha):
     nb_idx, nb_val = np.array([1, 4, 9]), np.array([0.5, 0.25, 0.8])
     lam = (3.0 if pop_reg else 3.0) + EPS + alpha * nb_val.sum()      # lambda_v / sqrt(0 + 1) = lambda_v
     for T in (0, 1, 4):
-        v, b = fold_item_reference(np.zeros((2, 5)), np.zeros(2), 3.0, V, np.zeros(0, np.int64), np.zeros(0),
-                                   nb_idx, nb_val, 3.0, pop_reg, 2.0, alpha, T)
+        v, b = fold_in_item(np.zeros((2, 5)), np.zeros(2), 3.0, V, np.zeros(0, np.int64), np.zeros(0), nb_idx, nb_val,
+                            3.0, pop_reg, 2.0, alpha, T)
         np.testing.assert_allclose(v, alpha * (nb_val @ V[nb_idx]) / lam, rtol=1e-13, atol=0)
         assert b == 0.0
 

@@ -15,9 +15,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests import mmr_ref
-from tests.common import Golden
-from tests.test_gpu_kernels import _record_margins
-from tests.test_gpu_recommend import _env, _factors, _model_for
+from tests.common import Golden, model_for
+from tests.gpu_common import env, factors, record_margins, upload
 
 N_ITEMS, B = 1003, 43
 
@@ -33,8 +32,8 @@ def _setup(k, pool):
     """Random factors and every row's top-`pool` list (als_recommend_topk, nothing seen), made once per (k, pool):
     (f, Z float64 [n, k'], cand_val fp32 [B, pool], cand_idx int32 [B, pool]) - device tensors, never changed."""
     if (k, pool) not in _POOLS:
-        torch, layout, be, dev = _env()
-        f = _factors(torch, layout, dev, B, N_ITEMS, k, seed=7 * k + 1)
+        torch, layout, be, dev = env().short
+        f = factors(torch, layout, dev, B, N_ITEMS, k, seed=7 * k + 1)
         tv = torch.empty(B, pool, dtype=torch.float32, device=dev)
         ti = torch.empty(B, pool, dtype=torch.int32, device=dev)
         tc = torch.empty(B, dtype=torch.int32, device=dev)
@@ -48,7 +47,7 @@ def _setup(k, pool):
 
 def _rerank(f, n, cand_val, cand_idx, lam, N, ild=True):
     """als_mmr_rerank on device tensors -> numpy (top_val, top_idx, top_cnt, top_ild or None)."""
-    torch, _, be, dev = _env()
+    torch, _, be, dev = env().short
     Bn = cand_idx.shape[0]
     tv = torch.full((Bn, N), 7.0, dtype=torch.float32, device=dev)
     ti = torch.full((Bn, N), 7, dtype=torch.int32, device=dev)
@@ -60,8 +59,7 @@ def _rerank(f, n, cand_val, cand_idx, lam, N, ild=True):
 
 
 def _dev(a):
-    torch, _, _, dev = _env()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return upload(a, env().dev)
 
 
 def _follow(Z64, n, cv, ci, lam, N, got, tol):
@@ -119,15 +117,15 @@ def test_every_pick_is_the_float64_best_given_the_kernels_own_path(k, lam):
         worst = max(worst, _follow(Z64, N_ITEMS, cv.cpu().numpy(), ci.cpu().numpy(), lam, N, got, TOL(k)))
         assert (got[1][:, 0] == ci.cpu().numpy()[:, 0]).all()
     print(f"k={k} lambda={lam}: largest shortfall {worst:.3e}, tol {TOL(k):.3e}")
-    _record_margins(f"mmr_rerank k={k} lambda={lam}", {"shortfall": worst, "tol": TOL(k)})
+    record_margins(f"mmr_rerank k={k} lambda={lam}", {"shortfall": worst, "tol": TOL(k)})
 
 
 # ------------------------------------------------------------------------------------------ 3. exact ties
 @pytest.mark.parametrize("lam", [0.0, 0.5, 1.0])
 def test_equal_objectives_go_to_the_lower_pool_position(lam):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     k, pool = 24, 128
-    f = dict(_factors(torch, layout, dev, B, N_ITEMS, k, seed=99))
+    f = dict(factors(torch, layout, dev, B, N_ITEMS, k, seed=99))
     Z = f["Z"].cpu().numpy()
     twins = [[10, 20, 30, 40], [500, 77, 900, 3, 650]]                  # ids with identical rows
     for grp in twins:
@@ -159,9 +157,9 @@ def test_equal_objectives_go_to_the_lower_pool_position(lam):
 
 # ------------------------------------------------------------------------------------------ 4. clusters
 def test_diversity_spreads_a_list_over_clusters():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     k, pool, N, nc = 64, 64, 8, 8
-    f = dict(_factors(torch, layout, dev, B, N_ITEMS, k, seed=4))
+    f = dict(factors(torch, layout, dev, B, N_ITEMS, k, seed=4))
     rng = np.random.default_rng(8)
     centres = rng.normal(size=(nc, k))
     Z = np.zeros((N_ITEMS, f["ld"]), np.float32)
@@ -213,7 +211,7 @@ def test_short_and_degenerate_pools(pool):
         assert not np.isnan(tl[(tc >= 2)]).any() and not np.isnan(tv).any()
         if lam == 0.5:                                                  # rel = 0: the first pick is position 0
             assert ti[4, 0] == ci[4, 0]
-    torch, _, be, dev = _env()
+    torch, _, be, dev = env().short
     ild = torch.empty(B, dtype=torch.float32, device=dev)
     be.list_diversity(k=k, ld=f["ld"], n=N_ITEMS, Z=f["Z"], idx=_dev(ci), ild=ild)
     want = mmr_ref.list_diversity(Z.astype(np.float64), N_ITEMS, ci)
@@ -234,11 +232,11 @@ def test_two_runs_are_bitwise_equal(k, pool):
 
 # ------------------------------------------------------------------------------------------ 7. end to end
 def test_model_level_calls():
-    _env()
+    env()
     from collaborative_filtering_amd.serving import FoldedItems
     g = Golden("g4_feat_uw5")
     r, c, v = g.train
-    model = _model_for(g, device="cuda:0")
+    model = model_for(g, device="cuda:0")
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"], verbose=0)
     model._eng.REC_BATCH = 16
     ft = g.features
@@ -291,7 +289,7 @@ def test_model_level_calls():
 
 # ------------------------------------------------------------------------------------------ 8. bad arguments
 def test_bad_arguments_return_the_documented_status():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     k, pool, N = 64, 40, 10

@@ -1,6 +1,7 @@
 """K11 (GPU): explanations (csrc/explain.hip, als_explain), ALS.explain / explain_new.
 
-The kernel is checked against a float64 numpy oracle built from the same fp32 Z, b_i, mu and lambda values.  The
+The kernel is checked against the float64 contract in tests/serving_ref.py (`explain_pair`) on the same fp32 Z, b_i,
+mu and lambda values.  The
 outputs are fp64, so the expected error is cond(A) * 1e-16 - the rounding of two different fp64 solution paths
 (Cholesky in the kernel, LU in numpy) - not an fp32 rounding.  Errors are relative to
 max(1, max_j |contribution[j]|) of the (row, target) (weights: max(1, max_j |weight[j]|); leverage and b_u: to
@@ -10,46 +11,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import serving_ref as ref
+from tests.gpu_common import csr_rows, env, item_table, record_margins, upload
+from tests.serving_ref import EPS
+
 pytestmark = pytest.mark.gpu
 
-EPS = 1e-10
 MU = 3.5
-
-
-def _env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
-    from collaborative_filtering_amd import layout
-    from collaborative_filtering_amd.backend import HipBackend
-    dev = torch.device("cuda", 0)
-    return torch, layout, HipBackend(dev), dev
-
-
-def _table(torch, layout, dev, n, k, seed, scale=0.5):
-    ld = layout.padded_k(k)
-    rng = np.random.default_rng(seed)
-    Z = np.zeros((n, ld), np.float32)
-    Z[:, :k] = rng.normal(scale=scale, size=(n, k))
-    bi = rng.normal(scale=0.3, size=n).astype(np.float32)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return dict(ld=ld, Z=Z, b_i=bi, Zd=t(Z), bid=t(bi), mud=torch.tensor([MU], dtype=torch.float64, device=dev))
-
-
-def _rows(lengths, n, seed):
-    rng = np.random.default_rng(seed)
-    cols = [np.sort(rng.permutation(n)[:L]) for L in lengths]
-    indptr = np.zeros(len(lengths) + 1, np.int64)
-    indptr[1:] = np.cumsum(lengths)
-    indices = np.concatenate(cols).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
-    vals = (rng.integers(1, 11, size=indices.size) * 0.5).astype(np.float32)
-    return indptr, indices, vals
 
 
 def _run(torch, be, dev, t, k, indptr, indices, vals, n, lam_u, lam_bu, T, tptr, titems, M, largest, rows=None):
     """One als_explain launch; every output buffer is poisoned first."""
     W, P = tptr.size - 1, titems.size
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d = lambda a: upload(a, dev)                    # noqa: E731
     nan64 = lambda *s: torch.full(s, float("nan"), dtype=torch.float64, device=dev)
     o = dict(score=nan64(P), latent=nan64(P), leverage=nan64(P), top_contrib=nan64(P, M), top_weight=nan64(P, M),
              b_u_out=nan64(W), top_item=torch.full((P, M), -7, dtype=torch.int32, device=dev),
@@ -66,33 +40,8 @@ def _run(torch, be, dev, t, k, indptr, indices, vals, n, lam_u, lam_bu, T, tptr,
 
 
 def _oracle_row(Z, b_i, lam_u, lam_bu, idx, vals, k, T, targets):
-    """float64 contract for one row: dict with b_u, and per target score / latent / leverage and the full weight /
-    contribution vectors over the row's ratings."""
-    lam = float(np.float32(lam_u)) + EPS
-    Zs = Z[idx, :k].astype(np.float64)
-    res = vals.astype(np.float64) - MU - b_i[idx].astype(np.float64)
-    A = Zs.T @ Zs + lam * np.eye(k)
-    b = bprev = 0.0
-    if idx.size:
-        g, h, s = Zs.T @ res, Zs.sum(axis=0), res.sum()
-        d = idx.size + float(np.float32(lam_bu)) + EPS
-        p, q = np.linalg.solve(A, g), np.linalg.solve(A, h)
-        if T == 0:
-            M = np.zeros((k + 1, k + 1))
-            M[:k, :k], M[:k, k], M[k, :k], M[k, k] = A, h, h, d
-            b = bprev = np.linalg.solve(M, np.append(g, s))[k]
-        else:
-            for _ in range(T):
-                bprev = b
-                b = (s - h @ p + b * (h @ q)) / d
-    rho = res - bprev
-    Zt = Z[targets, :k].astype(np.float64)
-    Wt = np.linalg.solve(A, Zt.T).T
-    weights = Wt @ Zs.T
-    contrib = weights * rho[None, :]
-    latent = contrib.sum(axis=1)
-    return dict(b_u=b, weights=weights, contrib=contrib, latent=latent, leverage=(Wt * Zt).sum(axis=1),
-                score=MU + b + b_i[targets].astype(np.float64) + latent, cond=np.linalg.cond(A))
+    """`explain_row` of tests/serving_ref.py, the lambdas rounded to fp32 as the kernel reads them."""
+    return ref.explain_row(Z, b_i, MU, float(np.float32(lam_u)), float(np.float32(lam_bu)), idx, vals, k, T, targets)
 
 
 def _targets(indptr, indices, n, seed):
@@ -136,19 +85,20 @@ def _check_lists(out, p, orc, j, idx, M, largest, tol):
 # relative to the scales in the module docstring; leverage relative to itself), and the bounds = ~10x these:
 #   lambda_u = 5:     values 6.3e-15, leverage 7.0e-15, b_u 1.7e-15          -> 7e-14   (cond(A) <= 32)
 #   lambda_u = 1e-4:  values 2.8e-10, leverage 2.8e-11, b_u 1.3e-12          -> 3e-9    (cond(A) <= 1.1e6)
-# i.e. a few hundred cond(A) * 2^-52 at k = 160, as two fp64 factorisations of the same A differ.
+# i.e. a few hundred cond(A) * 2^-52 at k = 160, as two fp64 factorisations of the same A differ.  The figures of
+# every case are recorded under ALS_RECORD_MARGINS (profiles/serving_kernel_test_margins.json).
 TOL = {5.0: 7e-14, 1e-4: 3e-9}
 
 
 @pytest.mark.parametrize("k", [1, 8, 16, 33, 50, 64, 80, 128, 150, 160])
 @pytest.mark.parametrize("lam_u", [5.0, 1e-4])
 def test_kernel_against_float64_oracle(k, lam_u):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n = 4600
     tol = TOL[lam_u]
-    t = _table(torch, layout, dev, n, k, seed=k)
+    t = item_table(torch, layout, dev, n, k, seed=k, mu=MU)
     lengths = [0, 1, max(k // 2, 1), k, 300, 4500]
-    indptr, indices, vals = _rows(lengths, n, seed=k + 1)
+    indptr, indices, vals = csr_rows(lengths, n, seed=k + 1)
     W = len(lengths)
     tg5 = _targets(indptr, indices, n, seed=k + 2)
     worst = dict(val=0.0, lev=0.0, b=0.0, cond=0.0)
@@ -186,16 +136,17 @@ def test_kernel_against_float64_oracle(k, lam_u):
                                                (z0 * z0).sum(axis=1) / (float(np.float32(lam_u)) + EPS), rtol=1e-14)
     print(f"explain k={k} lambda_u={lam_u}: max err values {worst['val']:.2e} leverage {worst['lev']:.2e} "
           f"b_u {worst['b']:.2e} cond(A) <= {worst['cond']:.2e}")
+    record_margins(f"explain[k={k},lambda_u={lam_u}]", {name: float(worst[name]) for name in ("val", "lev", "b")})
     assert worst["val"] < tol and worst["lev"] < tol and worst["b"] < tol, worst
 
 
 def test_repeated_target_and_single_target_are_bitwise_the_block_results():
     """Targets are served in blocks that share one pass over the row: a repeated target, and the same target
     asked for alone, give the same bits."""
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n, k = 4600, 50
-    t = _table(torch, layout, dev, n, k, seed=50)
-    indptr, indices, vals = _rows([0, 1, 25, 50, 300, 4500], n, seed=51)
+    t = item_table(torch, layout, dev, n, k, seed=50, mu=MU)
+    indptr, indices, vals = csr_rows([0, 1, 25, 50, 300, 4500], n, seed=51)
     tg5 = _targets(indptr, indices, n, seed=52)
     W = indptr.size - 1
     o5 = _run(torch, be, dev, t, k, indptr, indices, vals, n, 5.0, 3.0, 0, np.arange(W + 1, dtype=np.int64) * 5,
@@ -211,13 +162,13 @@ def test_repeated_target_and_single_target_are_bitwise_the_block_results():
 
 def test_a_result_depends_on_its_row_and_target_alone():
     """Alone, inside a batch of 1000, with the targets permuted, through `rows` or with the CSR pre-gathered."""
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n, k = 3000, 64
-    t = _table(torch, layout, dev, n, k, seed=11)
+    t = item_table(torch, layout, dev, n, k, seed=11, mu=MU)
     rng = np.random.default_rng(12)
     lengths = rng.integers(0, 200, size=1000)
     lengths[[0, 500, 999]] = [150, 700, 64]
-    indptr, indices, vals = _rows(lengths.tolist(), n, seed=13)
+    indptr, indices, vals = csr_rows(lengths.tolist(), n, seed=13)
     nt = rng.integers(1, 8, size=1000)
     tptr = np.zeros(1001, np.int64)
     tptr[1:] = np.cumsum(nt)
@@ -258,9 +209,9 @@ def test_a_result_depends_on_its_row_and_target_alone():
 
 
 def test_nan_in_Z_sets_the_status_word():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n, k = 300, 16
-    t = _table(torch, layout, dev, n, k, seed=7)
+    t = item_table(torch, layout, dev, n, k, seed=7, mu=MU)
     t["Z"][17, 3] = np.nan
     t["Zd"] = torch.from_numpy(t["Z"]).to(dev)
     indptr = np.array([0, 2, 4, 5], np.int64)
@@ -271,7 +222,7 @@ def test_nan_in_Z_sets_the_status_word():
 
 
 def test_c_abi_status_codes():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     p = _hip.ExplainParams()
@@ -318,7 +269,7 @@ def _user_rows(r, c, v, users):
 
 
 def test_model_explain_equals_explain_new_on_the_training_rows():
-    _env()
+    env()
     model, feats, r, c, v, m, n = _fit_with_features()
     rng = np.random.default_rng(3)
     users = np.concatenate([rng.integers(0, m, size=60), [5, 5, 17, 17]])      # user 5 has no ratings
@@ -350,7 +301,7 @@ def test_explain_new_agrees_with_fold_in_and_recommend_new():
     separates them is the fp32 rounding of fold-in's outputs and of the predict epilogue.
     Observed on an MI355X: |b_u - fold_in b| 9.0e-9 (relative to max(1, max |b|)), |score - recommend_new score|
     9.3e-7 (scores of size ~4, fp32 accumulation over k = 24 and three fp32 additions); bounds 10x."""
-    _env()
+    env()
     model, feats, r, c, v, m, n = _fit_with_features()
     users = np.arange(0, 120)
     R_new = _user_rows(r, c, v, users)
@@ -365,10 +316,10 @@ def test_explain_new_agrees_with_fold_in_and_recommend_new():
 
 def test_full_size_properties():
     """Z for 100K items at k = 64, 4096 rows of ~100 ratings from the synth distribution, one target each."""
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from tests.synth import make_ratings
     NI, k, B, lam_u = 100_000, 64, 4096, 5.0
-    t = _table(torch, layout, dev, NI, k, seed=3, scale=0.3)
+    t = item_table(torch, layout, dev, NI, k, seed=3, scale=0.3, mu=MU)
     r, c, v = make_ratings(B, NI, 100 * B, seed=B, user_exp=0.0)
     ptr = np.zeros(B + 1, np.int64)
     np.add.at(ptr, r + 1, 1)

@@ -1,82 +1,32 @@
 """K9 (GPU): fold-in of users outside the fit (csrc/fold_in.hip, als_fold_in), ALS.fold_in / recommend_new and
 cv.fold_in_ranking_at_k.
 
-The kernel is checked against a float64 oracle built from the same fp32 Z, b_i, mu and lambda values: the expected
-error is the fp32 rounding of the outputs.  recommend_new is checked exactly (==) against predict-epilogue scores of
-the folded table."""
+The kernel is checked against the float64 contract in tests/serving_ref.py (`fold_in_user`) on the same fp32 Z, b_i,
+mu and lambda values: the expected error is the fp32 rounding of the outputs.  recommend_new is checked exactly (==)
+against predict-epilogue scores of the folded table."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import serving_ref as ref
+from tests.gpu_common import csr_rows, env, item_table, record_margins, upload
+
 pytestmark = pytest.mark.gpu
-
-EPS = 1e-10
-
-
-def _env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
-    from collaborative_filtering_amd import layout
-    from collaborative_filtering_amd.backend import HipBackend
-    dev = torch.device("cuda", 0)
-    return torch, layout, HipBackend(dev), dev
 
 
 def _oracle(Z, b_i, mu, lam_u, lam_bu, indptr, indices, vals, k, T):
-    """float64 fold-in of every CSR row: T alternations of the user half-step from b = 0, or (T = 0) the bordered
-    solve."""
-    B = indptr.size - 1
-    U = np.zeros((B, k))
-    bu = np.zeros(B)
-    lam = float(np.float32(lam_u)) + EPS
-    for r in range(B):
-        idx = indices[indptr[r]: indptr[r + 1]]
-        if idx.size == 0:
-            continue
-        Zs = Z[idx, :k].astype(np.float64)
-        res = vals[indptr[r]: indptr[r + 1]].astype(np.float64) - mu - b_i[idx].astype(np.float64)
-        A = Zs.T @ Zs + lam * np.eye(k)
-        g, h, s = Zs.T @ res, Zs.sum(axis=0), res.sum()
-        d = idx.size + float(np.float32(lam_bu)) + EPS
-        if T == 0:
-            M = np.zeros((k + 1, k + 1))
-            M[:k, :k], M[:k, k], M[k, :k], M[k, k] = A, h, h, d
-            x = np.linalg.solve(M, np.append(g, s))
-            U[r], bu[r] = x[:k], x[k]
-        else:
-            b = 0.0
-            for _ in range(T):
-                u = np.linalg.solve(A, g - b * h)
-                b = (s - h @ u) / d
-            U[r], bu[r] = u, b
-    return U, bu
-
-
-def _table(torch, layout, dev, n, k, seed):
-    ld = layout.padded_k(k)
-    rng = np.random.default_rng(seed)
-    Z = np.zeros((n, ld), np.float32)
-    Z[:, :k] = rng.normal(scale=0.5, size=(n, k))
-    bi = rng.normal(scale=0.3, size=n).astype(np.float32)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return dict(ld=ld, Z=Z, b_i=bi, Zd=t(Z), bid=t(bi), mud=torch.tensor([3.5], dtype=torch.float64, device=dev))
-
-
-def _rows(lengths, n, seed):
-    rng = np.random.default_rng(seed)
-    cols = [np.sort(rng.permutation(n)[:L]) for L in lengths]
-    indptr = np.zeros(len(lengths) + 1, np.int64)
-    indptr[1:] = np.cumsum(lengths)
-    indices = np.concatenate(cols).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
-    vals = (rng.integers(1, 11, size=indices.size) * 0.5).astype(np.float32)
-    return indptr, indices, vals
+    """`fold_in_user` of tests/serving_ref.py on every CSR row, the lambdas rounded to fp32 as the kernel reads them:
+    T alternations of the user half-step from b = 0, or (T = 0) their fixed point."""
+    f = lambda x: float(np.float32(x))              # noqa: E731
+    rows = [ref.fold_in_user(Z, b_i, mu, f(lam_u), f(lam_bu), indices[indptr[r]: indptr[r + 1]],
+                             vals[indptr[r]: indptr[r + 1]], k, T) for r in range(indptr.size - 1)]
+    return np.array([u for u, _ in rows]), np.array([b for _, b in rows])
 
 
 def _run(torch, be, dev, t, k, indptr, indices, vals, n, lam_u, lam_bu, T):
     B = indptr.size - 1
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d = lambda a: upload(a, dev)                    # noqa: E731
     U = torch.full((B, t["ld"]), float("nan"), dtype=torch.float32, device=dev)
     b = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -95,11 +45,12 @@ TOL = 5e-7
 @pytest.mark.parametrize("k", [1, 8, 16, 33, 50, 64, 80, 128, 150, 160])
 @pytest.mark.parametrize("lam_u", [5.0, 1e-4])
 def test_kernel_against_float64_oracle(k, lam_u):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n = 4600
-    t = _table(torch, layout, dev, n, k, seed=k)
+    t = item_table(torch, layout, dev, n, k, seed=k)
     lengths = [0, 1, max(k // 2, 1), k, 300, 4500]
-    indptr, indices, vals = _rows(lengths, n, seed=k + 1)
+    indptr, indices, vals = csr_rows(lengths, n, seed=k + 1)
+    worst = {"u": 0.0, "b": 0.0}
     for T in (1, 3, 0):
         U, b, st = _run(torch, be, dev, t, k, indptr, indices, vals, n, lam_u, 3.0, T)
         assert st == 0
@@ -108,15 +59,17 @@ def test_kernel_against_float64_oracle(k, lam_u):
         scale = np.maximum(1.0, np.abs(Uo).max(axis=1))
         err_u = (np.abs(U[:, :k] - Uo).max(axis=1) / scale).max()
         err_b = (np.abs(b - bo) / np.maximum(1.0, np.abs(bo))).max()
+        worst = {"u": max(worst["u"], float(err_u)), "b": max(worst["b"], float(err_b))}
         assert err_u < TOL and err_b < TOL, (T, err_u, err_b)
         assert (U[0] == 0).all() and b[0] == 0          # no ratings: u = 0, b = 0
+    record_margins(f"fold_in[k={k},lambda_u={lam_u}]", worst)
 
 
 def test_many_sweeps_reach_the_fixed_point():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n, k = 2000, 64
-    t = _table(torch, layout, dev, n, k, seed=5)
-    indptr, indices, vals = _rows([3, 40, 64, 200], n, seed=6)
+    t = item_table(torch, layout, dev, n, k, seed=5)
+    indptr, indices, vals = csr_rows([3, 40, 64, 200], n, seed=6)
     U0, b0, _ = _run(torch, be, dev, t, k, indptr, indices, vals, n, 2.0, 1.0, 0)
     U5, b5, _ = _run(torch, be, dev, t, k, indptr, indices, vals, n, 2.0, 1.0, 500)
     assert np.abs(U5 - U0).max() < 1e-6 * max(1.0, np.abs(U0).max())
@@ -126,9 +79,9 @@ def test_many_sweeps_reach_the_fixed_point():
 
 
 def test_nan_in_Z_sets_the_status_word():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     n, k = 300, 16
-    t = _table(torch, layout, dev, n, k, seed=7)
+    t = item_table(torch, layout, dev, n, k, seed=7)
     t["Z"][17, 3] = np.nan
     t["Zd"] = torch.from_numpy(t["Z"]).to(dev)
     indptr = np.array([0, 2, 4, 5], np.int64)
@@ -139,7 +92,7 @@ def test_nan_in_Z_sets_the_status_word():
 
 
 def test_c_abi_status_codes():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     p = _hip.FoldInParams()
@@ -233,19 +186,6 @@ def test_empty_batch(fitted):
     assert items.shape == scores.shape == (0, 5)
 
 
-def _expected(P, seen_rows, N):
-    out_i = np.full((P.shape[0], N), -1, np.int64)
-    out_s = np.full((P.shape[0], N), -np.inf)
-    for b in range(P.shape[0]):
-        keep = np.ones(P.shape[1], bool)
-        keep[seen_rows[b]] = False
-        items = np.nonzero(keep)[0]
-        o = np.lexsort((items, -P[b, items]))[:N]
-        out_i[b, : o.size] = items[o]
-        out_s[b, : o.size] = P[b, items[o]]
-    return out_i, out_s
-
-
 @pytest.mark.parametrize("N", [1, 10, 128])
 @pytest.mark.parametrize("exclude_seen", [True, False])
 def test_recommend_new_against_the_masked_dense_sort(fitted, N, exclude_seen):
@@ -263,7 +203,7 @@ def test_recommend_new_against_the_masked_dense_sort(fitted, N, exclude_seen):
         P = P.cpu().numpy().astype(np.float64)
     seen = [ix[ip[r]: ip[r + 1]] if exclude_seen else np.zeros(0, np.int64) for r in range(R.shape[0])]
     items, scores = model.recommend_new(R, N, features=features, exclude_seen=exclude_seen)
-    ei, es = _expected(P, seen, N)
+    es, ei, _ = ref.topn_batch(P, seen, None, N)
     assert (items == ei).all() and (scores == es).all()
     Uf, bf = model.fold_in(R, features=features)
     assert (Uf == U[:, :K].cpu().numpy()).all() and (bf == b.cpu().numpy()).all()

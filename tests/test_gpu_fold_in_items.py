@@ -1,55 +1,33 @@
 """K9b (GPU): fold-in of items outside the fit (csrc/fold_in_items.hip, als_fold_in_items), the new items' graph
 rows, ALS.fold_in_items / predict_new_items / recommend(new_items=...) and cv.cold_item_rmse.
 
-The kernel is checked against a float64 oracle built from the same fp32 U, b_u, V, graph weights, mu and lambda
-values: the expected error is the fp32 rounding of the outputs.  Graph rows, predictions and recommendations are
-checked exactly (==) against the device's own fp32 cosines and predict-epilogue scores."""
+The kernel is checked against the float64 contract in tests/serving_ref.py (`fold_in_item`) on the same fp32 U, b_u,
+V, graph weights, mu and lambda values: the expected error is the fp32 rounding of the outputs.  Graph rows,
+predictions and recommendations are checked exactly (==) against the device's own fp32 cosines and predict-epilogue
+scores."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import serving_ref
+from tests.gpu_common import csr_rows, env, record_margins, upload
+
 pytestmark = pytest.mark.gpu
-
-EPS = 1e-10
-
-
-def _env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
-    from collaborative_filtering_amd import layout
-    from collaborative_filtering_amd.backend import HipBackend
-    dev = torch.device("cuda", 0)
-    return torch, layout, HipBackend(dev), dev
 
 
 def _oracle(U, b_u, mu, V, lam_v, pop_reg, lam_bi, alpha, indptr, indices, vals, S, k, T):
-    """float64 item fold-in of every CSR row (the contract in include/als_hip.h)."""
+    """`fold_in_item` of tests/serving_ref.py on every CSR row (S: the rows' graph CSR or None), the parameters rounded
+    to fp32 as the kernel reads them."""
+    f = lambda x: float(np.float32(x))              # noqa: E731
     B = indptr.size - 1
     Vo, bo = np.zeros((B, k)), np.zeros(B)
-    f = lambda x: float(np.float32(x))              # noqa: E731  (the kernel reads fp32 parameters)
     for r in range(B):
-        idx = indices[indptr[r]: indptr[r + 1]]
-        n_i = idx.size
+        sl = slice(indptr[r], indptr[r + 1])
         sj = S[1][S[0][r]: S[0][r + 1]] if S is not None else np.zeros(0, np.int64)
-        sv = S[2][S[0][r]: S[0][r + 1]].astype(np.float64) if S is not None else np.zeros(0)
-        lv = f(lam_v) / np.sqrt(n_i + 1.0) if pop_reg else f(lam_v)
-        lam = lv + EPS + f(alpha) * sv.sum()
-        Us = U[idx, :k].astype(np.float64)
-        res = vals[indptr[r]: indptr[r + 1]].astype(np.float64) - mu - b_u[idx].astype(np.float64)
-        A = Us.T @ Us + lam * np.eye(k)
-        g = Us.T @ res + f(alpha) * (sv @ V[sj, :k].astype(np.float64))
-        h, s, d = Us.sum(axis=0), res.sum(), n_i + f(lam_bi) + EPS
-        p, q = np.linalg.solve(A, g), np.linalg.solve(A, h)
-        if T == 0:
-            b = (s - h @ p) / (d - h @ q)
-            Vo[r], bo[r] = p - b * q, b
-        else:
-            b = bp = 0.0
-            for _ in range(T):
-                bp, b = b, (s - h @ p + b * (h @ q)) / d
-            Vo[r], bo[r] = p - bp * q, b
+        sv = S[2][S[0][r]: S[0][r + 1]] if S is not None else np.zeros(0)
+        Vo[r], bo[r] = serving_ref.fold_in_item(U, b_u, mu, V[:, :k], indices[sl], vals[sl], sj, sv, f(lam_v), pop_reg,
+                                                f(lam_bi), f(alpha), T)
     return Vo, bo
 
 
@@ -64,23 +42,10 @@ def _tables(layout, m, n, k, seed):
     return ld, U, V, bu
 
 
-def _csr(lengths, ncols, seed, weights=False):
-    rng = np.random.default_rng(seed)
-    cols = [np.sort(rng.permutation(ncols)[:L]) for L in lengths]
-    indptr = np.zeros(len(lengths) + 1, np.int64)
-    indptr[1:] = np.cumsum(lengths)
-    indices = np.concatenate(cols).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
-    if weights:
-        vals = rng.uniform(0.05, 1.0, size=indices.size).astype(np.float32)
-    else:
-        vals = (rng.integers(1, 11, size=indices.size) * 0.5).astype(np.float32)
-    return indptr, indices, vals
-
-
 def _run(torch, be, dev, k, ld, U, bu, V, ratings, S, lam_v, pop_reg, lam_bi, alpha, T):
     indptr, indices, vals = ratings
     B = indptr.size - 1
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    d = lambda a: upload(a, dev)                                         # noqa: E731
     nz = lambda a, dt: a if a.size else np.zeros(1, dt)                  # noqa: E731
     Vout = torch.full((B, ld), float("nan"), dtype=torch.float32, device=dev)
     b = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
@@ -103,12 +68,12 @@ NEIGHBOURS = [0, 1, 50, 128]
 @pytest.mark.parametrize("k", [1, 8, 16, 33, 50, 64, 80, 128, 150, 160])
 @pytest.mark.parametrize("pop_reg,alpha", [(False, 0.5), (True, 0.5), (False, 0.0)])
 def test_kernel_against_float64_oracle(k, pop_reg, alpha):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n = 4600, 3000
     ld, U, V, bu = _tables(layout, m, n, k, seed=k)
     lengths = [L for L in RATERS(k) for _ in NEIGHBOURS]
-    ratings = _csr(lengths, m, seed=k + 1)
-    S = _csr(NEIGHBOURS * len(RATERS(k)), n, seed=k + 2, weights=True)
+    ratings = csr_rows(lengths, m, seed=k + 1)
+    S = csr_rows(NEIGHBOURS * len(RATERS(k)), n, seed=k + 2, weights=True)
     worst = []
     for T in (1, 3, 0):
         Vg, bg, st = _run(torch, be, dev, k, ld, U, bu, V, ratings, S, 4.0, pop_reg, 2.0, alpha, T)
@@ -124,13 +89,15 @@ def test_kernel_against_float64_oracle(k, pop_reg, alpha):
         if alpha == 0.0:
             assert (Vg[0] == 0).all()                              # no ratings, no graph: v = 0
     print(f"k={k} pop_reg={pop_reg} alpha={alpha} (T, err_v, err_b): {worst}")
+    record_margins(f"fold_in_items[k={k},pop_reg={pop_reg},alpha={alpha}]",
+                   {"v": float(max(w[1] for w in worst)), "b": float(max(w[2] for w in worst))})
 
 
 def test_no_graph_equals_an_empty_graph():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k = 500, 200, 32
     ld, U, V, bu = _tables(layout, m, n, k, seed=3)
-    ratings = _csr([0, 5, 40, 200], m, seed=4)
+    ratings = csr_rows([0, 5, 40, 200], m, seed=4)
     empty = (np.zeros(5, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
     a = _run(torch, be, dev, k, ld, U, bu, V, ratings, None, 2.0, False, 1.0, 0.5, 0)
     b = _run(torch, be, dev, k, ld, U, bu, V, ratings, empty, 2.0, False, 1.0, 0.5, 0)
@@ -138,7 +105,7 @@ def test_no_graph_equals_an_empty_graph():
 
 
 def test_nan_in_U_sets_the_status_word():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k = 300, 100, 16
     ld, U, V, bu = _tables(layout, m, n, k, seed=7)
     U[17, 3] = np.nan
@@ -148,7 +115,7 @@ def test_nan_in_U_sets_the_status_word():
 
 
 def test_c_abi_status_codes():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     p = _hip.FoldInItemsParams()
@@ -343,19 +310,6 @@ def test_predict_new_items_is_the_predict_epilogue(fitted):
         model.predict_new_items(folded, [M])
 
 
-def _expected(P, seen_rows, N):
-    out_i = np.full((P.shape[0], N), -1, np.int64)
-    out_s = np.full((P.shape[0], N), -np.inf)
-    for b in range(P.shape[0]):
-        keep = np.ones(P.shape[1], bool)
-        keep[seen_rows[b]] = False
-        items = np.nonzero(keep)[0]
-        o = np.lexsort((items, -P[b, items]))[:N]
-        out_i[b, : o.size] = items[o]
-        out_s[b, : o.size] = P[b, items[o]]
-    return out_i, out_s
-
-
 @pytest.mark.parametrize("N", [1, 10, 128])
 @pytest.mark.parametrize("exclude_seen", [True, False])
 def test_recommend_with_new_items_against_the_masked_dense_sort(fitted, N, exclude_seen):
@@ -372,7 +326,7 @@ def test_recommend_with_new_items_against_the_masked_dense_sort(fitted, N, exclu
         s = np.concatenate([tr_c[tr_r == u], N_FIT + np.nonzero(~np.isnan(C[:, u]))[0]]) if exclude_seen else []
         seen.append(np.asarray(s, np.int64))
     items, scores = model.recommend(users, N, features=ff, exclude_seen=exclude_seen, new_items=folded)
-    ei, es = _expected(P, seen, N)
+    es, ei, _ = serving_ref.topn_batch(P, seen, None, N)
     assert (items == ei).all() and (scores == es).all()
     if N == 128:
         assert (items >= N_FIT).any()                      # new items do compete

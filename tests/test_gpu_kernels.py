@@ -3,57 +3,18 @@ rows (nnz = 1, < k, >> k, > ALS_SPLIT_CHUNK so the split/finish path runs) and
 k in {1, 16, 32, 50, 64, 128}.  Calls go through ctypes -> libals_hip.so.  The W-step entry points
 (als_w_normal_equations, als_item_stats, als_item_stats_f64) have their own file, tests/test_gpu_w_step.py, with
 its reference in tests/w_step_ref.py (validated without a device by tests/test_w_step_ref_cpu.py)."""
-import os
-
 import numpy as np
 import pytest
 
+from tests.gpu_common import env, pad, random_side, record_margins
+
 pytestmark = pytest.mark.gpu
-
-
-def _env(gram="f16x2"):
-    solve_dtype = "float64" if gram == "f64" else "float32"      # "f64": ALS_GRAM_F64 (row_solve_f64.hip)
-    gram = "f16x2" if gram == "f64" else gram
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
-    from collaborative_filtering_amd import layout
-    from collaborative_filtering_amd.als import _side_to_dev, _tasks_to_dev
-    from collaborative_filtering_amd.backend import HipBackend
-    dev = torch.device("cuda", 0)
-    return torch, layout, _side_to_dev, _tasks_to_dev, HipBackend(dev, gram=gram, solve_dtype=solve_dtype), dev
-
-
-def _random_side(layout, nrows, ncols, lens, seed):
-    rng = np.random.default_rng(seed)
-    indptr = np.zeros(nrows + 1, dtype=np.int64)
-    indptr[1:] = np.cumsum(lens)
-    idx = np.concatenate([np.sort(rng.choice(ncols, size=l, replace=False)) for l in lens]).astype(np.int32) \
-        if sum(lens) else np.zeros(0, np.int32)
-    vals = (np.round(rng.uniform(0.5, 5.0, size=idx.size) * 2) / 2).astype(np.float32)
-    return layout.SparseSide(nrows, ncols, indptr, idx, vals)
-
-
-def _pad(A, ld, extra_rows=0):
-    out = np.zeros((A.shape[0] + extra_rows, ld), dtype=np.float32)
-    out[: A.shape[0], : A.shape[1]] = A
-    return out
-
-
-def _record_margins(key, worst):
-    """ALS_RECORD_MARGINS=<file>: append the observed errors of a kernel test (the tolerances are set from them)."""
-    path = os.environ.get("ALS_RECORD_MARGINS")
-    if path:
-        import json
-        data = json.load(open(path)) if os.path.exists(path) else {}
-        data[key] = worst
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
 
 
 @pytest.mark.parametrize("gram", ["f16x2", "f32", "f64"])
 @pytest.mark.parametrize("k", [1, 16, 32, 50, 64, 80, 96, 112, 128, 160])
 def test_row_solve_against_numpy(k, gram):
-    torch, layout, side_dev, tasks_dev, be, dev = _env(gram)
+    torch, layout, side_dev, tasks_dev, be, dev = env(gram)
     # Tolerances at about 10x the error observed on the MI355X over all k and row lengths of this test
     # (profiles/r03_kernel_test_margins.json, written by this test under ALS_RECORD_MARGINS=<file>), relative to
     # max|x| of the row / max|G|: fp32 solve x observed 6.8e-6 (f16x2) / 2.8e-6 (f32), bias 1.5e-7, Gram 7.3e-7
@@ -66,7 +27,7 @@ def test_row_solve_against_numpy(k, gram):
     ncols = 9000
     lens = [1, 2, 0, k // 2 + 1, k, 3 * k + 5, 700, 0, 4096, 4097, 8200 + k, 33, 64, 65, 5]
     nrows = len(lens)
-    side = _random_side(layout, nrows, ncols, lens, seed=k)
+    side = random_side(layout, nrows, ncols, lens, seed=k)
     rng = np.random.default_rng(100 + k)
     ld = layout.padded_k(k)
     F = rng.normal(scale=0.3, size=(ncols, k))
@@ -85,12 +46,12 @@ def test_row_solve_against_numpy(k, gram):
     gram = torch.zeros(nrows, ld, ld, dtype=f32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = torch.empty(t.nslots * be.slot_bytes(k) // 4, dtype=f32, device=dev)
-    be.row_solve(k=k, ld=ld, side=sd, F=torch.from_numpy(_pad(F, ld, 1)).to(dev), zero_row=ncols,
+    be.row_solve(k=k, ld=ld, side=sd, F=torch.from_numpy(pad(F, ld, 1)).to(dev), zero_row=ncols,
                  bias_self=torch.from_numpy(b_self.astype(np.float32)).to(dev),
                  bias_other=torch.from_numpy(b_other.astype(np.float32)).to(dev),
                  mu=torch.tensor([mu], dtype=torch.float64, device=dev), lam=0.0,
                  lam_row=torch.from_numpy(lam_row.astype(np.float32)).to(dev), lam_b=lam_b, lam_b_row=None,
-                 rhs_extra=torch.from_numpy(_pad(rhs_extra, ld)).to(dev),
+                 rhs_extra=torch.from_numpy(pad(rhs_extra, ld)).to(dev),
                  diag_extra=torch.from_numpy(diag_extra.astype(np.float32)).to(dev),
                  X_out=X_out, bias_out=bias_out, gram_out=gram, factor_out=None, rhs_out=None,
                  colsum_out=None, sumr_out=None, status=status, tasks=td, workspace=ws)
@@ -127,7 +88,7 @@ def test_row_solve_against_numpy(k, gram):
         worst["gram"] = max(worst["gram"], float(np.max(np.abs(Gr - ref)[lower_block]) / max(np.max(np.abs(ref)), 1e-6)))
         np.testing.assert_allclose(Gr[lower_block], ref[lower_block], rtol=gr,
                                    atol=ga * max(np.max(np.abs(ref)), 1e-6))
-    _record_margins(f"row_solve k={k} {gram_name}", worst)
+    record_margins(f"row_solve k={k} {gram_name}", worst)
 
 
 @pytest.mark.parametrize("k", [50, 64, 120, 128])
@@ -136,12 +97,12 @@ def test_row_solve_presplit_operands_equal_the_in_kernel_split(k):
     Gram BIT FOR BIT (same terms, same products, same order); the right-hand side and the column sums come from the
     matrix cores instead of the vector unit, so x and the bias agree to rounding (every row class: 1 rating, < k, k,
     long, split rows with partial slots, empty rows untouched)."""
-    torch, layout, side_dev, tasks_dev, _, dev = _env()
+    torch, layout, side_dev, tasks_dev, _, dev = env()
     from collaborative_filtering_amd.backend import HipBackend
     ncols = 9000
     lens = [1, 2, 0, k // 2 + 1, k, 3 * k + 5, 700, 0, 4096, 4097, 8200 + k, 33, 64, 65, 5, 511, 513]
     nrows = len(lens)
-    side = _random_side(layout, nrows, ncols, lens, seed=7 * k)
+    side = random_side(layout, nrows, ncols, lens, seed=7 * k)
     rng = np.random.default_rng(9 + k)
     ld = layout.padded_k(k)
     F = rng.normal(scale=0.3, size=(ncols, k)) * 10.0 ** rng.uniform(-2, 0, size=(ncols, 1))      # two decades of row norms
@@ -159,7 +120,7 @@ def test_row_solve_presplit_operands_equal_the_in_kernel_split(k):
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         ws = torch.empty(t.nslots * be.slot_bytes(k) // 4, dtype=f32, device=dev)
         tt = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)       # noqa: E731
-        be.row_solve(k=k, ld=ld, side=sd, F=tt(_pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
+        be.row_solve(k=k, ld=ld, side=sd, F=tt(pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
                      mu=torch.tensor([3.3], dtype=torch.float64, device=dev), lam=2.5, lam_row=None, lam_b=1.7,
                      lam_b_row=None, rhs_extra=None, diag_extra=None, X_out=X_out, bias_out=bias_out, gram_out=gram,
                      factor_out=None, rhs_out=None, colsum_out=None, sumr_out=None, status=status, tasks=td, workspace=ws)
@@ -181,11 +142,11 @@ def test_row_solve_f64_small_lambda(k):
     """ALS_GRAM_F64 at lambda = 1e-4 with rows shorter than k (cond ~ 1/lambda, where the fp32 kernels lose the
     null-space components): the fp64 kernel returns numpy's float64 solution up to the fp32 rounding of the
     stored x, and the closed-form residual statistics equal the directly evaluated sums."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env("f64")
+    torch, layout, side_dev, tasks_dev, be, dev = env("f64")
     ncols = 5000
     lens = [1, 3, k // 2 + 1, max(k - 1, 1), k, k + 7, 300, 4100, 17, 2]
     nrows = len(lens)
-    side = _random_side(layout, nrows, ncols, lens, seed=900 + k)
+    side = random_side(layout, nrows, ncols, lens, seed=900 + k)
     rng = np.random.default_rng(950 + k)
     ld = layout.padded_k(k)
     F = rng.normal(scale=0.3, size=(ncols, k)).astype(np.float32)
@@ -201,7 +162,7 @@ def test_row_solve_f64_small_lambda(k):
     stat = torch.zeros(nrows, 2, dtype=f32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = torch.empty(max(t.nslots, 1) * be.slot_bytes(k) // 4, dtype=f32, device=dev)
-    be.row_solve(k=k, ld=ld, side=sd, F=tt(_pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
+    be.row_solve(k=k, ld=ld, side=sd, F=tt(pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
                  mu=torch.tensor([mu], dtype=torch.float64, device=dev), lam=lam, lam_row=None, lam_b=lam_b,
                  lam_b_row=None, rhs_extra=None, diag_extra=None, X_out=X_out, bias_out=bias_out, gram_out=None,
                  factor_out=None, rhs_out=None, colsum_out=None, sumr_out=None, status=status, tasks=td, workspace=ws,
@@ -233,12 +194,12 @@ def test_row_solve_f64_small_lambda(k):
 @pytest.mark.parametrize("k", [16, 64, 80, 96, 128, 160])
 def test_factor_mode_and_gs_level(k, gram):
     """factor-only als_row_solve + als_gs_sweep on one level == direct solve with the graph term."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env(gram)
+    torch, layout, side_dev, tasks_dev, be, dev = env(gram)
     ncols, nrows = 6000, 40
     rng = np.random.default_rng(7 + k)
     lens = list(rng.integers(1, 300, size=nrows))
     lens[3] = 5000
-    side = _random_side(layout, nrows, ncols, lens, seed=3 * k)
+    side = random_side(layout, nrows, ncols, lens, seed=3 * k)
     ld = layout.padded_k(k)
     F = rng.normal(scale=0.3, size=(ncols, k)).astype(np.float32)
     Vold = rng.normal(scale=0.3, size=(nrows, k)).astype(np.float32)
@@ -269,11 +230,11 @@ def test_factor_mode_and_gs_level(k, gram):
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = torch.empty(max(t.nslots, 1) * be.slot_bytes(k) // 4, dtype=f32, device=dev)
     mu_t = torch.tensor([mu], dtype=torch.float64, device=dev)
-    be.row_solve(k=k, ld=ld, side=sd, F=tt(_pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
+    be.row_solve(k=k, ld=ld, side=sd, F=tt(pad(F, ld, 1)), zero_row=ncols, bias_self=tt(b_self), bias_other=tt(b_other),
                  mu=mu_t, lam=0.0, lam_row=tt(lam_row), lam_b=lam_b, lam_b_row=None, rhs_extra=None,
                  diag_extra=tt(alpha * D), X_out=None, bias_out=None, gram_out=None, factor_out=factor,
                  rhs_out=rhs, colsum_out=cs, sumr_out=sumr, status=status, tasks=td, workspace=ws)
-    V = tt(_pad(Vold, ld))
+    V = tt(pad(Vold, ld))
     bias = tt(b_self.copy())
     be.gs_level(k=k, ld=ld, items=tt(sweep), S_ptr=tt(S_ptr), S_idx=tt(S_idx), S_val=tt(S_val),
                 alpha=alpha, factor=factor, rhs=rhs, colsum=cs, sumr=sumr, indptr=sd.indptr,
@@ -303,13 +264,13 @@ def test_factor_mode_and_gs_level(k, gram):
 
 @pytest.mark.parametrize("k", [1, 16, 50, 64, 96, 128, 160])
 def test_stats_predict_compose(k):
-    torch, layout, side_dev, tasks_dev, be, dev = _env()
+    torch, layout, side_dev, tasks_dev, be, dev = env()
     m, n = 300, 500
     rng = np.random.default_rng(5 + k)
     lens = list(rng.integers(0, 120, size=m))
     lens[7] = 0
     lens[11] = 450
-    side = _random_side(layout, m, n, lens, seed=k + 1)
+    side = random_side(layout, m, n, lens, seed=k + 1)
     ld = layout.padded_k(k)
     U = rng.normal(scale=0.3, size=(m, k)).astype(np.float32)
     V = rng.normal(scale=0.3, size=(n, k)).astype(np.float32)
@@ -319,9 +280,9 @@ def test_stats_predict_compose(k):
     b_i = rng.normal(scale=0.2, size=n).astype(np.float32)
     mu = 3.4
     tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    Ud, Vd = tt(_pad(U, ld)), tt(_pad(V, ld))
+    Ud, Vd = tt(pad(U, ld)), tt(pad(V, ld))
     Zd = torch.empty_like(Vd)
-    be.compose_z(Vd, tt(X), tt(_pad(W, ld)), Zd)
+    be.compose_z(Vd, tt(X), tt(pad(W, ld)), Zd)
     Zref = V.astype(np.float64) + X.astype(np.float64) @ W.astype(np.float64)
     Z = Zd.cpu().numpy()
     np.testing.assert_allclose(Z[:, :k], Zref, rtol=1e-5, atol=1e-6)
@@ -356,7 +317,7 @@ def test_stats_predict_compose(k):
 
 
 def test_bad_arguments_are_rejected():
-    torch, layout, side_dev, tasks_dev, be, dev = _env()
+    torch, layout, side_dev, tasks_dev, be, dev = env()
     import ctypes as C
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
@@ -382,7 +343,7 @@ def test_spd_solve_against_numpy(N):
     """als_spd_solve_f64 (the W-step's cholesky_solve, scripts/als.py:497-500) against numpy fp64:
     relative error of x at fp64 level scaled by the condition number, residual at rounding level,
     bitwise reproducible, inputs untouched."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env()
+    torch, layout, side_dev, tasks_dev, be, dev = env()
     A, b = _spd_system(N, seed=N)
     lam = 0.75
     ref = np.linalg.solve(A + lam * np.eye(N), b)
@@ -401,7 +362,7 @@ def test_spd_solve_against_numpy(N):
 
 
 def test_spd_solve_reports_indefinite_matrices():
-    torch, layout, side_dev, tasks_dev, be, dev = _env()
+    torch, layout, side_dev, tasks_dev, be, dev = env()
     N = 130
     A, b = _spd_system(N, seed=3)
     A[100, 100] = -5.0                                   # pivot 100 (or an earlier one) turns non-positive
@@ -419,12 +380,12 @@ def test_dual_form_short_rows_against_numpy_and_the_primal_kernel(k):
     dual form (n x n system); longer rows and split rows stay primal.  Every row against numpy fp64, the
     closed-form bias and residual sums against their definitions, and the dual rows against the primal kernel
     (ndual_tail = 0) on the same input."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env("f16x2")
+    torch, layout, side_dev, tasks_dev, be, dev = env("f16x2")
     ncols = 5000
     lens = [1, 2, 0, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 100, 4097 + 40, 64, 7, 300, 66, 79, 80, 81, 95,
             96, 97]
     nrows = len(lens)
-    side = _random_side(layout, nrows, ncols, lens, seed=3 * k)
+    side = random_side(layout, nrows, ncols, lens, seed=3 * k)
     rng = np.random.default_rng(7 + k)
     ld = layout.padded_k(k)
     F = rng.normal(scale=0.3, size=(ncols, k))
@@ -442,7 +403,7 @@ def test_dual_form_short_rows_against_numpy_and_the_primal_kernel(k):
     assert t.ndual == n_short and t.nslots == 2 and t.nmid == sum(1 for l in lens if dl < l <= dm)
     sd = side_dev(side, dev)
     f32 = torch.float32
-    Fd = torch.from_numpy(_pad(F, ld, 1)).to(dev)
+    Fd = torch.from_numpy(pad(F, ld, 1)).to(dev)
     ws = torch.empty(t.nslots * be.slot_bytes(k) // 4, dtype=f32, device=dev)
 
     def run(tasks):
@@ -494,17 +455,17 @@ def test_dual_form_short_rows_against_numpy_and_the_primal_kernel(k):
 def test_dual_classes_are_ignored_by_calls_with_byproducts():
     """Regression: a factor-only call (no X_out) whose task list carries dual classes (here: only the
     65...96 class, no short rows) must keep every row primal - the dual kernels write X_out."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env("f16x2")
+    torch, layout, side_dev, tasks_dev, be, dev = env("f16x2")
     k, ncols = 128, 3000
     lens = [70, 80, 96, 200, 90]
     nrows = len(lens)
-    side = _random_side(layout, nrows, ncols, lens, seed=5)
+    side = random_side(layout, nrows, ncols, lens, seed=5)
     rng = np.random.default_rng(6)
     ld = layout.padded_k(k)
     t = layout.build_row_tasks(side.indptr, dual_len=64, mid_len=96)
     assert t.ndual == 0 and t.nmid == 4
     f32 = torch.float32
-    F = torch.from_numpy(_pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)).to(dev)
+    F = torch.from_numpy(pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)).to(dev)
     factor = torch.zeros(nrows * ld * ld, dtype=f32, device=dev)
     rhs = torch.zeros(nrows, ld, dtype=f32, device=dev)
     cs = torch.zeros(nrows, ld, dtype=f32, device=dev)
@@ -526,7 +487,7 @@ def test_dual_classes_are_ignored_by_calls_with_byproducts():
 def test_dual_and_primal_agree_on_random_shapes():
     """Seeded sweep over ranks and row-length mixes: the dual classes (<= 64 ratings; 65...96 above k = 96)
     and the primal kernel must agree row by row within the fp32 tolerance, including bias and residual sums."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env("f16x2")
+    torch, layout, side_dev, tasks_dev, be, dev = env("f16x2")
     rng = np.random.default_rng(2024)
     f32 = torch.float32
     for trial in range(12):
@@ -534,10 +495,10 @@ def test_dual_and_primal_agree_on_random_shapes():
         ncols = int(rng.integers(200, 3000))
         nrows = int(rng.integers(5, 60))
         lens = [int(x) for x in np.minimum(rng.integers(0, 130, size=nrows), ncols)]
-        side = _random_side(layout, nrows, ncols, lens, seed=1000 + trial)
+        side = random_side(layout, nrows, ncols, lens, seed=1000 + trial)
         ld = layout.padded_k(k)
         t = layout.build_row_tasks(side.indptr, dual_len=64, mid_len=layout.dual_mid_len(k))
-        Fd = torch.from_numpy(_pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)).to(dev)
+        Fd = torch.from_numpy(pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)).to(dev)
         b_self = torch.from_numpy(rng.normal(scale=0.2, size=nrows).astype(np.float32)).to(dev)
         b_other = torch.from_numpy(rng.normal(scale=0.2, size=ncols).astype(np.float32)).to(dev)
         lam = float(rng.uniform(0.05, 5.0))

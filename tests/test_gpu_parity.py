@@ -27,7 +27,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from tests.common import Golden, golden_names
+from tests.common import Golden, golden_names, model_for
 
 
 def _cuda():
@@ -35,19 +35,6 @@ def _cuda():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
     return torch
-
-
-def _model_for(g: Golden, **kw):
-    from collaborative_filtering_amd import (ALS, ALSConfig, BiasesConfig, CoreConfig, GraphConfig,
-                                             GraphSimConfig)
-    c = g.cfg
-    cfg = ALSConfig(
-        core=CoreConfig(n_factors=c["n_factors"], n_iters=c["n_iters"], lambda_u=c["lambda_u"],
-                        lambda_v=c["lambda_v"], pop_reg_mode=c["pop_reg_mode"], random_state=42,
-                        update_w_every=c["update_w_every"]),
-        biases=BiasesConfig(lambda_bu=c["lambda_bu"], lambda_bi=c["lambda_bi"]),
-        graph=GraphConfig(alpha=c["alpha"], sim=GraphSimConfig(**c["sim"]) if c["sim"] else None))
-    return ALS(config=cfg, lambda_w=c["lambda_w"], **kw)
 
 
 TOL = dict(hist=2e-6, norms=2e-6, test_rmse=1e-6, f_rtol=1e-4, f_atol=5e-5, bias=5e-6, mu=1e-6, pred=3e-4)
@@ -126,7 +113,7 @@ def test_fit_matches_reference_fixture(name, gram):
     rows the call redoes in fp64, and the rank-deficient lambda_w = 0 designs."""
     _cuda()
     g = Golden(name)
-    model = _model_for(g, gram=gram)
+    model = model_for(g, gram=gram)
     r, c, v = g.train
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
                   min_iters=g.cfg["min_iters"], verbose=0)
@@ -140,7 +127,7 @@ def test_fp32_only_mode_at_small_lambda_is_what_the_docs_say(name):
     "auto" is the default."""
     _cuda()
     g = Golden(name)
-    model = _model_for(g, solve_dtype="float32")
+    model = model_for(g, solve_dtype="float32")
     r, c, v = g.train
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
                   min_iters=g.cfg["min_iters"], verbose=0)
@@ -158,7 +145,7 @@ def test_fit_float64_matches_reference_fixture(name):
     band on EVERY fixture, including the small-lambda corner where the fp32 solve is outside the 1e-4 budget."""
     _cuda()
     g = Golden(name)
-    model = _model_for(g, solve_dtype="float64")
+    model = model_for(g, solve_dtype="float64")
     r, c, v = g.train
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
                   min_iters=g.cfg["min_iters"], verbose=0)
@@ -182,14 +169,14 @@ def test_fit_falls_back_to_level_sweeps_when_the_dataflow_launch_gives_up(monkey
             hits["n"] += 1
     monkeypatch.setattr(A._Engine, "_gs_sweep", flaky)
     monkeypatch.setattr(A, "_DATAFLOW_GAVE_UP", set())      # (the per-device memory of the fallback: restored after the test)
-    model = _model_for(g)
+    model = model_for(g)
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
     assert hits["n"] == 1 and not model._eng.gs_dataflow and not model._dataflow_sweep
     _check_against_fixture(model, g, TOL)
     # the decision is remembered for the device: a NEW model (what a sweep driver makes per fit) starts with the
     # per-level launches instead of paying a failed attempt again
     assert A._DATAFLOW_GAVE_UP
-    again = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
+    again = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
     assert hits["n"] == 1 and not again._eng.gs_dataflow
     _check_against_fixture(again, g, TOL)
 
@@ -202,7 +189,7 @@ def test_refit_after_a_failed_sweep_leaves_no_history_of_the_failed_run(monkeypa
     g = Golden("g5_graph_a0.5")
     r, c, v = g.train
     monkeypatch.setattr(A, "_DATAFLOW_GAVE_UP", set())
-    model = _model_for(g)
+    model = model_for(g)
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
     first = list(model.history["train_rmse"])
     orig = A._Engine._gs_sweep
@@ -230,7 +217,7 @@ def test_predict_composes_z_from_the_features_it_is_given():
     g = Golden("g4_feat_uw1")
     r, c, v = g.train
     feats = {f: np.array(X, copy=True) for f, X in g.features.items()}
-    model = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=feats, tol=None, verbose=0)
+    model = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=feats, tol=None, verbose=0)
     idx = g.val_flat()
     base = model.predict_at(idx, feats)
     name = next(iter(feats))
@@ -253,7 +240,7 @@ def test_dense_entry_and_dense_predict():
     g = Golden("g2_bias_pop")
     r, c, v = g.train
     R = to_dense(r, c, v, (g.m, g.n))
-    model = _model_for(g).fit(R, tol=None, verbose=0)
+    model = model_for(g).fit(R, tol=None, verbose=0)
     R_hat = model.predict()
     assert R_hat.shape == (g.m, g.n) and R_hat.dtype == np.float64
     flat = g.val_flat()
@@ -266,8 +253,8 @@ def test_precomputed_graph_entry():
     _cuda()
     g = Golden("g5_graph_a0.5")
     r, c, v = g.train
-    m1 = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
-    m2 = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0, S=g.S_csr())
+    m1 = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
+    m2 = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0, S=g.S_csr())
     np.testing.assert_allclose(m1.V, m2.V, rtol=1e-4, atol=1e-5)
     np.testing.assert_allclose(m1.history["train_rmse"], m2.history["train_rmse"], atol=1e-6)
 
@@ -276,7 +263,7 @@ def test_history_appends_on_second_fit():
     _cuda()
     g = Golden("g1_plain")
     r, c, v = g.train
-    model = _model_for(g)
+    model = model_for(g)
     model.fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
     model.fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
     assert len(model.history["train_rmse"]) == 2 * g.cfg["n_iters"]      # reference quirk
@@ -296,14 +283,14 @@ def test_run_to_run_bitwise_reproducible():
     _cuda()
     g = Golden("g9_k64_mid")
     r, c, v = g.train
-    a = _model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
-    b = _model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
+    a = model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
+    b = model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
     assert np.array_equal(a.U, b.U) and np.array_equal(a.V, b.V)
     assert a.history["train_rmse"] == b.history["train_rmse"]
     # with the Laplacian: the dataflow sweep sums in a timing-independent order
     g = Golden("g5_graph_a0.5")
     r, c, v = g.train
-    runs = [_model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0) for _ in range(3)]
+    runs = [model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0) for _ in range(3)]
     for other in runs[1:]:
         assert np.array_equal(runs[0].V, other.V) and np.array_equal(runs[0].U, other.U)
         assert runs[0].history["train_rmse"] == other.history["train_rmse"]
@@ -321,7 +308,7 @@ def test_graph_without_features_matches_oracle(name):
     cfg = g.oracle_config()
     cfg.lambda_w = {}
     o = OracleALS(cfg).fit(g.train_ratings(), {}, tol=None, S_csr=g.S_csr())
-    m = _model_for(g)
+    m = model_for(g)
     m.fit_coo(r, c, v, (g.m, g.n), features=None, tol=None, verbose=0, S=g.S_csr())
     assert m._eng.fused_stats and m._eng.use_graph
     assert np.max(np.abs(np.asarray(m.history["train_rmse"]) - np.asarray(o.history["train_rmse"]))) <= TOL["hist"]
@@ -335,7 +322,7 @@ def test_fused_statistics_equal_the_standalone_pass():
     _cuda()
     g = Golden("g9_k64_mid")
     r, c, v = g.train
-    a = _model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
+    a = model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
     assert a._eng.fused_stats
     import collaborative_filtering_amd.als as A
     orig = A._Engine.stats_step
@@ -345,7 +332,7 @@ def test_fused_statistics_equal_the_standalone_pass():
         return orig(self, it)
     A._Engine.stats_step = unfused
     try:
-        b = _model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
+        b = model_for(g).fit_coo(r, c, v, (g.m, g.n), tol=None, verbose=0)
     finally:
         A._Engine.stats_step = orig
     np.testing.assert_allclose(a.history["train_rmse"], b.history["train_rmse"], atol=3e-6, rtol=0)
@@ -359,7 +346,7 @@ def test_feature_statistics_closed_form_equals_the_standalone_pass(name):
     _cuda()
     g = Golden(name)
     r, c, v = g.train
-    a = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
+    a = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
     assert a._eng.fused_feat_stats and not a._eng.fused_stats
     import collaborative_filtering_amd.als as A
     orig = A._Engine.stats_step
@@ -369,7 +356,7 @@ def test_feature_statistics_closed_form_equals_the_standalone_pass(name):
         return orig(self, it)
     A._Engine.stats_step = unfused
     try:
-        b = _model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
+        b = model_for(g).fit_coo(r, c, v, (g.m, g.n), features=g.features, tol=None, verbose=0)
     finally:
         A._Engine.stats_step = orig
     np.testing.assert_allclose(a.history["train_rmse"], b.history["train_rmse"], atol=3e-6, rtol=0)
@@ -476,8 +463,8 @@ def test_hip_graph_replay_is_bitwise_the_eager_fit(name):
     g = Golden(name)
     r, c, v = g.train
     kw = dict(features=g.features or None, tol=g.cfg["tol"], min_iters=g.cfg["min_iters"], verbose=0)
-    a = _model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
-    b = _model_for(g, hip_graph=True).fit_coo(r, c, v, (g.m, g.n), **kw)
+    a = model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
+    b = model_for(g, hip_graph=True).fit_coo(r, c, v, (g.m, g.n), **kw)
     assert b._eng.graphs_captured > 0                        # also with early stopping (g6: stops at iteration 32)
     assert len(a.history["train_rmse"]) == len(b.history["train_rmse"])
     for key in ("U", "V", "b_u", "b_i"):
@@ -497,10 +484,10 @@ def test_nondep_prepass_is_bitwise_the_in_sweep_gather(name, k, monkeypatch):
     r, c, v = g.train
     kw = dict(features=g.features or None, tol=None, verbose=0)
     monkeypatch.setenv("ALS_GS_NONDEP", "1")
-    a = _model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
+    a = model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
     assert a._eng.gs_nondep is not None
     monkeypatch.setenv("ALS_GS_NONDEP", "0")
-    b = _model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
+    b = model_for(g).fit_coo(r, c, v, (g.m, g.n), **kw)
     assert b._eng.gs_nondep is None
     np.testing.assert_array_equal(a.V, b.V)
     np.testing.assert_array_equal(a.U, b.U)

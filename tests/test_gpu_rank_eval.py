@@ -1,7 +1,8 @@
 """K11 (GPU): exact full-catalogue ranks (csrc/rank_eval.hip, als_rank_count), ALS.rank_of / rank_of_new.
 
 The oracle is exact: every score is bitwise the fp32 value als_predict_dense writes and the counts are integers, so
-the expected values come from the predict_dense rows with the seen items masked, and every comparison is ==."""
+the expected values are `rank_counts` of tests/serving_ref.py on the predict_dense rows with the seen items masked,
+and every comparison is ==."""
 import ctypes as C
 
 import numpy as np
@@ -9,8 +10,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from tests.common import Golden
-from tests.test_gpu_recommend import _dense, _env, _factors, _model_for, _run, _seen_csr
+from tests import serving_ref as ref
+from tests.common import Golden, model_for
+from tests.gpu_common import assert_same, env, factors, predict_dense, run_rank, run_topk, seen_csr
 
 
 def _targets(n, nq, seed, rows_seen=None):
@@ -29,92 +31,55 @@ def _targets(n, nq, seed, rows_seen=None):
     return ptr, items
 
 
-def _expected(dense_rows, seen_rows, q_ptr, q_items):
-    B, n = dense_rows.shape
-    sc = np.zeros(q_items.size, np.float32)
-    ab = np.zeros(q_items.size, np.int32)
-    nc = np.zeros(B, np.int32)
-    j = np.arange(n)
-    for b in range(B):
-        cand = ~np.isnan(dense_rows[b])
-        cand[seen_rows[b]] = False
-        nc[b] = cand.sum()
-        for p in range(q_ptr[b], q_ptr[b + 1]):
-            t, s = q_items[p], dense_rows[b, q_items[p]]
-            sc[p] = s
-            ab[p] = -1 if np.isnan(s) else (cand & ((dense_rows[b] > s) | ((dense_rows[b] == s) & (j < t)))).sum()
-    return sc, ab, nc
-
-
-def _rank(torch, be, f, users, n, seen_ptr, seen_idx, q_ptr, q_items, dev):
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dt))).to(dev)
-    nq, nt = len(users), q_items.size
-    sc = torch.full((max(nt, 1),), 7.0, dtype=torch.float32, device=dev)
-    ab = torch.full((max(nt, 1),), 7, dtype=torch.int32, device=dev)
-    nc = torch.full((nq,), 7, dtype=torch.int32, device=dev)
-    be.rank_count(k=f["k"], ld=f["ld"], n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"], mu=f["mu"],
-                  seen_ptr=None if seen_ptr is None else t(seen_ptr, np.int64),
-                  seen_idx=None if seen_idx is None else t(seen_idx, np.int32), q_users=t(users, np.int32),
-                  q_ptr=t(q_ptr, np.int64), q_items=t(q_items, np.int32)[:nt], t_score=sc[:nt], above=ab[:nt],
-                  n_cand=nc)
-    return sc[:nt].cpu().numpy(), ab[:nt].cpu().numpy(), nc.cpu().numpy()
-
-
-def _assert_same(got, exp):
-    for g, e in zip(got, exp):
-        assert g.shape == e.shape
-        same = (g == e) | ((g != g) & (e != e))                          # a NaN target score is NaN on both sides
-        assert same.all(), (np.argwhere(~same)[:5], g[~same][:5], e[~same][:5])
-
-
 @pytest.mark.parametrize("k", [1, 16, 50, 64, 128, 160])
 @pytest.mark.parametrize("n", [1, 17, 1000, 4099])
 def test_kernel_equals_masked_dense_count(k, n):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m = 40
-    f = _factors(torch, layout, dev, m, n, k, seed=10 * k + n)
+    f = factors(torch, layout, dev, m, n, k, seed=10 * k + n)
     if n > 16:
         f["Z"][5, 0] = float("nan")                                      # NaN scores: item 5 for every user
-    ptr, idx, rows = _seen_csr(m, n, seed=k + n)                         # user 0 sees nothing, user 1 all but 3
-    dense = _dense(torch, be, f, m, n, dev)
+    ptr, idx, rows = seen_csr(m, n, seed=k + n)                         # user 0 sees nothing, user 1 all but 3
+    dense = predict_dense(torch, be, f, m, n, dev)
     users = np.concatenate([np.arange(m), [3, 1, 3, 0]])[::-1].copy()    # order and duplicates kept
     seen_rows = [rows[u] for u in users]
     q_ptr, q_items = _targets(n, users.size, seed=k * n, rows_seen=seen_rows)
     if n > 16:
         q_items[q_ptr[4]] = 5                                            # a NaN target
-    got = _rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
-    _assert_same(got, _expected(dense[users], seen_rows, q_ptr, q_items))
+    got = run_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
+    assert_same(got, ref.rank_counts_batch(dense[users], seen_rows, None, q_ptr, q_items), nan_equal=True)
     if n > 16:
         assert got[1][q_ptr[4]] == -1 and np.isnan(got[0][q_ptr[4]])
-    got = _rank(torch, be, f, users, n, None, None, q_ptr, q_items, dev)                 # no exclusion
-    _assert_same(got, _expected(dense[users], [np.empty(0, np.int64)] * users.size, q_ptr, q_items))
+    got = run_rank(torch, be, f, users, n, None, None, q_ptr, q_items, dev)              # no exclusion
+    unseen = [np.empty(0, np.int64)] * users.size
+    assert_same(got, ref.rank_counts_batch(dense[users], unseen, None, q_ptr, q_items), nan_equal=True)
     full_ptr = np.arange(m + 1, dtype=np.int64) * n                      # every user has seen everything
-    got = _rank(torch, be, f, np.arange(m), n, full_ptr, np.tile(np.arange(n, dtype=np.int32), m), q_ptr[: m + 1],
-                q_items[: q_ptr[m]], dev)
+    got = run_rank(torch, be, f, np.arange(m), n, full_ptr, np.tile(np.arange(n, dtype=np.int32), m), q_ptr[: m + 1],
+                   q_items[: q_ptr[m]], dev)
     assert (got[2] == 0).all() and (got[1][~np.isnan(got[0])] == 0).all()
 
 
 def test_ties_follow_the_item_order():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n = 64, 3001
-    f = _factors(torch, layout, dev, m, n, 5, seed=4, integer=True)     # duplicated Z rows, b_i = 0: equal scores
-    ptr, idx, rows = _seen_csr(m, n, seed=4, density=0.1)
-    dense = _dense(torch, be, f, m, n, dev)
+    f = factors(torch, layout, dev, m, n, 5, seed=4, integer=True)     # duplicated Z rows, b_i = 0: equal scores
+    ptr, idx, rows = seen_csr(m, n, seed=4, density=0.1)
+    dense = predict_dense(torch, be, f, m, n, dev)
     users = np.arange(m)
     q_ptr = np.arange(m + 1, dtype=np.int64) * 40
     q_items = np.random.default_rng(4).integers(0, n, m * 40).astype(np.int32)
     assert sum(int((dense[u] == dense[u, q_items[40 * u]]).sum()) > 1 for u in range(m)) > m // 2
-    got = _rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
-    _assert_same(got, _expected(dense, rows, q_ptr, q_items))
+    got = run_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
+    assert_same(got, ref.rank_counts_batch(dense, rows, None, q_ptr, q_items), nan_equal=True)
 
 
 @pytest.mark.parametrize("B", [1, 3000])
 def test_result_does_not_depend_on_the_slice_count(B, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     m, n, k = 3000, 5003, 64
-    f = _factors(torch, layout, dev, m, n, k, seed=B)
-    ptr, idx, rows = _seen_csr(m, n, seed=B)
+    f = factors(torch, layout, dev, m, n, k, seed=B)
+    ptr, idx, rows = seen_csr(m, n, seed=B)
     users = np.random.default_rng(B).permutation(m)[:B]
     q_ptr, q_items = _targets(n, B, seed=B)
     if B == 1:
@@ -125,20 +90,21 @@ def test_result_does_not_depend_on_the_slice_count(B, monkeypatch):
         need = _hip.load().als_rank_count_workspace_bytes(k, B, nt, n, s)
         assert need == (0 if s == 1 else s * (nt + B) * 4)
         monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
-        outs.append(_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev))
+        outs.append(run_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev))
     monkeypatch.delenv("ALS_RECOMMEND_SLICES")
-    outs.append(_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev))            # automatic
+    outs.append(run_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev))            # automatic
     for o in outs[1:]:
-        _assert_same(o, outs[0])
-    dense = _dense(torch, be, f, m, n, dev)
-    _assert_same(outs[0], _expected(dense[users], [rows[u] for u in users], q_ptr, q_items))
+        assert_same(o, outs[0], nan_equal=True)
+    dense = predict_dense(torch, be, f, m, n, dev)
+    exp = ref.rank_counts_batch(dense[users], [rows[u] for u in users], None, q_ptr, q_items)
+    assert_same(outs[0], exp, nan_equal=True)
 
 
 def _cross_check(torch, be, f, users, n, ptr, idx, dev, extra_seed):
     """recommend(N = 128) against rank_count: the item at position p has rank p, and every unseen target with a
     rank below 128 is in the list."""
     N = 128
-    tv, ti, tc = _run(torch, be, f, users, n, ptr, idx, N, dev)
+    tv, ti, tc = run_topk(torch, be, f, users, n, ptr, idx, N, dev)
     B = len(users)
     rng = np.random.default_rng(extra_seed)
     extra = rng.integers(0, n, (B, 8)).astype(np.int32)
@@ -146,7 +112,7 @@ def _cross_check(torch, be, f, users, n, ptr, idx, dev, extra_seed):
     q_ptr = np.zeros(B + 1, np.int64)
     q_ptr[1:] = np.cumsum([r.size for r in rows])
     q_items = np.concatenate(rows).astype(np.int32)
-    sc, ab, nc = _rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
+    sc, ab, nc = run_rank(torch, be, f, users, n, ptr, idx, q_ptr, q_items, dev)
     for b in range(B):
         lo = q_ptr[b]
         assert (ab[lo: lo + tc[b]] == np.arange(tc[b])).all()
@@ -161,29 +127,28 @@ def _cross_check(torch, be, f, users, n, ptr, idx, dev, extra_seed):
 
 
 def test_cross_check_with_recommend():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k = 300, 4099, 50
-    f = _factors(torch, layout, dev, m, n, k, seed=2)
-    ptr, idx, rows = _seen_csr(m, n, seed=2)
+    f = factors(torch, layout, dev, m, n, k, seed=2)
+    ptr, idx, rows = seen_csr(m, n, seed=2)
     _cross_check(torch, be, f, np.arange(m), n, ptr, idx, dev, 2)
 
 
 # ---------------------------------------------------------------------------------------------- model level
 def _brute(P, seen, u, t):
-    cand = ~np.isnan(P[u])
-    cand[seen] = False
-    j = np.arange(P.shape[1])
-    return int((cand & ((P[u] > P[u, t]) | ((P[u] == P[u, t]) & (j < t)))).sum()), int(cand.sum())
+    """(rank, candidates) of item t for user u from the dense predictions, the seen items masked."""
+    _, above, n_cand = ref.rank_counts(P[u], seen, None, [t])
+    return int(above[0]), n_cand
 
 
 @pytest.mark.parametrize("name,use_features", [("g3_empty", True), ("g4_feat_uw5", True), ("g4_feat_uw5", False),
                                                ("g5_graph_a5.0", True)])
 def test_model_rank_of_on_fixtures(name, use_features):
-    _env()
+    env()
     from collaborative_filtering_amd import cv
     g = Golden(name)
     r, c, v = g.train
-    model = _model_for(g, device="cuda:0")
+    model = model_for(g, device="cuda:0")
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"], verbose=0)
     feats = g.features if use_features else None
     P = model.predict(feats).astype(np.float32)
@@ -207,10 +172,10 @@ def test_model_rank_of_on_fixtures(name, use_features):
 
 
 def test_rank_of_new_agrees_with_recommend_new():
-    _env()
+    env()
     g = Golden("g4_feat_uw5")
     r, c, v = g.train
-    model = _model_for(g, device="cuda:0")
+    model = model_for(g, device="cuda:0")
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"], verbose=0)
     rng = np.random.default_rng(1)
     B = 9
@@ -233,7 +198,7 @@ def test_rank_of_new_agrees_with_recommend_new():
 def test_full_size_property():
     """1M users x 100K items, k = 64, ~100 seen items per user (as test_full_size_all_users): 4096 users, checked
     against recommend(N = 128) - the item at position p has rank p, unseen targets ranked below 128 are listed."""
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k = 1_000_000, 100_000, 64
     gen = torch.Generator(device=dev).manual_seed(3)
     ld = layout.padded_k(k)
@@ -253,11 +218,11 @@ def test_full_size_property():
 
 # ------------------------------------------------------------------------------------------------ bad arguments
 def test_bad_arguments_return_the_documented_status():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     m, n, k, T = 8, 5000, 64, 3
-    f = _factors(torch, layout, dev, m, n, k, seed=1)
+    f = factors(torch, layout, dev, m, n, k, seed=1)
     users = torch.arange(m, dtype=torch.int32, device=dev)
     q_ptr = torch.arange(m + 1, dtype=torch.int64, device=dev) * T
     q_items = torch.arange(m * T, dtype=torch.int32, device=dev)

@@ -1,8 +1,8 @@
 """K8 (GPU): fused top-N recommendation (csrc/recommend.hip, als_recommend_topk) and ALS.recommend.
 
 The oracle is exact: every returned score is bitwise the fp32 value als_predict_dense writes, so the expected
-lists are the predict_dense rows with the seen items removed, sorted stably by (score descending, item ascending),
-and outputs are compared with ==."""
+lists are `topn` of tests/serving_ref.py on the predict_dense rows (seen items removed, sorted stably by (score
+descending, item ascending)), and outputs are compared with ==."""
 import ctypes as C
 
 import numpy as np
@@ -10,185 +10,75 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from tests.common import Golden
-
-
-def _env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests selected (-m gpu) but no ROCm device is visible")
-    from collaborative_filtering_amd import _hip, layout
-    from collaborative_filtering_amd.backend import HipBackend
-    dev = torch.device("cuda", 0)
-    return torch, layout, HipBackend(dev), dev
-
-
-def _factors(torch, layout, dev, m, n, k, seed, integer=False):
-    """U [m, ld], Z [n, ld] (padding columns zero), biases, mu - fp32 / fp64 device tensors."""
-    ld = layout.padded_k(k)
-    rng = np.random.default_rng(seed)
-    if integer:                                  # small integers: many exactly equal scores
-        U = np.zeros((m, ld), np.float32)
-        Z = np.zeros((n, ld), np.float32)
-        U[:, :k] = rng.integers(-2, 3, size=(m, k))
-        Z[:, :k] = rng.integers(-2, 3, size=(n, k))
-        Z[1::3] = Z[0::3][: Z[1::3].shape[0]]    # duplicated item rows
-        bu = rng.integers(-1, 2, size=m).astype(np.float32)
-        bi = np.zeros(n, np.float32)
-        mu = 0.0
-    else:
-        U = np.zeros((m, ld), np.float32)
-        Z = np.zeros((n, ld), np.float32)
-        U[:, :k] = rng.normal(size=(m, k))
-        Z[:, :k] = rng.normal(size=(n, k))
-        bu = rng.normal(scale=0.3, size=m).astype(np.float32)
-        bi = rng.normal(scale=0.3, size=n).astype(np.float32)
-        mu = 3.5
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return dict(k=k, ld=ld, U=t(U), Z=t(Z), b_u=t(bu), b_i=t(bi), mu=torch.tensor([mu], dtype=torch.float64, device=dev))
-
-
-def _seen_csr(m, n, seed, density=0.05):
-    """Seen rows by user id: user 0 sees nothing, user 1 all but 3 items, user 2 more than 3000 (when n allows),
-    the others a random subset."""
-    rng = np.random.default_rng(seed)
-    rows = []
-    for u in range(m):
-        if u == 0:
-            s = np.empty(0, np.int64)
-        elif u == 1:
-            s = np.sort(rng.permutation(n)[: max(n - 3, 0)])
-        elif u == 2 and n > 3500:
-            s = np.sort(rng.permutation(n)[: 3200])
-        else:
-            s = np.nonzero(rng.random(n) < density)[0]
-        rows.append(s)
-    ptr = np.zeros(m + 1, np.int64)
-    ptr[1:] = np.cumsum([len(s) for s in rows])
-    idx = np.concatenate(rows).astype(np.int32) if ptr[-1] else np.zeros(0, np.int32)
-    return ptr, idx, rows
-
-
-def _dense(torch, be, f, m, n, dev):
-    out = torch.empty(m, n, dtype=torch.float32, device=dev)
-    be.predict_dense(k=f["k"], ld=f["ld"], m=m, n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"], mu=f["mu"], out=out)
-    return out.cpu().numpy()
-
-
-def _expected(dense_rows, seen_rows, N):
-    """dense_rows[b]: predict_dense row of batch row b; seen_rows[b]: its seen items."""
-    B, n = dense_rows.shape
-    tv = np.full((B, N), -np.inf, np.float32)
-    ti = np.full((B, N), -1, np.int32)
-    tc = np.zeros(B, np.int32)
-    for b in range(B):
-        keep = np.ones(n, bool)
-        keep[seen_rows[b]] = False
-        items = np.nonzero(keep)[0]
-        sc = dense_rows[b, items]
-        order = np.lexsort((items, -sc))[:N]
-        tv[b, : order.size] = sc[order]
-        ti[b, : order.size] = items[order]
-        tc[b] = order.size
-    return tv, ti, tc
-
-
-def _run(torch, be, f, users, n, seen_ptr, seen_idx, N, dev):
-    us = torch.from_numpy(np.asarray(users, np.int32)).to(dev)
-    B = us.numel()
-    tv = torch.empty(B, N, dtype=torch.float32, device=dev)
-    ti = torch.empty(B, N, dtype=torch.int32, device=dev)
-    tc = torch.empty(B, dtype=torch.int32, device=dev)
-    sp = None if seen_ptr is None else torch.from_numpy(seen_ptr).to(dev)
-    si = None if seen_idx is None else torch.from_numpy(seen_idx).to(dev)
-    be.recommend_topk(k=f["k"], ld=f["ld"], users=us, n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"],
-                      mu=f["mu"], seen_ptr=sp, seen_idx=si, topn=N, top_val=tv, top_idx=ti, top_cnt=tc)
-    return tv.cpu().numpy(), ti.cpu().numpy(), tc.cpu().numpy()
-
-
-def _assert_same(got, exp):
-    for g, e in zip(got, exp):
-        assert g.shape == e.shape
-        assert (g == e).all(), np.argwhere(g != e)[:5]
+from tests import serving_ref as ref
+from tests.common import Golden, model_for
+from tests.gpu_common import assert_same, env, factors, predict_dense, run_topk, seen_csr
 
 
 @pytest.mark.parametrize("k", [1, 16, 50, 64, 128, 160])
 @pytest.mark.parametrize("n", [1, 17, 1000, 4099])
 def test_kernel_equals_masked_dense_sort(k, n):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m = 40
-    f = _factors(torch, layout, dev, m, n, k, seed=10 * k + n)
-    ptr, idx, rows = _seen_csr(m, n, seed=k + n)
-    dense = _dense(torch, be, f, m, n, dev)
+    f = factors(torch, layout, dev, m, n, k, seed=10 * k + n)
+    ptr, idx, rows = seen_csr(m, n, seed=k + n)
+    dense = predict_dense(torch, be, f, m, n, dev)
     users = np.concatenate([np.arange(m), [3, 1, 3, 0]])[::-1].copy()      # order and duplicates kept
     for N in (1, 10, 128):
-        got = _run(torch, be, f, users, n, ptr, idx, N, dev)
-        _assert_same(got, _expected(dense[users], [rows[u] for u in users], N))
+        got = run_topk(torch, be, f, users, n, ptr, idx, N, dev)
+        assert_same(got, ref.topn_batch(dense[users], [rows[u] for u in users], None, N))
         if n > 3 and N >= 3:
             b = int(np.nonzero(users == 1)[0][0])                          # all but 3 seen: padded
             assert got[2][b] == 3 and (got[1][b, 3:] == -1).all() and np.isneginf(got[0][b, 3:]).all()
     # no exclusion
-    got = _run(torch, be, f, users, n, None, None, 10, dev)
-    _assert_same(got, _expected(dense[users], [np.empty(0, np.int64)] * users.size, 10))
+    got = run_topk(torch, be, f, users, n, None, None, 10, dev)
+    assert_same(got, ref.topn_batch(dense[users], [np.empty(0, np.int64)] * users.size, None, 10))
 
 
 @pytest.mark.parametrize("N", [1, 10, 33, 128])
 def test_ties_go_to_the_lowest_item_index(N):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n = 64, 3001
-    f = _factors(torch, layout, dev, m, n, 5, seed=N, integer=True)
-    ptr, idx, rows = _seen_csr(m, n, seed=N, density=0.1)
-    dense = _dense(torch, be, f, m, n, dev)
+    f = factors(torch, layout, dev, m, n, 5, seed=N, integer=True)
+    ptr, idx, rows = seen_csr(m, n, seed=N, density=0.1)
+    dense = predict_dense(torch, be, f, m, n, dev)
     users = np.arange(m)
-    got = _run(torch, be, f, users, n, ptr, idx, N, dev)
-    tv, ti, tc = _expected(dense, rows, N)
+    got = run_topk(torch, be, f, users, n, ptr, idx, N, dev)
+    tv, ti, tc = ref.topn_batch(dense, rows, None, N)
     # ties across the N-th boundary really occur
     assert sum(int((dense[u] == tv[u, N - 1]).sum()) > 1 for u in range(3, m)) > m // 2
-    _assert_same(got, (tv, ti, tc))
+    assert_same(got, (tv, ti, tc))
 
 
 @pytest.mark.parametrize("B,N", [(1, 10), (1, 128), (3000, 10), (3000, 100)])
 def test_result_does_not_depend_on_the_slice_count(B, N, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     m, n, k = 3000, 5003, 64
-    f = _factors(torch, layout, dev, m, n, k, seed=B + N)
-    ptr, idx, rows = _seen_csr(m, n, seed=B)
+    f = factors(torch, layout, dev, m, n, k, seed=B + N)
+    ptr, idx, rows = seen_csr(m, n, seed=B)
     users = np.random.default_rng(B).permutation(m)[:B]
     outs = []
     for s in (1, 2, 7, 64):
         assert s <= 64 and _hip.load().als_recommend_workspace_bytes(B, n, N, s) == (0 if s == 1 else s * B * N * 8)
         monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
-        outs.append(_run(torch, be, f, users, n, ptr, idx, N, dev))
+        outs.append(run_topk(torch, be, f, users, n, ptr, idx, N, dev))
     monkeypatch.delenv("ALS_RECOMMEND_SLICES")
-    outs.append(_run(torch, be, f, users, n, ptr, idx, N, dev))          # automatic
+    outs.append(run_topk(torch, be, f, users, n, ptr, idx, N, dev))          # automatic
     for o in outs[1:]:
-        _assert_same(o, outs[0])
-    dense = _dense(torch, be, f, m, n, dev)
-    _assert_same(outs[0], _expected(dense[users], [rows[u] for u in users], N))
+        assert_same(o, outs[0])
+    dense = predict_dense(torch, be, f, m, n, dev)
+    assert_same(outs[0], ref.topn_batch(dense[users], [rows[u] for u in users], None, N))
 
 
 # ---------------------------------------------------------------------------------------------- model level
-def _model_for(g: Golden, **kw):
-    from collaborative_filtering_amd import (ALS, ALSConfig, BiasesConfig, CoreConfig, GraphConfig,
-                                             GraphSimConfig)
-    c = g.cfg
-    cfg = ALSConfig(
-        core=CoreConfig(n_factors=c["n_factors"], n_iters=c["n_iters"], lambda_u=c["lambda_u"],
-                        lambda_v=c["lambda_v"], pop_reg_mode=c["pop_reg_mode"], random_state=42,
-                        update_w_every=c["update_w_every"]),
-        biases=BiasesConfig(lambda_bu=c["lambda_bu"], lambda_bi=c["lambda_bi"]),
-        graph=GraphConfig(alpha=c["alpha"], sim=GraphSimConfig(**c["sim"]) if c["sim"] else None))
-    return ALS(config=cfg, lambda_w=c["lambda_w"], **kw)
-
-
 def _check_model(model, m, n, train_rows, train_cols, features):
     P = model.predict(features).astype(np.float32)            # fp32 values widened: exact round trip
     seen = [train_cols[train_rows == u] for u in range(m)]
     for N in (1, 10, 128):
         items, scores = model.recommend(None, N, features=features)
         assert items.shape == (m, N) and items.dtype == np.int64 and scores.dtype == np.float64
-        tv, ti, _ = _expected(P, seen, N)
+        tv, ti, _ = ref.topn_batch(P, seen, None, N)
         assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
         for u in range(m):                                   # no training item is ever returned
             assert not np.isin(items[u], seen[u]).any()
@@ -213,23 +103,23 @@ def _check_model(model, m, n, train_rows, train_cols, features):
     ("g1_plain", True, {"solve_dtype": "float64"}),
 ])
 def test_model_recommend_on_fixtures(name, use_features, kw):
-    _env()
+    env()
     g = Golden(name)
     r, c, v = g.train
-    model = _model_for(g, device="cuda:0", **kw)
+    model = model_for(g, device="cuda:0", **kw)
     model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"], verbose=0)
     _check_model(model, g.m, g.n, r, c, g.features if use_features else None)
 
 
 def test_sweep_fold_excludes_that_folds_training_ratings():
-    _env()
+    env()
     from collaborative_filtering_amd import cv, sweep
     g = Golden("g4_feat_uw2")
     ratings = cv.CooRatings(g.rows, g.cols, g.vals, (g.m, g.n))
     folds = cv.make_entrywise_folds(ratings, n_splits=3, seed=42)
     drv = sweep.SweepDriver(ratings, g.features, folds)
     f = drv.folds[1]
-    model = _model_for(g, device=drv.dev, fit_cache=f.cache)
+    model = model_for(g, device=drv.dev, fit_cache=f.cache)
     model._fit_sides(f.csr, f.csc, g.features, None, 1, 0, None, S_trusted=True)     # as SweepDriver.cv_score fits
     (tr, tc, _), (vr, vc, vv), _ = cv.train_valid_split(ratings, folds, 1)
     _check_model(model, g.m, g.n, tr, tc, g.features)
@@ -243,7 +133,7 @@ def test_sweep_fold_excludes_that_folds_training_ratings():
 # ------------------------------------------------------------------------------------------------ full size
 def test_full_size_all_users():
     """configs[3] shape: 1M users x 100K items, k = 64, ~100 seen items per user, all users, N = 10."""
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k, N = 1_000_000, 100_000, 64, 10
     gen = torch.Generator(device=dev).manual_seed(3)
     ld = layout.padded_k(k)
@@ -278,17 +168,17 @@ def test_full_size_all_users():
                      mu=mu, out=out)
     sp, si = seen_ptr.cpu().numpy(), seen_idx.cpu().numpy()
     s_np = samp.cpu().numpy()
-    exp = _expected(out.cpu().numpy(), [si[sp[u]: sp[u + 1]] for u in s_np], N)
-    _assert_same((tv[samp].cpu().numpy(), ti[samp].cpu().numpy(), tc[samp].cpu().numpy()), exp)
+    exp = ref.topn_batch(out.cpu().numpy(), [si[sp[u]: sp[u + 1]] for u in s_np], None, N)
+    assert_same((tv[samp].cpu().numpy(), ti[samp].cpu().numpy(), tc[samp].cpu().numpy()), exp)
 
 
 # ------------------------------------------------------------------------------------------------ bad arguments
 def test_bad_arguments_return_the_documented_status():
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     from collaborative_filtering_amd import _hip
     lib = _hip.load()
     m, n, k, N = 8, 5000, 64, 10
-    f = _factors(torch, layout, dev, m, n, k, seed=1)
+    f = factors(torch, layout, dev, m, n, k, seed=1)
     users = torch.arange(m, dtype=torch.int32, device=dev)
     tv = torch.full((m, N), 7.0, dtype=torch.float32, device=dev)
     ti = torch.full((m, N), 7, dtype=torch.int32, device=dev)

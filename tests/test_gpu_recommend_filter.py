@@ -2,15 +2,17 @@
 csrc/rank_eval.hip) and `items=` / `filter_items=` of ALS.recommend*, rank_of*.
 
 The oracle is exact, as in test_gpu_recommend.py: every score is bitwise the fp32 value als_predict_dense writes, so
-the expected lists are the predict_dense rows with the seen AND the disallowed columns removed, sorted by (score
-descending, item ascending); ranks are counts over the same rows.  Everything is compared with ==."""
+the expected lists are `topn` of tests/serving_ref.py on the predict_dense rows (the seen AND the disallowed columns
+removed, sorted by (score descending, item ascending)); ranks are `rank_counts` over the same rows.  Everything is
+compared with ==."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+from tests import serving_ref as ref
+from tests.gpu_common import assert_same, env, factors, predict_dense, run_rank, run_topk, seen_csr
 from tests.synth import make_ratings
-from tests.test_gpu_recommend import _assert_same, _dense, _env, _factors, _run, _seen_csr
 
 SLICES = (1, 2, 7, 64)
 
@@ -38,118 +40,56 @@ def _bitmap(torch, mask, dev):
     return torch.from_numpy(words.view(np.int32).copy()).to(dev)
 
 
-def _expected_masked(dense_rows, seen_rows, ok, N):
-    B, n = dense_rows.shape
-    tv = np.full((B, N), -np.inf, np.float32)
-    ti = np.full((B, N), -1, np.int32)
-    tc = np.zeros(B, np.int32)
-    for b in range(B):
-        keep = ok.copy()
-        keep[seen_rows[b]] = False
-        items = np.nonzero(keep)[0]
-        sc = dense_rows[b, items]
-        order = np.lexsort((items, -sc))[:N]
-        tv[b, : order.size] = sc[order]
-        ti[b, : order.size] = items[order]
-        tc[b] = order.size
-    return tv, ti, tc
-
-
-def _run_masked(torch, be, f, users, n, seen_ptr, seen_idx, allow, N, dev):
-    us = torch.from_numpy(np.asarray(users, np.int32)).to(dev)
-    B = us.numel()
-    tv = torch.empty(B, N, dtype=torch.float32, device=dev)
-    ti = torch.empty(B, N, dtype=torch.int32, device=dev)
-    tc = torch.empty(B, dtype=torch.int32, device=dev)
-    sp = None if seen_ptr is None else torch.from_numpy(seen_ptr).to(dev)
-    si = None if seen_idx is None else torch.from_numpy(seen_idx).to(dev)
-    be.recommend_topk_masked(k=f["k"], ld=f["ld"], users=us, n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"],
-                             mu=f["mu"], seen_ptr=sp, seen_idx=si, allow=allow, topn=N, top_val=tv, top_idx=ti,
-                             top_cnt=tc)
-    return tv.cpu().numpy(), ti.cpu().numpy(), tc.cpu().numpy()
-
-
 # ------------------------------------------------------------------------------------------------ kernel level
 @pytest.mark.parametrize("k,n", [(16, 1003), (64, 4099), (160, 2051)])     # n never a multiple of 32
 def test_masked_kernel_equals_masked_dense_sort(k, n, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m = 40
-    f = _factors(torch, layout, dev, m, n, k, seed=10 * k + n)
-    ptr, idx, rows = _seen_csr(m, n, seed=k + n)
-    dense = _dense(torch, be, f, m, n, dev)
+    f = factors(torch, layout, dev, m, n, k, seed=10 * k + n)
+    ptr, idx, rows = seen_csr(m, n, seed=k + n)
+    dense = predict_dense(torch, be, f, m, n, dev)
     users = np.concatenate([np.arange(m), [3, 1, 3, 0]])[::-1].copy()
     seen = [rows[u] for u in users]
     for name, ok in _masks(n, seed=n).items():
         allow = _bitmap(torch, ok, dev)
         for N in (10, 128):
-            exp = _expected_masked(dense[users], seen, ok, N)
+            exp = ref.topn_batch(dense[users], seen, ok, N)
             for s in SLICES:
                 monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
-                got = _run_masked(torch, be, f, users, n, ptr, idx, allow, N, dev)
+                got = run_topk(torch, be, f, users, n, ptr, idx, N, dev, allow)
                 for g, e in zip(got, exp):
                     assert (g == e).all(), (name, N, s, np.argwhere(g != e)[:5])
             monkeypatch.delenv("ALS_RECOMMEND_SLICES")
-            _assert_same(_run_masked(torch, be, f, users, n, ptr, idx, allow, N, dev), exp)      # automatic
+            assert_same(run_topk(torch, be, f, users, n, ptr, idx, N, dev, allow), exp)      # automatic
         if name == "empty":
             assert (exp[2] == 0).all()
         # no seen rows at all
-        _assert_same(_run_masked(torch, be, f, users, n, None, None, allow, 10, dev),
-                     _expected_masked(dense[users], [np.empty(0, np.int64)] * users.size, ok, 10))
+        assert_same(run_topk(torch, be, f, users, n, None, None, 10, dev, allow),
+                     ref.topn_batch(dense[users], [np.empty(0, np.int64)] * users.size, ok, 10))
 
 
 @pytest.mark.parametrize("B,N", [(1, 10), (3000, 10), (3000, 128)])
 def test_all_ones_mask_equals_the_unmasked_call_bitwise(B, N, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m, n, k = 3000, 5003, 64
-    f = _factors(torch, layout, dev, m, n, k, seed=B + N)
-    ptr, idx, rows = _seen_csr(m, n, seed=B)
+    f = factors(torch, layout, dev, m, n, k, seed=B + N)
+    ptr, idx, rows = seen_csr(m, n, seed=B)
     users = np.random.default_rng(B).permutation(m)[:B]
     ones = _bitmap(torch, np.ones(n, bool), dev)
     ones.view(torch.int32)[-1] = -1                                        # bits at positions >= n are ignored
     for s in (0, 1, 7):
         monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
-        _assert_same(_run_masked(torch, be, f, users, n, ptr, idx, ones, N, dev),
-                     _run(torch, be, f, users, n, ptr, idx, N, dev))
-
-
-def _rank_run(torch, be, f, n, seen, q_users, q_ptr, q_items, dev, allow=None):
-    t = lambda a, dt: torch.from_numpy(np.asarray(a, dt)).to(dev)
-    nq, nt = len(q_users), len(q_items)
-    score = torch.empty(nt, dtype=torch.float32, device=dev)
-    above = torch.empty(nt, dtype=torch.int32, device=dev)
-    ncand = torch.empty(nq, dtype=torch.int32, device=dev)
-    kw = dict(k=f["k"], ld=f["ld"], n=n, U=f["U"], Z=f["Z"], b_u=f["b_u"], b_i=f["b_i"], mu=f["mu"],
-              seen_ptr=None if seen is None else t(seen[0], np.int64),
-              seen_idx=None if seen is None else t(seen[1], np.int32), q_users=t(q_users, np.int32),
-              q_ptr=t(q_ptr, np.int64), q_items=t(q_items, np.int32), t_score=score, above=above, n_cand=ncand)
-    if allow is None:
-        be.rank_count(**kw)
-    else:
-        be.rank_count_masked(allow=allow, **kw)
-    return above.cpu().numpy(), ncand.cpu().numpy(), score.cpu().numpy()
-
-
-def _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items):
-    """above[p]: allowed unseen items ahead of target p in (score descending, item ascending); cand[b]: their number."""
-    j = np.arange(dense.shape[1])
-    exp_above, exp_cand = np.zeros(len(q_items), np.int32), np.zeros(len(q_users), np.int32)
-    for b, u in enumerate(q_users):
-        cand = ok.copy()
-        cand[rows[u]] = False
-        exp_cand[b] = cand.sum()
-        for p in range(q_ptr[b], q_ptr[b + 1]):
-            t = q_items[p]
-            exp_above[p] = (cand & ((dense[u] > dense[u, t]) | ((dense[u] == dense[u, t]) & (j < t)))).sum()
-    return exp_above, exp_cand
+        assert_same(run_topk(torch, be, f, users, n, ptr, idx, N, dev, ones),
+                    run_topk(torch, be, f, users, n, ptr, idx, N, dev))
 
 
 @pytest.mark.parametrize("k,n", [(16, 1003), (64, 4099), (160, 2051)])
 def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     m = 40
-    f = _factors(torch, layout, dev, m, n, k, seed=7 * k + n)
-    ptr, idx, rows = _seen_csr(m, n, seed=k + n + 1)
-    dense = _dense(torch, be, f, m, n, dev)
+    f = factors(torch, layout, dev, m, n, k, seed=7 * k + n)
+    ptr, idx, rows = seen_csr(m, n, seed=k + n + 1)
+    dense = predict_dense(torch, be, f, m, n, dev)
     rng = np.random.default_rng(k)
     q_users = np.concatenate([np.arange(m), [5, 5]])
     counts = rng.integers(0, 6, q_users.size)
@@ -158,17 +98,17 @@ def test_masked_rank_count_equals_counts_over_the_dense_rows(k, n, monkeypatch):
     q_items = rng.integers(0, n, q_ptr[-1])
     for name, ok in _masks(n, seed=n + 1).items():
         allow = _bitmap(torch, ok, dev)
-        exp_above, exp_cand = _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items)
+        _, exp_above, exp_cand = ref.rank_counts_batch(dense[q_users], [rows[u] for u in q_users], ok, q_ptr,
+                                                       q_items)
         for s in SLICES + (0,):
             monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(s))
-            above, ncand, score = _rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev, allow)
+            score, above, ncand = run_rank(torch, be, f, q_users, n, ptr, idx, q_ptr, q_items, dev, allow)
             assert (above == exp_above).all(), (name, s)
             assert (ncand == exp_cand).all(), (name, s)
             assert (score == dense[np.repeat(q_users, counts), q_items]).all()
         if name == "all":                                                  # all ones == the unmasked call
             monkeypatch.setenv("ALS_RECOMMEND_SLICES", "0")
-            for g, e in zip(_rank_run(torch, be, f, n, (ptr, idx), q_users, q_ptr, q_items, dev),
-                            (above, ncand, score)):
+            for g, e in zip(run_rank(torch, be, f, q_users, n, ptr, idx, q_ptr, q_items, dev), (score, above, ncand)):
                 assert (g == e).all()
 
 
@@ -204,37 +144,37 @@ def _skip_case():
 
 @pytest.mark.parametrize("slices", [1, 2])
 def test_masked_topk_seen_cursor_passes_skipped_chunks(slices, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     ok, kinds, rows, ptr, idx = _skip_case()
     B = len(rows)
-    f = _factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
-    dense = _dense(torch, be, f, B, SKIP_N, dev)
+    f = factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
+    dense = predict_dense(torch, be, f, B, SKIP_N, dev)
     users = np.arange(B)[::-1].copy()
-    exp = _expected_masked(dense[users], [rows[u] for u in users], ok, SKIP_TOPN)
+    exp = ref.topn_batch(dense[users], [rows[u] for u in users], ok, SKIP_TOPN)
     assert (exp[2][kinds[users] != "saturated"] == SKIP_TOPN).all()       # full lists ...
     assert (exp[2][kinds[users] == "saturated"] == 4).all()               # ... and short ones, padded
     monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(slices))
-    _assert_same(_run_masked(torch, be, f, users, SKIP_N, ptr, idx, _bitmap(torch, ok, dev), SKIP_TOPN, dev), exp)
+    assert_same(run_topk(torch, be, f, users, SKIP_N, ptr, idx, SKIP_TOPN, dev, _bitmap(torch, ok, dev)), exp)
 
 
 @pytest.mark.parametrize("slices", [1, 2])
 def test_masked_rank_count_seen_cursor_passes_skipped_chunks(slices, monkeypatch):
-    torch, layout, be, dev = _env()
+    torch, layout, be, dev = env().short
     ok, kinds, rows, ptr, idx = _skip_case()
     B = len(rows)
-    f = _factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
-    dense = _dense(torch, be, f, B, SKIP_N, dev)
+    f = factors(torch, layout, dev, B, SKIP_N, SKIP_K, seed=131)
+    dense = predict_dense(torch, be, f, B, SKIP_N, dev)
     q_users = np.arange(B)[::-1].copy()
     # targets in front of, inside and behind the gap; allowed, denied, seen: 0 ... 5 per row
     pool = np.array([0, 31, 40, 64, 81, 95, 96, 130])
     counts = np.arange(B) % 6
     q_ptr = np.concatenate([[0], np.cumsum(counts)])
     q_items = np.concatenate([pool[(b + np.arange(c)) % pool.size] for b, c in enumerate(counts)])
-    exp_above, exp_cand = _expected_ranks(dense, rows, ok, q_users, q_ptr, q_items)
+    _, exp_above, exp_cand = ref.rank_counts_batch(dense[q_users], [rows[u] for u in q_users], ok, q_ptr, q_items)
     assert (exp_cand[kinds[q_users] == "saturated"] == 4).all()
     monkeypatch.setenv("ALS_RECOMMEND_SLICES", str(slices))
-    above, ncand, score = _rank_run(torch, be, f, SKIP_N, (ptr, idx), q_users, q_ptr, q_items, dev,
-                                    _bitmap(torch, ok, dev))
+    score, above, ncand = run_rank(torch, be, f, q_users, SKIP_N, ptr, idx, q_ptr, q_items, dev,
+                                   _bitmap(torch, ok, dev))
     assert (above == exp_above).all()
     assert (ncand == exp_cand).all()
     assert (score == dense[np.repeat(q_users, counts), q_items]).all()
@@ -246,7 +186,7 @@ M, N_ITEMS, K = 300, 1003, 24
 
 @pytest.fixture(scope="module")
 def fitted():
-    _env()
+    env()
     from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig
     r, c, v = make_ratings(M, N_ITEMS, 12000, seed=5, empty_users=(4,))
     cfg = ALSConfig(core=CoreConfig(n_factors=K, n_iters=3, lambda_u=3.0, lambda_v=3.0),
@@ -285,10 +225,10 @@ def test_model_recommend_with_filters_equals_the_masked_oracle(fitted, monkeypat
         ok = _allowed(kw, N_ITEMS)
         for N in (10, 128):
             items, scores = model.recommend(None, N, **kw)
-            tv, ti, _ = _expected_masked(P, seen, ok, N)
+            tv, ti, _ = ref.topn_batch(P, seen, ok, N)
             assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
         items, scores = model.recommend([7, 0, 7], 10, exclude_seen=False, **kw)
-        tv, ti, _ = _expected_masked(P[[7, 0, 7]], [np.empty(0, np.int64)] * 3, ok, 10)
+        tv, ti, _ = ref.topn_batch(P[[7, 0, 7]], [np.empty(0, np.int64)] * 3, ok, 10)
         assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
     items, scores = model.recommend([1, 2], 5, items=[])
     assert (items == -1).all() and np.isneginf(scores).all()
@@ -382,7 +322,7 @@ def test_recommend_with_folded_items_and_a_mask_over_the_joint_catalogue(fitted)
     Pj = np.concatenate([P, model.predict_new_items(folded).astype(np.float32)], axis=1)
     seen_j = [np.concatenate([seen[u], N_ITEMS + np.nonzero(~np.isnan(C_new[:, u]))[0]]) for u in range(M)]
     base = model.recommend(None, 10, new_items=folded)
-    tv, ti, _ = _expected_masked(Pj, seen_j, np.ones(nt, bool), 10)
+    tv, ti, _ = ref.topn_batch(Pj, seen_j, np.ones(nt, bool), 10)
     assert (base[0] == ti).all() and (base[1] == tv.astype(np.float64)).all()
     mask = rng.random(nt) < 0.3
     mask[N_ITEMS: N_ITEMS + 20] = True                                     # folded ids inside ...
@@ -391,7 +331,7 @@ def test_recommend_with_folded_items_and_a_mask_over_the_joint_catalogue(fitted)
                dict(items=np.arange(N_ITEMS, nt)), dict(filter_items=np.arange(N_ITEMS, nt))):
         ok = _allowed(kw, nt)
         items, scores = model.recommend(None, 10, new_items=folded, **kw)
-        tv, ti, _ = _expected_masked(Pj, seen_j, ok, 10)
+        tv, ti, _ = ref.topn_batch(Pj, seen_j, ok, 10)
         assert (items == ti).all() and (scores == tv.astype(np.float64)).all()
     items, _ = model.recommend(None, 10, new_items=folded, items=mask)
     assert (items >= N_ITEMS).any() and not (items >= N_ITEMS + 20).any()

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import row_auto_ref as R
-from tests.test_gpu_kernels import _record_margins
+from tests.gpu_common import record_margins
 
 pytestmark = pytest.mark.gpu
 
@@ -142,7 +142,7 @@ def test_estimate_matches_reference(k, gram, planes, limit):
             assert dev <= EST_TOL, (r, b.classes[r], got, ref["est"])
         else:
             assert got > limit, (r, b.classes[r], got, ref["est"])           # inf: the fp32 factorisation broke down
-    _record_margins(f"estimate k={k} {gram} planes={planes} limit={limit:g}", {"rel_dev": worst, "tolerance": EST_TOL})
+    record_margins(f"estimate k={k} {gram} planes={planes} limit={limit:g}", {"rel_dev": worst, "tolerance": EST_TOL})
 
 
 @pytest.mark.parametrize("k,gram,planes", CASES, ids=CASE_IDS)
@@ -245,7 +245,7 @@ def test_fp32_rows_hold_the_documented_error(k, gram, planes):
         units = rel / (max(ref[r]["est"], 1.0) * U24)
         print(f"fp32 row k={k} {gram} row {r} {b.classes[r]}: est {ref[r]['est']:.4g} rel err {rel:.3e} units {units:.1f}")
         worst_units, worst_rel = max(worst_units, units), max(worst_rel, rel)
-    _record_margins(f"fp32 rows k={k} {gram} planes={planes}", {"err_units": worst_units, "rel_err": worst_rel,
+    record_margins(f"fp32 rows k={k} {gram} planes={planes}", {"err_units": worst_units, "rel_err": worst_rel,
                                                                 "tolerance_units": FP32_ERR_UNITS})
     assert worst_units <= FP32_ERR_UNITS
 

@@ -36,7 +36,7 @@ import numpy as np
 import pytest
 
 from tests import stats_predict_ref as ref
-from tests.test_gpu_kernels import _env, _record_margins
+from tests.gpu_common import env, ptr, ratio, record_margins, same_bits, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -47,16 +47,11 @@ U32, U64 = ref.U32, ref.U64
 
 @functools.lru_cache(maxsize=None)
 def _E():
-    return _env()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+    return env()
 
 
 def _up(a):
-    torch, dev = _E()[0], _E()[5]
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return upload(a, _E().dev)
 
 
 def _up_tail(a):
@@ -79,7 +74,7 @@ class _Out:
 
     @property
     def ptr(self):
-        return _ptr(self.buf)
+        return ptr(self.buf)
 
     def get(self):
         """The used part as numpy, after checking that nothing behind it was written."""
@@ -95,19 +90,6 @@ def _sync():
     _E()[0].cuda.synchronize()
 
 
-def _ratio(got, exp, bound, what):
-    err = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(exp, dtype=np.float64))
-    bound = np.asarray(bound, dtype=np.float64)
-    assert np.isfinite(err).all(), what
-    pos = bound > 0
-    assert not err[~pos].any(), f"{what}: non-zero where every term is zero"
-    return float(np.max(err[pos] / bound[pos])) if pos.any() else 0.0
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 # ---- predictions -----------------------------------------------------------------------------------------------------
 def _predict_dev(inp):
     return dict(U=_up(inp.U), Z=_up(inp.Z), b_u=_up(inp.b_u), b_i=_up(inp.b_i), mu=_f64(inp.mu))
@@ -117,8 +99,8 @@ def _dense(inp, d, m, n):
     """als_predict_dense on the first m users and n items of inp."""
     be = _E()[4]
     out = _Out(m * n)
-    rc = be.lib.als_predict_dense(inp.k, inp.ld, m, n, _ptr(d["U"]), _ptr(d["Z"]), _ptr(d["b_u"]), _ptr(d["b_i"]),
-                                  _ptr(d["mu"]), out.ptr, be._stream())
+    rc = be.lib.als_predict_dense(inp.k, inp.ld, m, n, ptr(d["U"]), ptr(d["Z"]), ptr(d["b_u"]), ptr(d["b_i"]),
+                                  ptr(d["mu"]), out.ptr, be._stream())
     assert rc == 0
     _sync()
     return out.get().reshape(m, n)
@@ -128,8 +110,8 @@ def _at(inp, d, us, is_):
     be = _E()[4]
     out = _Out(us.size)
     us_d, is_d = _up(us), _up(is_)                      # (held until the call has run)
-    rc = be.lib.als_predict_at(inp.k, inp.ld, us.size, _ptr(us_d), _ptr(is_d), _ptr(d["U"]), _ptr(d["Z"]),
-                               _ptr(d["b_u"]), _ptr(d["b_i"]), _ptr(d["mu"]), out.ptr, be._stream())
+    rc = be.lib.als_predict_at(inp.k, inp.ld, us.size, ptr(us_d), ptr(is_d), ptr(d["U"]), ptr(d["Z"]),
+                               ptr(d["b_u"]), ptr(d["b_i"]), ptr(d["mu"]), out.ptr, be._stream())
     assert rc == 0
     _sync()
     return out.get()
@@ -179,8 +161,8 @@ def test_predict_at_without_pairs_is_a_no_op():
     be = _E()[4]
     out = _Out(4)
     idx = _up(np.zeros(4, np.int32))
-    args = (_ptr(d["U"]), _ptr(d["Z"]), _ptr(d["b_u"]), _ptr(d["b_i"]), _ptr(d["mu"]))
-    assert be.lib.als_predict_at(inp.k, inp.ld, 0, _ptr(idx), _ptr(idx), *args, out.ptr, be._stream()) == 0
+    args = (ptr(d["U"]), ptr(d["Z"]), ptr(d["b_u"]), ptr(d["b_i"]), ptr(d["mu"]))
+    assert be.lib.als_predict_at(inp.k, inp.ld, 0, ptr(idx), ptr(idx), *args, out.ptr, be._stream()) == 0
     assert be.lib.als_predict_at(inp.k, inp.ld, 0, None, None, *args, None, be._stream()) == 0
     _sync()
     assert out.untouched()
@@ -193,10 +175,10 @@ def test_predictions_real_inputs_within_the_derived_bound(k):
     P, S = ref.expected_predict_real(inp)
     bound = (inp.ld + 3) * U32 * S
     us, is_ = np.divmod(np.arange(inp.m * inp.n), inp.n)
-    ratios = {"dense": _ratio(_dense(inp, d, inp.m, inp.n), P, bound, "dense"),
-              "at": _ratio(_at(inp, d, us.astype(np.int32), is_.astype(np.int32)).reshape(inp.m, inp.n), P, bound, "at")}
+    ratios = {"dense": ratio(_dense(inp, d, inp.m, inp.n), P, bound, "dense"),
+              "at": ratio(_at(inp, d, us.astype(np.int32), is_.astype(np.int32)).reshape(inp.m, inp.n), P, bound, "at")}
     print(f"predict k={k}", ratios)
-    _record_margins(f"predict k={k}", ratios)
+    record_margins(f"predict k={k}", ratios)
     assert all(r <= 1.0 for r in ratios.values()), ratios
 
 
@@ -213,7 +195,7 @@ def test_compose_z(k):
                 inp = ref.compose_inputs(k, n, D, kind, seed=1000 * D + n + k)
                 Z = _Out(n * inp.ld)
                 V, X, W = _up(inp.V), (_up(inp.X) if D else None), (_up(inp.W) if D else None)
-                rc = be.lib.als_compose_z(n, inp.ld, D, _ptr(V), _ptr(X), _ptr(W), Z.ptr, be._stream())
+                rc = be.lib.als_compose_z(n, inp.ld, D, ptr(V), ptr(X), ptr(W), Z.ptr, be._stream())
                 assert rc == 0
                 _sync()
                 got = Z.get().reshape(n, inp.ld)
@@ -222,9 +204,9 @@ def test_compose_z(k):
                 if kind == "exact" or D == 0:
                     assert np.array_equal(got, exp.astype(np.float32)), (D, n, kind)
                 else:
-                    worst = max(worst, _ratio(got, exp, D * U32 * S + U32 * np.abs(exp), f"compose D={D} n={n}"))
+                    worst = max(worst, ratio(got, exp, D * U32 * S + U32 * np.abs(exp), f"compose D={D} n={n}"))
     print(f"compose_z k={k}", worst)
-    _record_margins(f"compose_z k={k}", {"Z": worst})
+    record_margins(f"compose_z k={k}", {"Z": worst})
     assert worst <= 1.0
 
 
@@ -241,8 +223,8 @@ def _stats(inp, d):
     be = _E()[4]
     nblk = (d["ntasks"] + 3) // 4
     partials, out = _Out(2 * nblk, "float64"), _Out(2, "float64")
-    rc = be.lib.als_residual_stats(inp.k, inp.ld, _ptr(d["indptr"]), _ptr(d["indices"]), _ptr(d["vals"]), _ptr(d["U"]),
-                                   _ptr(d["Z"]), _ptr(d["b_u"]), _ptr(d["b_i"]), _ptr(d["mu"]), _ptr(d["tasks"]),
+    rc = be.lib.als_residual_stats(inp.k, inp.ld, ptr(d["indptr"]), ptr(d["indices"]), ptr(d["vals"]), ptr(d["U"]),
+                                   ptr(d["Z"]), ptr(d["b_u"]), ptr(d["b_i"]), ptr(d["mu"]), ptr(d["tasks"]),
                                    d["ntasks"], partials.ptr, out.ptr, be._stream())
     assert rc == 0
     _sync()
@@ -253,14 +235,14 @@ def _check_stats(inp, key):
     d = _stats_dev(inp)
     got, part = _stats(inp, d)
     again, part2 = _stats(inp, d)
-    assert _same_bits(got, again) and _same_bits(part, part2), "not reproducible"
+    assert same_bits(got, again) and same_bits(part, part2), "not reproducible"
     s0, s1, b0, b1 = ref.expected_stats(inp)
     if inp.kind == "exact":
         assert got[0] == s0 and got[1] == s1, (got, s0, s1)
         return
     ratios = {"sum_d": float(abs(got[0] - s0) / b0), "sum_d2": float(abs(got[1] - s1) / b1)}
     print(key, ratios)
-    _record_margins(key, ratios)
+    record_margins(key, ratios)
     assert all(r <= 1.0 for r in ratios.values()), (ratios, got, s0, s1)
 
 
@@ -285,7 +267,7 @@ def test_residual_stats_many_short_rows(kind):
 def _sumsq(x_dev, n):
     be = _E()[4]
     partials, out = _Out(be.lib.als_sumsq_partials(), "float64"), _Out(1, "float64")
-    assert be.lib.als_sumsq(_ptr(x_dev), n, partials.ptr, out.ptr, be._stream()) == 0
+    assert be.lib.als_sumsq(ptr(x_dev), n, partials.ptr, out.ptr, be._stream()) == 0
     _sync()
     partials.get()
     return out.get()[0]
@@ -294,7 +276,7 @@ def _sumsq(x_dev, n):
 def _sum_pairs(x_dev, npairs):
     be = _E()[4]
     partials, out = _Out(2 * be.lib.als_sumsq_partials(), "float64"), _Out(2, "float64")
-    assert be.lib.als_sum_pairs(_ptr(x_dev), npairs, partials.ptr, out.ptr, be._stream()) == 0
+    assert be.lib.als_sum_pairs(ptr(x_dev), npairs, partials.ptr, out.ptr, be._stream()) == 0
     _sync()
     partials.get()
     return out.get().copy()
@@ -314,7 +296,7 @@ def test_sumsq_tails_and_block_cap():
         else:
             worst = max(worst, abs(got - s) / (n * U64 * s))
     print("sumsq", worst)
-    _record_margins("sumsq", {"sumsq": worst})
+    record_margins("sumsq", {"sumsq": worst})
     assert worst <= 1.0
 
 
@@ -332,7 +314,7 @@ def test_sum_pairs_tails_and_block_cap():
         else:
             worst = max(worst, float(np.max(np.abs(got - s) / (npairs * U64 * a))))
     print("sum_pairs", worst)
-    _record_margins("sum_pairs", {"sum_pairs": worst})
+    record_margins("sum_pairs", {"sum_pairs": worst})
     assert worst <= 1.0
 
 
@@ -344,8 +326,8 @@ def _history(arrays_dev, lengths, stats, nnz, mu):
     stats_d = _f64(*stats)
     args = []
     for x, n in zip(arrays_dev, lengths):
-        args += [_ptr(x), n]
-    assert be.lib.als_history_row(*args, _ptr(stats_d), nnz, mu_t.ptr, partials.ptr, row.ptr, be._stream()) == 0
+        args += [ptr(x), n]
+    assert be.lib.als_history_row(*args, ptr(stats_d), nnz, mu_t.ptr, partials.ptr, row.ptr, be._stream()) == 0
     _sync()
     partials.get()
     return row.get().copy(), mu_t.get()[0]
@@ -391,7 +373,7 @@ def test_factor_scale(nfloats):
     positions = ref.scale_positions(nfloats)
 
     def call(F_dev, F_host):
-        assert be.lib.als_factor_scale(_ptr(F_dev), nfloats, sc.ptr, be._stream()) == 0
+        assert be.lib.als_factor_scale(ptr(F_dev), nfloats, sc.ptr, be._stream()) == 0
         _sync()
         got = sc.get()
         assert not got[2:4].view(np.int32).any(), "work words not reset"
@@ -424,7 +406,7 @@ def test_bad_arguments_are_rejected_before_any_launch():
     x = _up(np.ones(1024, dtype=np.float32))
     idx = _up(np.zeros(16, dtype=np.int32))
     ptr64 = _up(np.zeros(16, dtype=np.int64))
-    p, off4 = _ptr(x), C.c_void_p(x.data_ptr() + 4)
+    p, off4 = ptr(x), C.c_void_p(x.data_ptr() + 4)
     outs = [_Out(64, "float64") for _ in range(3)]
     o0, o1, o2 = (o.ptr for o in outs)
     fo = _Out(64)
@@ -434,19 +416,19 @@ def test_bad_arguments_are_rejected_before_any_launch():
     for bad in (1, 2, 3, 7, -4):
         assert lib.als_factor_scale(p, bad, fo.ptr, None) == BADARG
     assert lib.als_factor_scale(off4, 8, fo.ptr, None) == BADARG
-    pa = lambda k, ld, npairs: lib.als_predict_at(k, ld, npairs, _ptr(idx), _ptr(idx), p, p, p, p, _ptr(mu), fo.ptr, None)  # noqa: E731
+    pa = lambda k, ld, npairs: lib.als_predict_at(k, ld, npairs, ptr(idx), ptr(idx), p, p, p, p, ptr(mu), fo.ptr, None)  # noqa: E731
     assert pa(50, 48, 4) == BADARG and pa(50, 80, 4) == BADARG and pa(161, 176, 4) == BADK and pa(0, 0, 4) == BADK
     assert pa(50, 64, -1) == BADARG
-    pd = lambda k, ld, m, n: lib.als_predict_dense(k, ld, m, n, p, p, p, p, _ptr(mu), fo.ptr, None)  # noqa: E731
+    pd = lambda k, ld, m, n: lib.als_predict_dense(k, ld, m, n, p, p, p, p, ptr(mu), fo.ptr, None)  # noqa: E731
     assert pd(50, 48, 2, 2) == BADARG and pd(161, 176, 2, 2) == BADK
     assert pd(50, 64, -1, 2) == BADARG and pd(50, 64, 2, -1) == BADARG and pd(50, 64, 0, 2) == BADARG
-    rs = lambda k, ld, nt: lib.als_residual_stats(k, ld, _ptr(ptr64), _ptr(idx), p, p, p, p, p, _ptr(mu), _ptr(idx), nt,  # noqa: E731
+    rs = lambda k, ld, nt: lib.als_residual_stats(k, ld, ptr(ptr64), ptr(idx), p, p, p, p, p, ptr(mu), ptr(idx), nt,  # noqa: E731
                                                  o0, o1, None)
     assert rs(50, 48, 1) == BADARG and rs(161, 176, 1) == BADK and rs(50, 64, -1) == BADARG and rs(50, 64, 0) == BADARG
     cz = lambda n, ld, D: lib.als_compose_z(n, ld, D, p, p, p, fo.ptr, None)  # noqa: E731
     assert cz(-1, 16, 1) == BADARG and cz(2, 0, 1) == BADARG and cz(2, 16, -1) == BADARG
     assert lib.als_compose_z(2, 16, 1, p, None, p, fo.ptr, None) == BADARG
-    hr = lambda nU, nnz, U=p: lib.als_history_row(U, nU, p, 4, p, 4, p, 4, _ptr(mu), nnz, o2, o0, o1, None)  # noqa: E731
+    hr = lambda nU, nnz, U=p: lib.als_history_row(U, nU, p, 4, p, 4, p, 4, ptr(mu), nnz, o2, o0, o1, None)  # noqa: E731
     assert hr(-1, 5) == BADARG and hr(4, -1) == BADARG and hr(4, 5, off4) == BADARG
     _sync()
     assert all(o.untouched() for o in outs) and fo.untouched()

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from tests.cpu_backend import NumpyBackend
-from tests.test_gpu_kernels import _env, _pad, _random_side
+from tests.gpu_common import env, pad, random_side
 
 pytestmark = pytest.mark.gpu
 
@@ -44,15 +44,15 @@ TOL = {"f16x2": (6e-5, 2e-6), "f64": (6e-7, 6e-7)}
 def _solve(k, gram, nslots_list, seed):
     """One als_row_solve over rows split into `nslots_list` slots plus the ordinary rows.  Returns what the checks
     need: outputs, the workspace after the full call and after the partials-only call, the reference solution."""
-    torch, layout, side_dev, tasks_dev, be, dev = _env(gram)
+    torch, layout, side_dev, tasks_dev, be, dev = env(gram)
     from collaborative_filtering_amd.als import _TasksDev
     assert layout.SPLIT_CHUNK == CHUNK
     lens = [(n - 1) * CHUNK + LAST_SEG for n in nslots_list] + ORDINARY
     nrows, ncols = len(lens), max(lens) + 1000
-    side = _random_side(layout, nrows, ncols, lens, seed=seed)
+    side = random_side(layout, nrows, ncols, lens, seed=seed)
     rng = np.random.default_rng(seed + 1)
     ld = layout.padded_k(k)
-    F = _pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)
+    F = pad(rng.normal(scale=0.3, size=(ncols, k)), ld, 1)
     b_self = rng.normal(scale=0.2, size=nrows).astype(np.float32)
     b_other = rng.normal(scale=0.2, size=ncols).astype(np.float32)
     mu, lam, lam_b = 3.3, 2.5, 1.7

@@ -1,65 +1,20 @@
 """T5' (GPU): the sharded code path with the REAL kernels - two ranks sharing cuda:0, collectives over
 gloo (RCCL refuses two ranks on one device; the 8-GPU node is the driver's).  Every rank must end with the
 same factors, and those must match the one-rank HIP fit and the reference fixture."""
-import os
-import socket
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 
+from tests.dist_common import sharded_fit, single_fit
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, name, gs_mode, outdir):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tests.common import Golden
-        from tests.test_gpu_parity import _model_for
-        g = Golden(name)
-        r, c, v = g.train
-        model = _model_for(g, device="cuda:0", gs_mode=gs_mode, process_group="world")
-        model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
-                      min_iters=g.cfg["min_iters"], verbose=0)
-        assert model._eng.world == world and model._eng.multi
-        np.savez(os.path.join(outdir, f"rank{rank}.npz"), U=model.U, V=model.V, b_u=model.b_u, b_i=model.b_i,
-                 mu=model.mu, rmse=np.asarray(model.history["train_rmse"]),
-                 **{"W_" + f: model.W[f] for f in g.cfg["feats"]})
-    finally:
-        dist.destroy_process_group()
 
 
 def _run(name, gs_mode=None, world=2):
-    import torch.multiprocessing as mp
-    with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_worker, args=(world, _free_port(), name, gs_mode, d), nprocs=world, join=True)
-        return [dict(np.load(os.path.join(d, f"rank{r}.npz"))) for r in range(world)]
+    return sharded_fit(name, gs_mode, world, gpu=True)
 
 
 def _single(name):
-    from tests.common import Golden
-    from tests.test_gpu_parity import _model_for
-    g = Golden(name)
-    r, c, v = g.train
-    model = _model_for(g, device="cuda:0")
-    model.fit_coo(r, c, v, (g.m, g.n), features=g.features or None, tol=g.cfg["tol"],
-                  min_iters=g.cfg["min_iters"], verbose=0)
-    return g, model
+    return single_fit(name, gpu=True)
 
 
 @pytest.mark.parametrize("name", ["g2_bias_pop", "g4_feat_uw2", "g5_graph_a0.5"])

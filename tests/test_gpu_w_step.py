@@ -22,16 +22,12 @@ import numpy as np
 import pytest
 
 from tests import w_step_ref as ref
-from tests.test_gpu_kernels import _env, _record_margins
+from tests.gpu_common import env as gpu_env, ptr, ratio, record_margins, same_bits, upload
 
 pytestmark = pytest.mark.gpu
 
 KS = sorted(ref.CASES)
 U32, U64 = ref.U32, ref.U64
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _twin_scale(torch, dev, ld, dtype, s):
@@ -49,7 +45,7 @@ def _run(env, inp, twin=1.0, wrapper=False):
     lib = be.lib
     k, ld, n, f64 = inp.k, inp.ld, inp.n, inp.f64
     dt = torch.float64 if f64 else torch.float32
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)       # noqa: E731
+    up = lambda a: upload(a, dev)       # noqa: E731
     gram = up(inp.gram)
     if twin != 1.0:
         gram = gram * _twin_scale(torch, dev, ld, dt, twin)
@@ -69,8 +65,8 @@ def _run(env, inp, twin=1.0, wrapper=False):
         p = _hip.WParams()
         p.k, p.ld, p.phase, p.nfeat, p.f64 = k, ld, 0, inp.nfeat, int(f64)
         p.item_begin, p.item_end = inp.ib, inp.ie
-        p.gram, p.rhs, p.colsum, p.V, p.b_new, p.b_old = _ptr(gram), _ptr(rhs), _ptr(colsum), _ptr(V), _ptr(b_new), _ptr(b_old)
-        p.D, p.X, p.feat_off, p.W, p.H, p.nrows_h = inp.D, _ptr(X), _ptr(feat_off), _ptr(W), _ptr(H), nrows_h
+        p.gram, p.rhs, p.colsum, p.V, p.b_new, p.b_old = ptr(gram), ptr(rhs), ptr(colsum), ptr(V), ptr(b_new), ptr(b_old)
+        p.D, p.X, p.feat_off, p.W, p.H, p.nrows_h = inp.D, ptr(X), ptr(feat_off), ptr(W), ptr(H), nrows_h
         st = be._stream()
         assert lib.als_w_normal_equations(C.byref(p), st) == 0
         npairs, kb, nch = d * (d + 1) // 2, ld // 16, inp.nchunks
@@ -78,7 +74,7 @@ def _run(env, inp, twin=1.0, wrapper=False):
         partA, partB = nan64(npairs * nch * (kb * (kb + 1) // 2) * 256), nan64(d * nch * ld)
         A, B = nan64(d * k, d * k), nan64(d * k)
         p.phase, p.feat_index, p.feat_col0, p.feat_d, p.nchunks = 1, inp.feat, c0, d, nch
-        p.partA, p.partB, p.A_out, p.B_out = _ptr(partA), _ptr(partB), _ptr(A), _ptr(B)
+        p.partA, p.partB, p.A_out, p.B_out = ptr(partA), ptr(partB), ptr(A), ptr(B)
         assert lib.als_w_normal_equations(C.byref(p), st) == 0
     stat = torch.full((n, 2), 7.0, dtype=torch.float32, device=dev)
     be.item_stats(k=k, ld=ld, item_begin=inp.ib, item_end=inp.ie, gram=gram, rhs=rhs, colsum=colsum, sumr=sumr,
@@ -119,15 +115,6 @@ def _check_exact(env, inp, out):
     assert np.array_equal(out["stat"][sl], stat[sl].astype(np.float32))
 
 
-def _ratio(got, exp, bound, what):
-    err = np.abs(np.asarray(got, dtype=exp.dtype) - exp)
-    bound = np.asarray(bound, dtype=exp.dtype)
-    assert np.isfinite(err).all(), what
-    pos = bound > 0
-    assert not err[~pos].any(), f"{what}: non-zero where every term is zero"
-    return float(np.max(err[pos] / bound[pos])) if pos.any() else 0.0
-
-
 def _check_real(env, inp, out, key):
     torch = env[0]
     sl = slice(inp.ib, inp.ie)
@@ -136,15 +123,15 @@ def _check_real(env, inp, out, key):
     wide = inp.f64                                   # long double reference where the kernel works in fp64
     ratios = {}
     H, S = ref.expected_h(inp, wide=wide)
-    ratios["H"] = _ratio(out["H"][:, sl], H[:, sl], (KP + D + 4) * u * S[:, sl] + u * np.abs(H[:, sl]), "H")
+    ratios["H"] = ratio(out["H"][:, sl], H[:, sl], (KP + D + 4) * u * S[:, sl] + u * np.abs(H[:, sl]), "H")
     d = inp.dims[inp.feat]
     A, SA, B, SB = ref.expected_ab(inp, out["H"][inp.feat], wide=wide and m * d * d * inp.k * inp.k <= 1e8)
-    ratios["B"] = _ratio(out["B"], B, (m + 2) * U64 * SB, "B")
-    ratios["A"] = _ratio(out["A"].numpy(), A, ((m + 2) * U64 + (0.0 if inp.f64 else U32)) * SA, "A")
+    ratios["B"] = ratio(out["B"], B, (m + 2) * U64 * SB, "B")
+    ratios["A"] = ratio(out["A"].numpy(), A, ((m + 2) * U64 + (0.0 if inp.f64 else U32)) * SA, "A")
     stat, Ss = ref.expected_stats(inp, wide=wide)
-    ratios["stat"] = _ratio(out["stat"][sl], stat[sl], (KP + 4) * u * Ss[sl] + U32 * np.abs(stat[sl]), "stat")
+    ratios["stat"] = ratio(out["stat"][sl], stat[sl], (KP + 4) * u * Ss[sl] + U32 * np.abs(stat[sl]), "stat")
     print(key, ratios)
-    _record_margins(key, ratios)
+    record_margins(key, ratios)
     # worst-case bounds (module docstring), derived, not tuned; the observed error / bound of every quantity goes to the
     # ALS_RECORD_MARGINS file (profiles/w_step_kernel_test_margins.json once recorded on the device)
     assert all(r <= 1.0 for r in ratios.values()), ratios
@@ -153,16 +140,11 @@ def _check_real(env, inp, out, key):
     _untouched_outside(inp, out)
 
 
-def _same_bits(a, b):
-    a, b = (x.numpy() if hasattr(x, "numpy") else x for x in (a, b))
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 @pytest.mark.parametrize("f64", [0, 1])
 @pytest.mark.parametrize("k", KS)
 def test_w_step_exact_inputs(k, f64):
     """Integer inputs: H, A, B equal the exact values, the statistics their float rounding; A bitwise symmetric."""
-    env = _env()
+    env = gpu_env()
     inp = ref.build_inputs(k=k, kind="exact", f64=f64, seed=k, **ref.CASES[k])
     _check_exact(env, inp, _run(env, inp))
 
@@ -172,12 +154,12 @@ def test_w_step_exact_inputs(k, f64):
 def test_w_step_real_inputs(k, f64):
     """Real inputs within the derived bounds, and the lower-twin rule: with the upper triangle of every diagonal
     Gram block scaled by 1.5 every output keeps every bit."""
-    env = _env()
+    env = gpu_env()
     inp = ref.build_inputs(k=k, kind="real", f64=f64, seed=1000 + k, **ref.CASES[k])
     out = _run(env, inp)
     out15 = _run(env, inp, twin=1.5)
     for name in ("H", "A", "B", "stat"):
-        assert _same_bits(out[name], out15[name]), f"{name} depends on the upper twin of a diagonal block"
+        assert same_bits(out[name], out15[name]), f"{name} depends on the upper twin of a diagonal block"
     _check_real(env, inp, out, f"w_step k={k} {'f64' if f64 else 'f32'}")
 
 
@@ -187,7 +169,7 @@ def test_w_step_real_inputs(k, f64):
 def test_w_step_extra_cases(case, kind, f64):
     """A shard whose last chunk is empty, and the path through HipBackend.w_item_vectors / w_accumulate with the
     wrapper's own chunking (d = 20, 4900 items: 19 chunks of 258)."""
-    env = _env()
+    env = gpu_env()
     cfg = ref.EXTRA_CASES[case]
     inp = ref.build_inputs(kind=kind, f64=f64, seed=77, **cfg)
     out = _run(env, inp, wrapper=(case == "wrapper"))
@@ -200,7 +182,7 @@ def test_w_step_extra_cases(case, kind, f64):
 def test_w_step_bad_arguments_are_rejected():
     """Every argument check of als_w_normal_equations and of both statistics entry points returns before any launch
     (the pointers below are not device memory); an empty item range is a no-op."""
-    torch, _, _, _, be, dev = _env()
+    torch, _, _, _, be, dev = gpu_env()
     from collaborative_filtering_amd import _hip
     lib = be.lib
     BADARG, BADK = -1, -2
@@ -250,6 +232,6 @@ def test_w_step_bad_arguments_are_rejected():
     for f64 in (False, True):
         stat = torch.full((4, 2), 7.0, dtype=torch.float32, device=dev)
         fn = lib.als_item_stats_f64 if f64 else lib.als_item_stats
-        assert fn(50, 64, 3, 3, *([_ptr(stat)] * 10), None) == 0
+        assert fn(50, 64, 3, 3, *([ptr(stat)] * 10), None) == 0
         torch.cuda.synchronize()
         assert bool((stat == 7.0).all())

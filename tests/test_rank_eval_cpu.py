@@ -1,51 +1,13 @@
 """ALS.rank_of / rank_of_new host logic and cv.rank_metrics / fold_in_rank_metrics, without a GPU: the engine runs on
-a numpy stand-in backend whose rank_count restates the contract of als_rank_count (predict_dense scores, seen items
-and NaN scores no candidates, `above` = candidates that precede the target in (score desc, item asc))."""
+the numpy stand-in backend, whose rank_count and fold_in are the contracts of als_rank_count and als_fold_in in
+tests/serving_ref.py (`rank_counts`, `fold_in_user`) over predict_dense scores."""
 import numpy as np
 import pytest
-import torch
 
 from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, cv
+from tests import serving_ref as ref
+from tests.cpu_backend import NumpyBackend
 from tests.synth import make_ratings
-from tests.test_recommend_cpu import RecommendNumpyBackend
-
-
-class RankNumpyBackend(RecommendNumpyBackend):
-    def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above,
-                   n_cand):
-        u = q_users.long()
-        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
-        ptr = q_ptr.numpy()
-        for b, uu in enumerate(u.tolist()):
-            cand = ~np.isnan(S[b])
-            if seen_ptr is not None:
-                cand[seen_idx[seen_ptr[uu]: seen_ptr[uu + 1]].numpy()] = False
-            n_cand[b] = int(cand.sum())
-            j = np.arange(n)
-            for p in range(ptr[b], ptr[b + 1]):
-                t = int(q_items[p])
-                s = S[b, t]
-                t_score[p] = float(s)
-                above[p] = -1 if np.isnan(s) else int((cand & ((S[b] > s) | ((S[b] == s) & (j < t)))).sum())
-
-    def fold_in(self, *, k, ld, indptr, indices, vals, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, U_out, b_u_out,
-                status):
-        assert n_sweeps == 0                             # the fixed point: the bordered system of als_fold_in
-        ptr = indptr.numpy()
-        U_out.zero_()
-        b_u_out.zero_()
-        for r in range(ptr.size - 1):
-            S = indices[ptr[r]: ptr[r + 1]].long()
-            if S.numel() == 0:
-                continue
-            Zs = Z[S, :k].double().numpy()
-            res = vals[ptr[r]: ptr[r + 1]].double().numpy() - mu.item() - b_i[S].double().numpy()
-            h = Zs.sum(axis=0)
-            M = np.block([[Zs.T @ Zs + (lam_u + 1e-10) * np.eye(k), h[:, None]],
-                          [h[None, :], np.array([[S.numel() + lam_bu + 1e-10]])]])
-            x = np.linalg.solve(M, np.append(Zs.T @ res, res.sum()))
-            U_out[r, :k] = torch.from_numpy(x[:k]).to(U_out.dtype)
-            b_u_out[r] = float(x[k])
 
 
 M, N_ITEMS = 30, 25
@@ -54,7 +16,7 @@ M, N_ITEMS = 30, 25
 def _fit(r, c, v, shape, k=5):
     cfg = ALSConfig(core=CoreConfig(n_factors=k, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    return ALS(cfg, device="cpu", backend=RankNumpyBackend()).fit_coo(r, c, v, shape, tol=None, verbose=0)
+    return ALS(cfg, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, shape, tol=None, verbose=0)
 
 
 @pytest.fixture(scope="module")
@@ -65,10 +27,8 @@ def fitted():
 
 def _brute_rank(P, seen, u, t):
     """(rank, candidates) of item t for user u from the dense predictions, the seen items masked."""
-    cand = ~np.isnan(P[u])
-    cand[list(seen)] = False
-    j = np.arange(P.shape[1])
-    return int((cand & ((P[u] > P[u, t]) | ((P[u] == P[u, t]) & (j < t)))).sum()), int(cand.sum())
+    _, above, n_cand = ref.rank_counts(P[u], list(seen), None, [t])
+    return int(above[0]), n_cand
 
 
 # ------------------------------------------------------------------------------------------ rank_of
@@ -113,7 +73,7 @@ def test_rank_of_argument_errors(fitted):
     model = fitted[0]
     cfg = ALSConfig(core=CoreConfig(n_factors=3, n_iters=1, lambda_u=1.0, lambda_v=1.0))
     with pytest.raises(RuntimeError, match="Model must be fitted before prediction."):
-        ALS(cfg, device="cpu", backend=RankNumpyBackend()).rank_of([0], [0])
+        ALS(cfg, device="cpu", backend=NumpyBackend()).rank_of([0], [0])
     for users in ([M], [-1]):
         with pytest.raises(IndexError):
             model.rank_of(users, [0])

@@ -1,31 +1,11 @@
-"""ALS.recommend host logic and cv.ranking_at_k, without a GPU: the engine runs on a numpy stand-in backend whose
-recommend_topk restates the kernel's contract (predict_dense scores, seen items out, stable (score desc, item asc))."""
+"""ALS.recommend host logic and cv.ranking_at_k, without a GPU: the engine runs on the numpy stand-in backend, whose
+recommend_topk is the kernel's contract in tests/serving_ref.py (`topn`) over predict_dense scores."""
 import numpy as np
 import pytest
-import torch
 
 from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, cv
 from tests.cpu_backend import NumpyBackend
 from tests.synth import make_ratings
-
-
-class RecommendNumpyBackend(NumpyBackend):
-    def recommend_topk(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx,
-                       top_cnt):
-        u = users.long()
-        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
-        top_val.fill_(-np.inf)
-        top_idx.fill_(-1)
-        for b, uu in enumerate(u.tolist()):
-            keep = np.ones(n, bool)
-            if seen_ptr is not None:
-                keep[seen_idx[seen_ptr[uu]: seen_ptr[uu + 1]].numpy()] = False
-            keep &= ~np.isnan(S[b])
-            items = np.nonzero(keep)[0]
-            order = np.lexsort((items, -S[b, items]))[:topn]
-            top_val[b, : order.size] = torch.from_numpy(S[b, items[order]])
-            top_idx[b, : order.size] = torch.from_numpy(items[order].astype(np.int32))
-            top_cnt[b] = order.size
 
 
 M, N_ITEMS = 30, 25
@@ -36,14 +16,13 @@ def fitted():
     r, c, v = make_ratings(M, N_ITEMS, 300, seed=3, empty_users=(4,))
     cfg = ALSConfig(core=CoreConfig(n_factors=5, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    model = ALS(cfg, device="cpu", backend=RecommendNumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None,
-                                                                            verbose=0)
+    model = ALS(cfg, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
     return model, r, c
 
 
 def test_recommend_before_fit_raises_like_predict():
     cfg = ALSConfig(core=CoreConfig(n_factors=3, n_iters=1, lambda_u=1.0, lambda_v=1.0))
-    model = ALS(cfg, device="cpu", backend=RecommendNumpyBackend())
+    model = ALS(cfg, device="cpu", backend=NumpyBackend())
     with pytest.raises(RuntimeError, match="Model must be fitted before prediction."):
         model.recommend()
 

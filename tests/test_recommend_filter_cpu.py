@@ -1,6 +1,6 @@
 """Item allow / block lists (`items=` / `filter_items=`) of ALS.recommend*, rank_of* and the cv ranking measures,
-without a GPU: validation, bitmap packing against a numpy definition, the host orchestration over a numpy stand-in
-backend whose *_masked methods restate the contract of als_recommend_topk_masked / als_rank_count_masked, the cv
+without a GPU: validation, bitmap packing against a numpy definition, the host orchestration over the numpy stand-in
+backend, whose *_masked methods are the contracts of tests/serving_ref.py with `allowed` unpacked from the bitmap, the cv
 pass-through with its dropped-pair counts, and the presence of the new symbols in the built library."""
 import ctypes
 import os
@@ -11,81 +11,13 @@ import torch
 
 from collaborative_filtering_amd import ALS, ALSConfig, BiasesConfig, CoreConfig, cv, validate
 from collaborative_filtering_amd.serving import FoldedItems, pack_bitmap
+from tests import serving_ref as ref
+from tests.cpu_backend import NumpyBackend
+from tests.serving_ref import bitmap_numpy
 from tests.synth import make_ratings
-from tests.test_rank_eval_cpu import RankNumpyBackend
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "collaborative-filtering_amd", "csrc", "libals_hip.so")
-
-
-def bitmap_numpy(mask: np.ndarray) -> np.ndarray:
-    """The C ABI's definition, item by item: bit i & 31 of word i >> 5, uint32 words, ceil(n / 32) of them."""
-    words = np.zeros((mask.size + 31) // 32, dtype=np.uint32)
-    for i in np.nonzero(mask)[0]:
-        words[i >> 5] |= np.uint32(1) << np.uint32(i & 31)
-    return words
-
-
-def unpack(allow: torch.Tensor, n: int) -> np.ndarray:
-    words = allow.numpy().view(np.uint32)
-    assert words.size == (n + 31) // 32
-    i = np.arange(n)
-    return ((words[i >> 5] >> (i & 31).astype(np.uint32)) & 1).astype(bool)
-
-
-class MaskedNumpyBackend(RankNumpyBackend):
-    """recommend_topk_masked / rank_count_masked = the unmasked stand-ins with the disallowed items taken out of
-    the candidates; every call is recorded."""
-
-    def __init__(self):
-        super().__init__()
-        self.calls = []
-
-    def recommend_topk(self, **kw):
-        self.calls.append(("recommend_topk", kw["users"].numel()))
-        super().recommend_topk(**kw)
-
-    def rank_count(self, **kw):
-        self.calls.append(("rank_count", kw["q_users"].numel()))
-        super().rank_count(**kw)
-
-    def recommend_topk_masked(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, topn, top_val,
-                              top_idx, top_cnt):
-        self.calls.append(("recommend_topk_masked", users.numel(), allow.data_ptr()))
-        ok = unpack(allow, n)
-        u = users.long()
-        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
-        top_val.fill_(-np.inf)
-        top_idx.fill_(-1)
-        for b, uu in enumerate(u.tolist()):
-            keep = ok.copy()
-            if seen_ptr is not None:
-                keep[seen_idx[seen_ptr[uu]: seen_ptr[uu + 1]].numpy()] = False
-            keep &= ~np.isnan(S[b])
-            items = np.nonzero(keep)[0]
-            order = np.lexsort((items, -S[b, items]))[:topn]
-            top_val[b, : order.size] = torch.from_numpy(S[b, items[order]])
-            top_idx[b, : order.size] = torch.from_numpy(items[order].astype(np.int32))
-            top_cnt[b] = order.size
-
-    def rank_count_masked(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, q_users, q_ptr, q_items,
-                          t_score, above, n_cand):
-        self.calls.append(("rank_count_masked", q_users.numel(), allow.data_ptr()))
-        ok = unpack(allow, n)
-        u = q_users.long()
-        S = self._score(U[u].double() @ Z[:n].double().T, mu, b_u[u][:, None], b_i[None, :n]).numpy()
-        ptr = q_ptr.numpy()
-        j = np.arange(n)
-        for b, uu in enumerate(u.tolist()):
-            cand = ok & ~np.isnan(S[b])
-            if seen_ptr is not None:
-                cand[seen_idx[seen_ptr[uu]: seen_ptr[uu + 1]].numpy()] = False
-            n_cand[b] = int(cand.sum())
-            for p in range(ptr[b], ptr[b + 1]):
-                t = int(q_items[p])
-                s = S[b, t]
-                t_score[p] = float(s)
-                above[p] = -1 if np.isnan(s) else int((cand & ((S[b] > s) | ((S[b] == s) & (j < t)))).sum())
 
 
 M, N_ITEMS = 30, 70             # n not a multiple of 32
@@ -96,16 +28,13 @@ def fitted():
     r, c, v = make_ratings(M, N_ITEMS, 500, seed=3, empty_users=(4,))
     cfg = ALSConfig(core=CoreConfig(n_factors=5, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    model = ALS(cfg, device="cpu", backend=MaskedNumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
+    model = ALS(cfg, device="cpu", backend=NumpyBackend()).fit_coo(r, c, v, (M, N_ITEMS), tol=None, verbose=0)
     return model, r, c
 
 
 def _brute_top(P, seen, ok, N):
     """Dense oracle: predict() with seen and disallowed columns masked, (score desc, id asc)."""
-    keep = ok & ~np.isnan(P)
-    keep[list(seen)] = False
-    items = np.nonzero(keep)[0]
-    return items[np.lexsort((items, -P[items]))][:N]
+    return ref.topn(P, list(seen), ok, N)[1]
 
 
 # ------------------------------------------------------------------------------------------ validation
@@ -312,8 +241,8 @@ def split():
     test = np.random.default_rng(1).random(r.size) < 0.3
     cfg = ALSConfig(core=CoreConfig(n_factors=6, n_iters=3, lambda_u=2.0, lambda_v=2.0),
                     biases=BiasesConfig(lambda_bu=1.0, lambda_bi=1.0))
-    model = ALS(cfg, device="cpu", backend=MaskedNumpyBackend()).fit_coo(r[~test], c[~test], v[~test], (m, n),
-                                                                          tol=None, verbose=0)
+    model = ALS(cfg, device="cpu", backend=NumpyBackend()).fit_coo(r[~test], c[~test], v[~test], (m, n), tol=None,
+                                                                   verbose=0)
     return model, (r[~test], c[~test]), (r[test], c[test], v[test])
 
 
