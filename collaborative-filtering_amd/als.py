@@ -426,6 +426,46 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.list_diversity(torch.from_numpy(lists).to(self._eng.dev), features, new_items)
 
+    # ----------------------------------------------------------- neighbours
+    def similar_items(self, items=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                      allow_items=None, filter_items=None):
+        """The N items most similar to each query item: returns (ids int64 [B, N], sims float64 [B, N]), each row
+        ordered by similarity descending, ties to the lower item id.
+
+        The similarity is `recommend_diverse`'s: the cosine of two rows of Z, sim(i, j) = z_i.z_j / (|z_i| |z_j|), in
+        fp32 with the norms accumulated in fp64, 0 when either row is zero; `features` decides Z as in `predict` and
+        `list_diversity`.  `items`: None = all n items in id order - the item-item top-N graph of the model -, else
+        a 1-D array-like of item ids in [0, n) (order and duplicates kept).  An item is never its own neighbour; an
+        item with the same factors as the query is.  Slots beyond the number of candidates hold id -1 and
+        similarity -inf.  The result does not depend on the scale of the rows.
+
+        `allow_items` / `filter_items`: `rank_of`'s (the allow-list has that name because `items` are the queries):
+        the neighbours - not the queries - are restricted to `allow_items` minus `filter_items`, each a 1-D array of
+        item ids or a boolean mask over the catalogue.  One fused kernel walks the catalogue and selects
+        (als_similar_topk); nothing n x n and no normalised copy of Z is formed.  Local to the calling rank."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        n = self.V.shape[0]
+        i = validate.item_ids(items, n)
+        filters = validate.item_filters(allow_items, filter_items, n)
+        if i.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.similar_items(self._dev_i32(i), N, features, filters)
+
+    def similar_users(self, users=None, N: int = 10):
+        """The N users most similar to each query user by the cosine of their rows of U: `similar_items` over the
+        user table, without features or filters.  `users`: None = all m users in id order, else a 1-D array-like of
+        user ids in [0, m).  Returns (ids int64 [B, N], sims float64 [B, N]), unused slots -1 / -inf; a user is
+        never their own neighbour (als_similar_topk).  Local to the calling rank."""
+        validate.fitted(self)
+        N = validate.top_count(N, "N")
+        u = validate.user_ids(users, self.U.shape[0])
+        if u.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.similar_users(self._dev_i32(u), N)
+
     # ---------------------------------------------------------- evaluation
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
                 allow_items=None, filter_items=None):

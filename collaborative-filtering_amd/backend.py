@@ -49,6 +49,7 @@ class HipBackend:
         self._spd_ws: Optional[torch.Tensor] = None
         self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
         self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
+        self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -408,3 +409,28 @@ class HipBackend:
         assert idx.is_contiguous()
         self._check(self.lib.als_list_diversity(k, ld, B, n, _p(Z), L, _p(idx), _p(ild), self._stream()),
                     "als_list_diversity")
+
+    # -- K13 -------------------------------------------------------------------
+    def row_inv_norms(self, *, k, ld, T, inv_norm):
+        """inv_norm fp32 [rows] = 1 / |T_r| of the rows of T fp32 [rows, ld], squares summed in fp64; 0 for a zero
+        row, NaN for a row with a non-finite entry: als_row_inv_norms."""
+        assert T.is_contiguous() and T.shape[1] == ld and inv_norm.numel() >= T.shape[0]
+        self._check(self.lib.als_row_inv_norms(k, ld, T.shape[0], _p(T), _p(inv_norm), self._stream()),
+                    "als_row_inv_norms")
+
+    def similar_topk(self, *, k, ld, q_ids, Q, q_inv, self_ids, n, T, t_inv, allow, topn, top_val, top_idx, top_cnt):
+        """Top-`topn` rows of T [n, ld] by cosine for every query row q_ids[b] (int32) of Q, row self_ids[b] left
+        out (None: no exclusion), restricted to the bitmap `allow` (None: every row); q_inv / t_inv are the
+        `row_inv_norms` of Q / T: als_similar_topk.  The slice workspace is owned here and grows as needed;
+        ALS_RECOMMEND_SLICES applies."""
+        if allow is not None:
+            self._check_bitmap(allow, n)
+        nq = q_ids.numel()
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_similar_workspace_bytes(nq, n, topn, nsl))
+        if need > 0 and (self._sim_ws is None or self._sim_ws.numel() < need):
+            self._sim_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_similar_topk(k, ld, nq, _p(q_ids), _p(Q), _p(q_inv), _p(self_ids), n, _p(T),
+                                              _p(t_inv), _p(allow), topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
+                                              _p(self._sim_ws) if need > 0 else None, need, self._stream()),
+                    "als_similar_topk")

@@ -1,5 +1,5 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
-`fold_in_items`, `recommend*_diverse` and `list_diversity`.
+`fold_in_items`, `recommend*_diverse`, `list_diversity` and `similar_items` / `similar_users`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -572,6 +572,39 @@ class _Serving:
                                    ild=ild)
             out[b0: b0 + nb] = ild.cpu().numpy()
         return out
+
+    # ----------------------------------------------------------- neighbours
+    def _similar_chunks(self, T: torch.Tensor, ids: torch.Tensor, N: int, allow: Optional[torch.Tensor] = None):
+        """The N rows of the table T [rows, ld] most similar (cosine) to each of its rows `ids` (int32, device), a row
+        never its own neighbour: one als_row_inv_norms launch over T per call (nothing is kept between calls, so a
+        refit or other features cannot meet stale norms), then als_similar_topk in REC_BATCH chunks.  `allow`: the
+        bitmap of the call (`allow_bitmap`) or None.  Returns host (ids int64 [B, N], sims float64 [B, N]), unused
+        slots -1 / -inf."""
+        B, rows = ids.numel(), T.shape[0]
+        inv = torch.empty(rows, dtype=torch.float32, device=self.dev)
+        self.be.row_inv_norms(k=self.k, ld=self.ld, T=T, inv_norm=inv)
+        out_ids = np.empty((B, N), dtype=np.int64)
+        out_sims = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            q = ids[b0: b0 + nb]
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.similar_topk(k=self.k, ld=self.ld, q_ids=q, Q=T, q_inv=inv, self_ids=q, n=rows, T=T, t_inv=inv,
+                                 allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc)
+            out_ids[b0: b0 + nb] = ti.cpu().numpy()
+            out_sims[b0: b0 + nb] = tv.cpu().numpy()
+        return out_ids, out_sims
+
+    def similar_items(self, items_t: torch.Tensor, N: int, features, filters=None):
+        """Nearest items of the items `items_t` (int32, device) by the cosine of their rows of Z, composed as in
+        `list_diversity`; `filters` restricts the neighbours, not the queries."""
+        return self._similar_chunks(self._compose_for(features), items_t, N, self.allow_bitmap(filters, self.n))
+
+    def similar_users(self, users_t: torch.Tensor, N: int):
+        """Nearest users of the users `users_t` (int32, device) by the cosine of their rows of U."""
+        return self._similar_chunks(self.U, users_t, N)
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items

@@ -101,6 +101,15 @@ def user_ids(users, m: int) -> np.ndarray:
     return u
 
 
+def item_ids(items, n: int) -> np.ndarray:
+    """Query item ids in [0, n) of `similar_items`, order and duplicates kept; None = all n items in id order."""
+    if items is None:
+        return np.arange(n, dtype=np.int64)
+    i = _ids(items, "item")
+    _in_range(i, n, "item")
+    return i
+
+
 def id_pairs(users, items, m: int, n: int):
     u, i = _ids(users, "user"), _ids(items, "item")
     if u.shape != i.shape:

@@ -615,6 +615,39 @@ int als_list_diversity(int k, int ld, int64_t nrows, int64_t n, const float* Z, 
                        float* ild, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Nearest neighbours under the cosine: the rows of a factor table most similar to query rows.
+ *
+ * als_row_inv_norms: one pass over T [nrows][ld] (fp32, padding columns zero):
+ *   inv_norm[r] = (float)(1 / sqrt(s)),  s = sum_c (double)T[r][c]^2 accumulated in fp64 - rows at 1e-20 or 1e19
+ *   neither underflow nor overflow;  exactly 0 when s == 0;  NaN when s is NaN or +inf (a non-finite entry).
+ *   nrows < 2^31; nrows == 0 is a no-op.
+ *
+ * als_similar_topk: for every batch row b, with q = q_ids[b] a row of Q (duplicates allowed, order kept):
+ *   sim(b, j) = (Q_q.T_j * q_inv[q]) * t_inv[j] in fp32, in exactly this association; Q_q.T_j is bitwise the fp32
+ *   value als_predict_dense writes for (U = Q, Z = T, zero biases, mu = 0); q_inv / t_inv are the als_row_inv_norms
+ *   of Q / T.  A zero-norm row (inv 0) has similarity 0 to everything and competes like any other candidate; a row
+ *   with inv NaN is never returned, and as a query it gets an empty list (top_cnt 0).
+ *   The candidates are the rows j < n of T with j != self_ids[b] (self_ids NULL, or an entry of -1: no exclusion),
+ *   the bit of j set in allow (the bitmap of als_recommend_topk_masked: ceil(n / 32) words, bit (j & 31) of word
+ *   (j >> 5), bits >= n ignored; NULL allows every row), and a similarity that is not NaN.
+ *   top_val / top_idx [nq][topn], ordered by (sim descending, j ascending), -0.0 == +0.0; unused slots: top_idx -1,
+ *   top_val -inf; top_cnt [nq] = number of valid slots.  1 <= topn <= ALS_TOPK_MAX, n < 2^31; nq == 0 is a no-op.
+ *   Q and T may be the same table (the neighbours of its own rows, self_ids = q_ids) or different ones of the same
+ *   width (e.g. folded-in rows against the fitted table).
+ * nslices: as als_recommend_topk - 0 = automatic, otherwise the number of slices (<= ALS_RECOMMEND_MAX_SLICES, at
+ *   most one per 32 rows) the range of T is cut into, the slices' lists merged by a second launch; the result does
+ *   not depend on it.
+ * workspace: als_similar_workspace_bytes(nq, n, topn, nslices) bytes of device memory (0: may be NULL); the call
+ *   allocates nothing.
+ * ------------------------------------------------------------------------- */
+int als_row_inv_norms(int k, int ld, int64_t nrows, const float* T, float* inv_norm, void* stream);
+size_t als_similar_workspace_bytes(int64_t nq, int64_t n, int topn, int nslices);
+int als_similar_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_inv,
+                     const int32_t* self_ids, int64_t n, const float* T, const float* t_inv, const uint32_t* allow,
+                     int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
