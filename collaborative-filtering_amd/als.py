@@ -15,7 +15,7 @@ signature is unchanged):
   predict_at(flat_idx, ...) predictions at flat indices u*n+i without the
                             dense m x n matrix
   recommend / fold_in / recommend_new / rank_of / rank_of_new / explain / explain_new / fold_in_items /
-  predict_new_items         serving calls on the fitted tables
+  predict_new_items / similar_items / similar_users / recommend_users    serving calls on the fitted tables
 
 This module holds the `ALS` facade (each public method: validate, enter the device, call the engine, convert) and
 the memoised host build of the similarity graph.  The fit engine `_Engine` is engine.py; the device containers it
@@ -465,6 +465,39 @@ class ALS:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             return self._eng.similar_users(self._dev_i32(u), N)
+
+    # ------------------------------------------------------------- audience
+    def recommend_users(self, items=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
+                        exclude_seen: bool = True, new_items: Optional[FoldedItems] = None, users=None,
+                        filter_users=None):
+        """Top-N users per item - the audience of an item, `recommend` in the other direction: returns
+        (users int64 [B, N], scores float64 [B, N]), each row ordered by score descending, ties to the lower user id.
+
+        `items`: None = all n fitted items in id order (all n + B with `new_items`), else a 1-D array-like of item
+        ids in [0, n) - [0, n + B) with `new_items`, folded item b being item n + b - order and duplicates kept.
+        `features` is handled as in `predict`.  With `exclude_seen` the users who rated the item in the ratings of
+        the last fit are never returned; for a folded item, the raters in its ratings (`fold_in_items`' C_new).
+        Slots beyond the number of candidate users hold user -1 and score -inf.  NaN scores are never returned.
+
+        Contract: scores[b, j] == predict(features)[users[b, j], items[b]] exactly - for a folded item
+        predict_new_items(new_items)[users[b, j], items[b] - n] -, and no user outside the returned list scores
+        higher (or equal with a lower id) than users[b, N - 1], the item's raters aside.  Nothing m x n is formed:
+        one fused kernel walks the user table and selects (als_audience_topk).  Local to the calling rank.
+
+        `users` (allow-list) / `filter_users` (block-list): restrict the audience to `users` minus `filter_users`,
+        each a 1-D array of user ids (any order, duplicates accepted) or a boolean mask over the m users; None = no
+        restriction, an empty allow-list is legal (nothing is a candidate).  Applied inside the kernel (one bit per
+        user)."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        N = validate.top_count(N, "N")
+        i = validate.item_ids(items, self.V.shape[0] + (new_items.n_items if new_items is not None else 0))
+        filters = validate.user_filters(users, filter_users, self.U.shape[0])
+        if i.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_users(self._dev_i32(i), N, features, exclude_seen, new_items, filters)
 
     # ---------------------------------------------------------- evaluation
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,

@@ -50,6 +50,7 @@ class HipBackend:
         self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
         self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
         self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
+        self._aud_ws: Optional[torch.Tensor] = None        # slice lists of als_audience_topk
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -434,3 +435,23 @@ class HipBackend:
                                               _p(t_inv), _p(allow), topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
                                               _p(self._sim_ws) if need > 0 else None, need, self._stream()),
                     "als_similar_topk")
+
+    # -- K14 -------------------------------------------------------------------
+    def audience_topk(self, *, k, ld, q_ids, Q, q_bias, m, U, b_u, mu, seen_ptr, seen_idx, allow, topn, top_val,
+                      top_idx, top_cnt):
+        """Top-`topn` users of every query item q_ids[b] (int32, a row of Q / q_bias), the item's raters (CSR by
+        ITEM id over user ids; None = none) left out, restricted to the user bitmap `allow` (None: every user):
+        als_audience_topk.  The slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
+        if allow is not None:
+            self._check_bitmap(allow, m)
+        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
+            seen_ptr = seen_idx = None
+        nq = q_ids.numel()
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_audience_workspace_bytes(nq, m, topn, nsl))
+        if need > 0 and (self._aud_ws is None or self._aud_ws.numel() < need):
+            self._aud_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_audience_topk(k, ld, nq, _p(q_ids), _p(Q), _p(q_bias), m, _p(U), _p(b_u), _p(mu),
+                                               _p(seen_ptr), _p(seen_idx), _p(allow), topn, nsl, _p(top_val),
+                                               _p(top_idx), _p(top_cnt), _p(self._aud_ws) if need > 0 else None, need,
+                                               self._stream()), "als_audience_topk")

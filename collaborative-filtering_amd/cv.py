@@ -189,6 +189,36 @@ def diversity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, diversity:
             "coverage@K": np.unique(top[top >= 0]).size / n_allowed if n_allowed else float("nan"), **extra}
 
 
+def audience_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
+                  features: Optional[Dict[str, np.ndarray]] = None, users=None, filter_users=None) -> Dict[str, Any]:
+    """recall@K and NDCG@K of `model.recommend_users` on held-out (user, item) pairs: `ranking_at_k` per ITEM - is
+    the held-out rater among the item's top-K users who did not rate it in the fit?  For every item i of the
+    held-out set, rel(i) = {u : (u, i) held out, and vals >= min_rating unless min_rating is None}, top(i) =
+    model.recommend_users([i], K, features=features), and recall / DCG / NDCG as in `ranking_at_k` with users and
+    items swapped.  Items with an empty rel(i) are left out: {"items": their number, "recall@K", "ndcg@K"} (NaN
+    means when no item is left).
+
+    `users` / `filter_users` (as `ALS.recommend_users`): the measures within the restricted audience - held-out
+    pairs whose user is not allowed are left out, and the result gains "filtered_out", their number."""
+    rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
+    extra, kw = {}, {}
+    if users is not None or filter_users is not None:
+        validate.fitted(model)
+        m = model.U.shape[0]
+        mask = validate.allowed_mask(validate.user_filters(users, filter_users, m), m)
+        keep = np.zeros(rows.size, dtype=bool)
+        inside = (rows >= 0) & (rows < m)
+        keep[inside] = mask[rows[inside]]
+        extra, kw = {"filtered_out": int((~keep).sum())}, {"users": users, "filter_users": filter_users}
+        rows, cols = rows[keep], cols[keep]
+    items, ib = np.unique(cols, return_inverse=True)
+    if items.size == 0:
+        return {"items": 0, "recall@K": float("nan"), "ndcg@K": float("nan"), **extra}
+    top, _ = model.recommend_users(items, K, features=features, **kw)
+    out = _ranking_metrics(top, ib, rows, model.U.shape[0], K)
+    return {"items": out.pop("users"), **out, **extra}
+
+
 def _users_at_k(model, rows, cols, vals, min_rating, items, filter_items):
     """The users scored by ranking_at_k / diversity_at_k: (users, ub, cols, kw, extra) - the distinct users of the
     held-out pairs that survive `min_rating` and the item filter, the position `ub` of every surviving pair's user,

@@ -1,5 +1,5 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
-`fold_in_items`, `recommend*_diverse`, `list_diversity` and `similar_items` / `similar_users`.
+`fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users` and `recommend_users`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -605,6 +605,50 @@ class _Serving:
     def similar_users(self, users_t: torch.Tensor, N: int):
         """Nearest users of the users `users_t` (int32, device) by the cosine of their rows of U."""
         return self._similar_chunks(self.U, users_t, N)
+
+    # ------------------------------------------------------------- audience
+    def _rater_rows(self, folded: Optional["FoldedItems"]):
+        """The rater CSR als_audience_topk excludes by, indexed by item id: the training CSC, followed with `folded`
+        by the rows of its ratings (item n + b = row n + b) - one indptr with the second part's offsets shifted, one
+        index array, built on the device.  (None, None) when no item has a rater."""
+        ptr, idx, total = self.csc.indptr, self.csc.indices, self.nnz
+        if folded is not None:
+            fptr = torch.from_numpy(np.asarray(folded.ratings[0], dtype=np.int64)).to(self.dev)
+            fidx = torch.from_numpy(np.asarray(folded.ratings[1], dtype=np.int32)).to(self.dev)
+            ptr = torch.cat([ptr, fptr[1:] + self.nnz])
+            idx = torch.cat([idx[: self.nnz], fidx])
+            total += int(fidx.numel())
+        if total == 0:
+            return None, None
+        return ptr, idx
+
+    def recommend_users(self, items_t: torch.Tensor, N: int, features, exclude_seen: bool,
+                        folded: Optional["FoldedItems"] = None, filters=None):
+        """Top-N users of the items `items_t` (int32, device; ids >= n are the folded items of `folded`): (users
+        int64 [B, N], scores float64 [B, N]), unused slots -1 / -inf - als_audience_topk in REC_BATCH chunks.  The
+        query table is the Z of `predict` (the joint table of `_joint_side` with `folded`), the raters left out are
+        `_rater_rows`; `filters`: the validated user allow / block pair of the call over the m users, or None."""
+        if folded is None:
+            Q, q_bias = self._compose_for(features), self.b_i
+        else:
+            side = self._joint_side(features, folded)
+            Q, q_bias = side["Z"], side["b_i"]
+        seen_ptr, seen_idx = self._rater_rows(folded) if exclude_seen else (None, None)
+        allow = self.allow_bitmap(filters, self.m)
+        B = items_t.numel()
+        out_users = np.empty((B, N), dtype=np.int64)
+        out_scores = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.audience_topk(k=self.k, ld=self.ld, q_ids=items_t[b0: b0 + nb], Q=Q, q_bias=q_bias, m=self.m,
+                                  U=self.U, b_u=self.b_u, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                                  allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc)
+            out_users[b0: b0 + nb] = ti.cpu().numpy()
+            out_scores[b0: b0 + nb] = tv.cpu().numpy()
+        return out_users, out_scores
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items

@@ -134,24 +134,25 @@ def target_lists(targets, B: int, n: int):
     return tptr, ti.astype(np.int64)
 
 
-def item_filter(x, n_total: int, name: str) -> Optional[np.ndarray]:
+def item_filter(x, n_total: int, name: str, kind: str = "item") -> Optional[np.ndarray]:
     """One of `items=` / `filter_items=` (`name`) over a catalogue of n_total items -> None (not given), a bool mask
-    [n_total], or int64 item ids in [0, n_total) (any order, duplicates kept).  Raises ValueError otherwise."""
+    [n_total], or int64 item ids in [0, n_total) (any order, duplicates kept).  Raises ValueError otherwise.
+    `kind`: what the ids name in the messages ("user" for `user_filters`)."""
     if x is None:
         return None
     a = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
     if a.ndim != 1:
-        raise ValueError(f"{name} must be a 1-D array of integer item ids or a boolean mask of length {n_total}")
+        raise ValueError(f"{name} must be a 1-D array of integer {kind} ids or a boolean mask of length {n_total}")
     if a.dtype == np.bool_:
         if a.size != n_total:
-            raise ValueError(f"{name} as a boolean mask has {a.size} entries. Expected number of items: {n_total}.")
+            raise ValueError(f"{name} as a boolean mask has {a.size} entries. Expected number of {kind}s: {n_total}.")
         return a
     if a.size == 0:                                          # an empty list, whatever dtype numpy gave it
         return np.empty(0, dtype=np.int64)
     if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f"{name} must hold integer item ids or booleans, got dtype {a.dtype}")
+        raise ValueError(f"{name} must hold integer {kind} ids or booleans, got dtype {a.dtype}")
     if a.min() < 0 or a.max() >= n_total:
-        raise ValueError(f"{name}: item ids must lie in [0, {n_total})")
+        raise ValueError(f"{name}: {kind} ids must lie in [0, {n_total})")
     return a.astype(np.int64)
 
 
@@ -161,6 +162,14 @@ def item_filters(items, filter_items, n_total: int):
     if items is None and filter_items is None:
         return None
     return item_filter(items, n_total, "items"), item_filter(filter_items, n_total, "filter_items")
+
+
+def user_filters(users, filter_users, m: int):
+    """The allow-list `users=` and the block-list `filter_users=` of `recommend_users`, over the m users: as
+    `item_filters` (None when neither is given), the messages naming these two parameters and user ids."""
+    if users is None and filter_users is None:
+        return None
+    return item_filter(users, m, "users", "user"), item_filter(filter_users, m, "filter_users", "user")
 
 
 def allowed_mask(filters, n_total: int) -> np.ndarray:

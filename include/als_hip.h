@@ -648,6 +648,35 @@ int als_similar_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const floa
                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Audience of an item: als_recommend_topk in the other direction - the users to show an item
+ * to.  For every batch row b, with i = q_ids[b] a row of Q (an item; duplicates allowed, order kept):
+ *   score(b, u) = U_u.Q_i + mu + b_u[u] + q_bias[i] = ((dot + mu) + b_u[u]) + q_bias[i] in fp32 - bitwise the value
+ *   als_predict_dense writes at (u, i) for Z = Q, b_i = q_bias (als_recommend_topk called with the two sides swapped
+ *   adds the biases in the other order and differs in the last bit) -
+ *   over all users u < m that are not in row i of the rater CSR (seen_ptr [rows(Q) + 1] / seen_idx: indexed by the
+ *   QUERY'S ROW ID q_ids[b], user ids ascending within each row - the training CSC; both NULL = exclude nothing) and
+ *   whose bit is set in allow (the bitmap of als_recommend_topk_masked over USERS: ceil(m / 32) words, bit (u & 31) of
+ *   word (u >> 5), bits >= m ignored; NULL allows every user).  NaN scores are never returned.
+ *   top_val / top_idx [nq][topn], ordered by (score descending, user ascending), -0.0 == +0.0 - among equal scores the
+ *   LOWEST user ids win; unused slots: top_idx -1, top_val -inf; top_cnt [nq] = number of valid slots.
+ *   1 <= topn <= ALS_TOPK_MAX, m < 2^31; nq == 0 is a no-op.  Q [rows][ld] and U [m][ld] with zero padding columns,
+ *   ld = als_padded_k(k); q_bias [rows(Q)], b_u [m], mu: device double.
+ * nslices: as als_recommend_topk - 0 = automatic, otherwise the number of slices (<= ALS_RECOMMEND_MAX_SLICES, at
+ *   most one per 32 users) the user range is cut into, the slices' lists merged by a second launch; the result does
+ *   not depend on it.
+ * The users are walked in chunks of 32; a chunk whose bitmap word is 0 is not scored.  A rater list of any length
+ *   costs one 16-entry load per block that holds a rater and a binary search per slice or skipped range.
+ * workspace: als_audience_workspace_bytes(nq, m, topn, nslices) bytes of device memory (0: may be NULL); the call
+ *   allocates nothing.
+ * ------------------------------------------------------------------------- */
+size_t als_audience_workspace_bytes(int64_t nq, int64_t m, int topn, int nslices);
+int als_audience_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_bias,
+                      int64_t m, const float* U, const float* b_u, const double* mu,
+                      const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                      int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
