@@ -499,6 +499,43 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.recommend_users(self._dev_i32(i), N, features, exclude_seen, new_items, filters)
 
+    # --------------------------------------------------------------- groups
+    def recommend_group(self, groups, N: int = 10, *, aggregate: str = "mean",
+                        features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                        new_items: Optional[FoldedItems] = None, items=None, filter_items=None):
+        """Top-N items per group of users - one list for a household, a table, a room: returns (items int64 [G, N],
+        scores float64 [G, N]), each row ordered by group score descending, ties to the lower item id.
+
+        `groups`: a sequence of 1-D arrays of user ids in [0, m) (groups of different sizes), or a 2-D integer array
+        [G, g] of equal-size groups; a group has 1 ... 64 distinct members; order and repeated groups are kept.
+        `aggregate`: how the members' scores of an item become the group's - "mean", "min" (least misery: the list
+        the worst-off member likes best) or "max" (most pleasure).  `features`, `new_items`, `items` and
+        `filter_items` as in `recommend`.  With `exclude_seen` an item that ANY member has rated in the ratings of the
+        last fit is never returned.  Slots beyond the number of candidate items hold item -1 and score -inf.  An item
+        for which some member's score is NaN is no candidate, whatever the aggregate; NaN scores are never returned.
+
+        Contract: with P = predict(features) as float32 and mem the members of group g, scores[g, j] is exactly
+        P[mem, i].min() for "min", P[mem, i].max() for "max" and np.float32(P[mem, i].astype(np.float64).sum() /
+        len(mem)) for "mean", i = items[g, j], and no candidate outside the list has a higher group score (or an equal
+        one with a lower id) than items[g, N - 1].  The fp64 sum of the mean is exact - independent of the order of
+        the members - when the nonzero member scores of an item lie within a factor 2^17 of each other in magnitude
+        (ratings on any usual scale do); outside that band it is within one fp64 rounding of the exact sum.  A group of
+        one gets `recommend`'s list for that user, bit for bit, under every aggregate.  Nothing m x n is formed and no
+        member's row of scores leaves the kernel: one fused kernel scores the members, folds their scores and selects
+        (als_group_topk).  Local to the calling rank."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        N = validate.top_count(N, "N")
+        aggregate = validate.group_aggregate(aggregate)
+        g_ptr, g_users = validate.user_groups(groups, self.U.shape[0])
+        filters = validate.item_filters(items, filter_items,
+                                        self.V.shape[0] + (new_items.n_items if new_items is not None else 0))
+        if g_ptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_group(g_ptr, g_users, N, aggregate, features, exclude_seen, new_items, filters)
+
     # ---------------------------------------------------------- evaluation
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
                 allow_items=None, filter_items=None):

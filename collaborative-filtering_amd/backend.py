@@ -51,6 +51,7 @@ class HipBackend:
         self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
         self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
         self._aud_ws: Optional[torch.Tensor] = None        # slice lists of als_audience_topk
+        self._grp_ws: Optional[torch.Tensor] = None        # slice lists of als_group_topk
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -455,3 +456,28 @@ class HipBackend:
                                                _p(seen_ptr), _p(seen_idx), _p(allow), topn, nsl, _p(top_val),
                                                _p(top_idx), _p(top_cnt), _p(self._aud_ws) if need > 0 else None, need,
                                                self._stream()), "als_audience_topk")
+
+    # -- K15 -------------------------------------------------------------------
+    GROUP_AGGREGATES = {"mean": 0, "min": 1, "max": 2}     # ALS_GROUP_MEAN / _MIN / _MAX
+
+    def group_topk(self, *, k, ld, g_ptr, g_users, max_members, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow,
+                   aggregate, topn, top_val, top_idx, top_cnt):
+        """Top-`topn` items of every group: group b has the members g_users[g_ptr[b]:g_ptr[b + 1]] (int64 prefix sum,
+        int32 rows of U / b_u; at most `max_members` <= 64 each), its score for an item is the `aggregate` ("mean",
+        "min", "max") of the members' scores, the items of row b of the seen CSR (indexed by BATCH GROUP; None =
+        none) are left out, restricted to the item bitmap `allow` (None: every item): als_group_topk.  The slice
+        workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
+        if allow is not None:
+            self._check_bitmap(allow, n)
+        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
+            seen_ptr = seen_idx = None
+        ng = g_ptr.numel() - 1
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_group_workspace_bytes(ng, n, topn, nsl))
+        if need > 0 and (self._grp_ws is None or self._grp_ws.numel() < need):
+            self._grp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_group_topk(k, ld, ng, _p(g_ptr), _p(g_users), int(max_members), n, _p(U), _p(Z),
+                                            _p(b_u), _p(b_i), _p(mu), _p(seen_ptr), _p(seen_idx), _p(allow),
+                                            self.GROUP_AGGREGATES[aggregate], topn, nsl, _p(top_val), _p(top_idx),
+                                            _p(top_cnt), _p(self._grp_ws) if need > 0 else None, need,
+                                            self._stream()), "als_group_topk")

@@ -231,9 +231,9 @@ def _users_at_k(model, rows, cols, vals, min_rating, items, filter_items):
     return users, ub, cols, kw, extra
 
 
-def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int) -> Dict[str, Any]:
-    """recall@K / NDCG@K of ranked lists `items` [U, K] (-1 = empty slot) against the relevant (position ub, item
-    cols) pairs; every position 0 .. U-1 has at least one (see ranking_at_k)."""
+def _ranking_rows(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int):
+    """(recall@K [U], NDCG@K [U]) of ranked lists `items` [U, K] (-1 = empty slot) against the relevant (position ub,
+    item cols) pairs; every position 0 .. U-1 has at least one (see ranking_at_k)."""
     nu = items.shape[0]
     n = int(max(n_items, cols.max() + 1))
     rel = np.unique(ub * n + cols)                                      # (user position, item), duplicates merged
@@ -242,8 +242,74 @@ def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_item
     disc = 1.0 / np.log2(np.arange(2, K + 2, dtype=np.float64))         # rank r = 1 .. K
     dcg = (hit * disc).sum(axis=1)
     idcg = np.cumsum(disc)[np.minimum(nrel, K) - 1]
-    return {"users": int(nu), "recall@K": float(np.mean(hit.sum(axis=1) / nrel)),
-            "ndcg@K": float(np.mean(dcg / idcg))}
+    return hit.sum(axis=1) / nrel, dcg / idcg
+
+
+def _ranking_metrics(items: np.ndarray, ub: np.ndarray, cols: np.ndarray, n_items: int, K: int) -> Dict[str, Any]:
+    """The means of `_ranking_rows` over the U lists, as ranking_at_k reports them."""
+    recall, ndcg = _ranking_rows(items, ub, cols, n_items, K)
+    return {"users": int(items.shape[0]), "recall@K": float(np.mean(recall)), "ndcg@K": float(np.mean(ndcg))}
+
+
+def group_ranking_at_k(model: ALS, groups, rows, cols, vals=None, *, K: int = 10, aggregate: str = "mean",
+                       min_rating: Optional[float] = None,
+                       features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+    """recall@K and NDCG@K of `model.recommend_group(groups, K, aggregate=aggregate)` on held-out (user, item) pairs:
+    how well does ONE list serve every member?  For member u of group g:
+
+      rel(g, u) = {i : (u, i) held out, and vals >= min_rating unless min_rating is None}, without the items that a
+                  member of g has among the training ratings of the fit - the group's list leaves those out, so they
+                  cannot be candidates;
+      recall@K(g, u), NDCG@K(g, u): `ranking_at_k`'s definitions for the list of g against rel(g, u).
+
+    Members with an empty rel(g, u) are left out, and groups without a member left as well.  The result is
+    {"groups": groups evaluated, "members": (group, member) pairs evaluated,
+     "recall@K": {"mean_member": ..., "min_member": ...}, "ndcg@K": {"mean_member": ..., "min_member": ...}}:
+    mean_member is the mean over the evaluated members of a group, averaged over the groups; min_member is the value
+    of the worst-off evaluated member of a group, averaged over the groups - what least misery ("min") is meant to
+    raise.  NaN when no group is left.  `groups` as in `ALS.recommend_group`; a group listed twice counts twice."""
+    validate.fitted(model)
+    aggregate = validate.group_aggregate(aggregate)
+    m, n = model.U.shape[0], model.V.shape[0]
+    g_ptr, g_users = validate.user_groups(groups, m)
+    rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
+    nan = float("nan")
+    empty = {"groups": 0, "members": 0, "recall@K": {"mean_member": nan, "min_member": nan},
+             "ndcg@K": {"mean_member": nan, "min_member": nan}}
+    # every (member slot, held-out item of that member): slot s = position in g_users, group gs[s]
+    sizes = np.diff(g_ptr)
+    gs = np.repeat(np.arange(sizes.size, dtype=np.int64), sizes)
+    order = np.argsort(rows, kind="stable")
+    rows, cols = rows[order], cols[order]
+    first = np.searchsorted(rows, g_users, side="left")
+    count = np.searchsorted(rows, g_users, side="right") - first
+    slot = np.repeat(np.arange(g_users.size, dtype=np.int64), count)
+    item = cols[np.repeat(first, count) + (np.arange(slot.size) - np.repeat(np.cumsum(count) - count, count))]
+    if slot.size == 0:
+        return empty
+    # drop the entries whose item a member of the group has in training: one (fellow, item) pair per fellow
+    gsz = sizes[gs[slot]]
+    entry = np.repeat(np.arange(slot.size, dtype=np.int64), gsz)
+    fellow = g_users[np.repeat(g_ptr[gs[slot]], gsz) + (np.arange(entry.size) - np.repeat(np.cumsum(gsz) - gsz, gsz))]
+    inside = (np.repeat(item, gsz) >= 0) & (np.repeat(item, gsz) < n)
+    seen = np.zeros(entry.size, dtype=bool)
+    seen[inside] = model._seen_pairs(fellow[inside].astype(np.int64), np.repeat(item, gsz)[inside])
+    keep = np.bincount(entry, weights=seen, minlength=slot.size) == 0
+    slot, item = slot[keep], item[keep]
+    if slot.size == 0:
+        return empty
+    # the evaluated members (slots with a relevant item left) and their groups
+    mslots, mb = np.unique(slot, return_inverse=True)
+    gids, gpos = np.unique(gs[mslots], return_inverse=True)
+    top, _ = model.recommend_group([g_users[g_ptr[g]: g_ptr[g + 1]] for g in gids], K, aggregate=aggregate,
+                                   features=features)
+    recall, ndcg = _ranking_rows(top[gpos], mb, item, n, K)
+    out = {"groups": int(gids.size), "members": int(mslots.size)}
+    starts = np.searchsorted(gpos, np.arange(gids.size))               # gpos ascends with the slots
+    for name, v in (("recall@K", recall), ("ndcg@K", ndcg)):
+        out[name] = {"mean_member": float(np.mean(np.add.reduceat(v, starts) / np.bincount(gpos))),
+                     "min_member": float(np.mean(np.minimum.reduceat(v, starts)))}
+    return out
 
 
 def fold_in_ranking_at_k(model: ALS, known, held_out, *, K: int = 10, min_rating: Optional[float] = None,

@@ -1,5 +1,6 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
-`fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users` and `recommend_users`.
+`fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users` and
+`recommend_group`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -649,6 +650,68 @@ class _Serving:
             out_users[b0: b0 + nb] = ti.cpu().numpy()
             out_scores[b0: b0 + nb] = tv.cpu().numpy()
         return out_users, out_scores
+
+    # --------------------------------------------------------------- groups
+    def _group_seen(self, members: torch.Tensor, ptr: torch.Tensor, n_total: int, new_u: torch.Tensor,
+                    new_i: torch.Tensor):
+        """Seen CSR by batch group (device): the union of the members' seen rows - an item any member has seen is
+        out.  `members` int32, group b = members[ptr[b]:ptr[b + 1]]; the members' rows are gathered as `_merged_seen`
+        gathers them (training row, then the folded items of the pairs new_u / new_i), keyed by (group, item),
+        sorted, repeats dropped, counted.  (None, None) when no member has seen anything."""
+        mptr, midx = self._merged_seen(members.to(torch.int64), new_u, new_i)
+        if mptr is None:
+            return None, None
+        nb = ptr.numel() - 1
+        group_of_member = torch.repeat_interleave(torch.arange(nb, device=self.dev), ptr[1:] - ptr[:-1])
+        group = torch.repeat_interleave(group_of_member, mptr[1:] - mptr[:-1])
+        key = torch.unique(group * n_total + midx[: group.numel()].to(torch.int64))      # ascending, distinct
+        group = torch.div(key, n_total, rounding_mode="floor")
+        out_ptr = torch.zeros(nb + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(torch.bincount(group, minlength=nb), 0, out=out_ptr[1:])
+        return out_ptr, (key - group * n_total).to(torch.int32)
+
+    def recommend_group(self, g_ptr: np.ndarray, g_users: np.ndarray, N: int, aggregate: str, features,
+                        exclude_seen: bool, folded: Optional["FoldedItems"] = None, filters=None):
+        """Top-N items of the groups g_users[g_ptr[b]:g_ptr[b + 1]] (validate.user_groups: host int64 / int32) under
+        `aggregate`: (items int64 [G, N], scores float64 [G, N]), unused slots -1 / -inf - als_group_topk in REC_BATCH
+        chunks of groups.  The item tables are the Z of `predict` (the joint table of `_joint_side` with `folded`);
+        the members index the resident U / b_u; per chunk the seen rows of the groups are `_group_seen`; `filters`:
+        the validated item allow / block pair of the call over the catalogue scored, or None."""
+        side = self._item_side(self._compose_for(features)) if folded is None else self._joint_side(features, folded)
+        allow = self.allow_bitmap(filters, side["n"])
+        G = g_ptr.size - 1
+        sizes = np.diff(g_ptr)
+        ptr_d = torch.from_numpy(g_ptr).to(self.dev)
+        users_d = torch.from_numpy(g_users).to(self.dev)
+        new_u = torch.empty(0, dtype=torch.int64, device=self.dev)
+        new_i = torch.empty(0, dtype=torch.int32, device=self.dev)
+        if exclude_seen and folded is not None:
+            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item (as `_joint_rows`)
+            rp, ri = folded.ratings[0], folded.ratings[1]
+            fu = ri.astype(np.int64)
+            fi = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
+            o = np.lexsort((fi, fu))
+            new_u = torch.from_numpy(fu[o]).to(self.dev)
+            new_i = torch.from_numpy(fi[o].astype(np.int32)).to(self.dev)
+        out_items = np.empty((G, N), dtype=np.int64)
+        out_scores = np.empty((G, N), dtype=np.float64)
+        for b0 in range(0, G, self.REC_BATCH):
+            nb = min(self.REC_BATCH, G - b0)
+            p0, p1 = int(g_ptr[b0]), int(g_ptr[b0 + nb])
+            ptr = (ptr_d[b0: b0 + nb + 1] - p0).contiguous()
+            members = users_d[p0:p1]
+            seen_ptr = seen_idx = None
+            if exclude_seen and (self.nnz > 0 or new_u.numel() > 0):
+                seen_ptr, seen_idx = self._group_seen(members, ptr, side["n"], new_u, new_i)
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.group_topk(g_ptr=ptr, g_users=members, max_members=int(sizes[b0: b0 + nb].max()), U=self.U,
+                               b_u=self.b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, allow=allow, aggregate=aggregate,
+                               topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **side)
+            out_items[b0: b0 + nb] = ti.cpu().numpy()
+            out_scores[b0: b0 + nb] = tv.cpu().numpy()
+        return out_items, out_scores
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items

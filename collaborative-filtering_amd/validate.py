@@ -110,6 +110,51 @@ def item_ids(items, n: int) -> np.ndarray:
     return i
 
 
+GROUP_MAX_MEMBERS = 64      # ALS_GROUP_MAX_MEMBERS: the members one wave of als_group_topk holds
+GROUP_AGGREGATES = ("mean", "min", "max")
+
+
+def user_groups(groups, m: int):
+    """The groups of `recommend_group`: a ragged sequence of 1-D arrays of user ids, or a 2-D integer array [G, g] of
+    equal-size groups -> (ptr int64 [G + 1], users int32): group b is users[ptr[b]:ptr[b + 1]], order and repeated
+    groups kept.  Raises ValueError for an empty group, an id outside [0, m), a user twice in one group, or a group of
+    more than GROUP_MAX_MEMBERS members."""
+    if torch.is_tensor(groups):
+        groups = groups.detach().cpu().numpy()
+    if isinstance(groups, np.ndarray) and groups.ndim == 2:
+        if groups.size and not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError("groups must hold integer user ids")
+        rows = list(groups)
+    elif isinstance(groups, np.ndarray) and groups.ndim != 1:
+        raise ValueError("groups must be a sequence of 1-D arrays of user ids or a 2-D integer array [G, g]")
+    else:
+        try:
+            rows = [np.asarray(g.detach().cpu().numpy() if torch.is_tensor(g) else g) for g in groups]
+        except TypeError:
+            raise ValueError("groups must be a sequence of 1-D arrays of user ids or a 2-D integer array [G, g]")
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    for b, g in enumerate(rows):
+        if g.ndim != 1 or (g.size and not np.issubdtype(g.dtype, np.integer)):
+            raise ValueError(f"group {b} must be a 1-D array of integer user ids")
+        if g.size == 0:
+            raise ValueError(f"group {b} is empty: a group needs at least one member")
+        if g.size > GROUP_MAX_MEMBERS:
+            raise ValueError(f"group {b} has {g.size} members; a group holds at most {GROUP_MAX_MEMBERS}")
+        if g.min() < 0 or g.max() >= m:
+            raise ValueError(f"group {b}: user ids must lie in [0, {m})")
+        if np.unique(g).size != g.size:
+            raise ValueError(f"group {b} names a user more than once")
+        ptr[b + 1] = ptr[b] + g.size
+    users = np.concatenate(rows).astype(np.int32) if rows else np.empty(0, dtype=np.int32)
+    return ptr, users
+
+
+def group_aggregate(aggregate) -> str:
+    if not isinstance(aggregate, str) or aggregate not in GROUP_AGGREGATES:
+        raise ValueError(f"aggregate must be one of {GROUP_AGGREGATES}, got {aggregate!r}")
+    return aggregate
+
+
 def id_pairs(users, items, m: int, n: int):
     u, i = _ids(users, "user"), _ids(items, "item")
     if u.shape != i.shape:

@@ -677,6 +677,49 @@ int als_audience_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const flo
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Top-N for a group of users: one list for a household, a table, a room.  Batch group b has the
+ * members g_users[g_ptr[b] .. g_ptr[b+1]) (g_ptr [ngroups+1] int64, device; rows of U and b_u, distinct within a group;
+ * groups may repeat, order kept), 0 ... ALS_GROUP_MAX_MEMBERS of them.  Member j scores item i with
+ *   s_j(i) = U_j.Z_i + mu + b_u[j] + b_i[i] - bitwise the fp32 value als_predict_dense writes at (j, i) -
+ * and the group score of item i over the g members is, by aggregate,
+ *   ALS_GROUP_MIN   the smallest s_j(i) (least misery),
+ *   ALS_GROUP_MAX   the largest s_j(i),
+ *   ALS_GROUP_MEAN  the fp64 sum of the fp32 s_j(i), divided by g in fp64, rounded once to fp32.  The order of the
+ *                   sum is not specified: it is exact, and so independent of order, tiling and lane layout, when the
+ *                   nonzero member scores of an item lie within a factor 2^17 of each other in magnitude (24-bit
+ *                   values, at most 64 of them, 53-bit accumulator); outside that band the result is within one fp64
+ *                   rounding of the exact sum.
+ * Candidates of group b: the items i < n that are not in row b of the seen CSR (seen_ptr [ngroups+1] / seen_idx:
+ *   indexed by BATCH GROUP, not by user - the caller forms the union of the members' rows; item ids ascending and
+ *   distinct within a row; both NULL = exclude nothing), whose bit is set in allow (the item bitmap of
+ *   als_recommend_topk_masked; NULL allows every item), for which NO member score is NaN (a minimum or maximum that
+ *   skipped a NaN member is never returned) and whose group score is not NaN (a mean of +inf and -inf).
+ *   top_val / top_idx [ngroups][topn], ordered by (group score descending, item ascending), -0.0 == +0.0 - among equal
+ *   scores the LOWEST item ids win; unused slots: top_idx -1, top_val -inf; top_cnt [ngroups] = number of valid slots.
+ *   A group without members gets an empty list (top_cnt 0).  A group of one gets als_recommend_topk's list for that
+ *   user, bit for bit, under every aggregate.
+ *   1 <= topn <= ALS_TOPK_MAX, n < 2^31; ngroups == 0 is a no-op.
+ * max_members: the host cannot read the device g_ptr without a copy, so the caller states an upper bound of the group
+ *   sizes, 0 ... ALS_GROUP_MAX_MEMBERS (anything else, like an unknown aggregate, is ALS_E_BADARG).  The kernel sizes
+ *   nothing by g_ptr alone: a group longer than max_members is cut to its first max_members members.
+ * nslices, workspace: as als_recommend_topk - 0 = automatic, the slices' lists merged by a second launch, the result
+ *   does not depend on it; als_group_workspace_bytes(ngroups, n, topn, nslices) bytes of device memory (0: may be
+ *   NULL); the call allocates nothing.
+ * One wave serves one group: a group of <= 16 members costs one 16-row score tile per 16 items whatever its size, a
+ *   larger one ceil(g / 16) tiles.  A chunk of 32 items whose bitmap word is 0 is neither loaded nor scored.
+ * ------------------------------------------------------------------------- */
+#define ALS_GROUP_MAX_MEMBERS 64
+#define ALS_GROUP_MEAN 0
+#define ALS_GROUP_MIN  1
+#define ALS_GROUP_MAX  2
+size_t als_group_workspace_bytes(int64_t ngroups, int64_t n, int topn, int nslices);
+int als_group_topk(int k, int ld, int64_t ngroups, const int64_t* g_ptr, const int32_t* g_users, int max_members,
+                   int64_t n, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
+                   const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, int aggregate,
+                   int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
