@@ -17,7 +17,7 @@ SPLIT_CHUNK = 4096          # ALS_SPLIT_CHUNK
 MAX_K = 160                 # ALS_MAX_K
 
 EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_bytes", "als_partial_slot_bytes_f64",
-           "als_row_solve", "als_factor_scale", "als_gs_sweep", "als_gs_sweep_levels", "als_gs_sweep_dataflow", "als_residual_stats", "als_w_normal_equations", "als_spd_solve_workspace_bytes", "als_spd_solve_f64", "als_item_stats", "als_item_stats_f64", "als_sum_pairs", "als_sumsq_partials",
+           "als_row_solve", "als_row_solve_refine", "als_factor_scale", "als_gs_sweep", "als_gs_sweep_levels", "als_gs_sweep_dataflow", "als_residual_stats", "als_w_normal_equations", "als_spd_solve_workspace_bytes", "als_spd_solve_f64", "als_item_stats", "als_item_stats_f64", "als_sum_pairs", "als_sumsq_partials",
            "als_sumsq", "als_history_row", "als_compose_z", "als_predict_at", "als_predict_dense",
            "als_topk_similarity", "als_graph_classify", "als_normalize_features", "als_impute_col_median",
            "als_host_coo_to_sides", "als_host_row_tasks", "als_host_level_schedule",
@@ -47,6 +47,11 @@ class RowSolveParams(C.Structure):
         ("workspace", _vp), ("cond_limit", _f32), ("byproducts_f64", _i32), ("redo_count", _vp), ("redo_rows", _vp),
         ("cond_out", _vp), ("F_scale", _vp), ("F_planes", _vp),
     ]
+
+
+class RefineParams(C.Structure):
+    """struct als_refine_params (include/als_hip.h)."""
+    _fields_ = [("max_steps", _i32), ("fallback_count", _vp), ("fallback_rows", _vp), ("step_hist", _vp)]
 
 
 class GsSweepParams(C.Structure):
@@ -141,6 +146,7 @@ def load():
     lib.als_partial_slot_bytes_f64.argtypes = [C.c_int]
     lib.als_partial_slot_bytes_f64.restype = _i64
     lib.als_row_solve.argtypes = [C.POINTER(RowSolveParams), _vp]
+    lib.als_row_solve_refine.argtypes = [C.POINTER(RowSolveParams), C.POINTER(RefineParams), _vp]
     lib.als_factor_scale.argtypes = [_vp, _i64, _vp, _vp]
     lib.als_gs_sweep.argtypes = [C.POINTER(GsSweepParams), _vp]
     lib.als_gs_sweep_levels.argtypes = [C.POINTER(GsSweepParams), _vp, _i64, _vp]

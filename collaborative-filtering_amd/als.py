@@ -122,8 +122,10 @@ class ALS:
         # "float64": every row's normal equations are accumulated, factorised and solved in fp64 (the reference's
         # arithmetic type) - for the small-lambda corner of the tuner's search space, where rank-deficient rows
         # have cond ~ 1/lambda; factors stay fp32 in HBM.  Several times slower than fp32.
-        if solve_dtype not in ("auto", "float32", "float64"):
-            raise ValueError("solve_dtype must be 'auto', 'float32' or 'float64'")
+        # "refine": "auto" with the flagged rows of the U-step brought to fp64 accuracy by iterative refinement on their
+        # fp32 factor instead of an fp64 factorisation; opt-in.
+        if solve_dtype not in ("auto", "refine", "float32", "float64"):
+            raise ValueError("solve_dtype must be 'auto', 'refine', 'float32' or 'float64'")
         self._solve_dtype = solve_dtype
         if graph_build not in ("host", "device"):
             raise ValueError("graph_build must be 'host' (reference-identical, dense n x n) or 'device'")

@@ -26,14 +26,16 @@ class HipBackend:
 
     GRAM_MODES = {"f32": 0, "f16x2": 1, "f64": 2}
     COND_LIMIT = 300.0
+    SOLVE_DTYPES = ("auto", "refine", "float32", "float64")
+    REFINE_MAX_STEPS = 5
     PLANES_MAX_FLOATS = 16 << 20       # 64 MiB table: V / Z of every BASELINE shape, never U
     PLANES_MAX_FLOATS_K128 = (1 << 31) - 1     # k = 128: any table als_row_solve accepts (element offsets < 2^31)
 
     def __init__(self, device: torch.device, gram: str = "f16x2", solve_dtype: str = "auto"):
         if gram not in ("f32", "f16x2"):
             raise ValueError("gram must be 'f16x2' or 'f32'")
-        if solve_dtype not in ("auto", "float32", "float64"):
-            raise ValueError("solve_dtype must be 'auto', 'float32' or 'float64'")
+        if solve_dtype not in self.SOLVE_DTYPES:
+            raise ValueError("solve_dtype must be 'auto', 'refine', 'float32' or 'float64'")
         # solve_dtype="float64": Gram, Cholesky and substitutions of every row in fp64 (ALS_GRAM_F64); `gram` then
         # has no effect
         self.solve_dtype = solve_dtype
@@ -72,9 +74,20 @@ class HipBackend:
         # row of 4100 ratings, so about 1e-3 at COND_LIMIT; 1e-5 on well-conditioned rows
         # (tests/test_gpu_row_auto.py, profiles/row_auto_kernel_test_margins.json).
         # ALS_COND_LIMIT overrides.
-        self.cond_limit = float(os.environ.get("ALS_COND_LIMIT", self.COND_LIMIT)) if solve_dtype == "auto" else 0.0
+        # solve_dtype="refine": "auto" in everything above - same estimate, same limit, same flagged rows - but a plain
+        # solve call (the U-step) hands the flagged rows to als_row_solve_refine: a few steps of iterative refinement
+        # on the row's own fp32 factor, the residual in fp64 from the ratings.  Rows that do
+        # not contract within refine_max_steps, whose fp32 factorisation breaks down or that are longer than
+        # SPLIT_CHUNK fall back to the fp64 kernel: _fallback_count of the _redo_count flagged rows; _refine_steps[s]
+        # counts the rows accepted after s steps.  All three describe the last row_solve call.
+        self.cond_limit = (float(os.environ.get("ALS_COND_LIMIT", self.COND_LIMIT))
+                           if solve_dtype in ("auto", "refine") else 0.0)
         self._redo_count = torch.zeros(1, dtype=torch.int32, device=device)
         self._redo_rows: dict = {}         # rows of the orientation -> int32 list buffer
+        self.refine_max_steps = self.REFINE_MAX_STEPS
+        self._fallback_count = torch.zeros(1, dtype=torch.int32, device=device)
+        self._fallback_rows: dict = {}
+        self._refine_steps = torch.zeros(9, dtype=torch.int32, device=device)
         self.cond_probe: Optional[torch.Tensor] = None     # diagnostics: float32 [nrows], receives every row's estimate
 
     # -- helpers -------------------------------------------------------------
@@ -139,6 +152,15 @@ class HipBackend:
             p.cond_limit = self.cond_limit
             p.redo_count, p.redo_rows = _p(self._redo_count), _p(self._redo_rows[side.nrows])
             p.cond_out = _p(self.cond_probe) if (self.cond_probe is not None and self.cond_probe.numel() >= side.nrows) else None
+            if self.solve_dtype == "refine":
+                if side.nrows not in self._fallback_rows:
+                    self._fallback_rows[side.nrows] = torch.empty(max(side.nrows, 1), dtype=torch.int32, device=self.device)
+                r = _hip.RefineParams()
+                r.max_steps = int(self.refine_max_steps)
+                r.fallback_count, r.fallback_rows = _p(self._fallback_count), _p(self._fallback_rows[side.nrows])
+                r.step_hist = _p(self._refine_steps)
+                self._check(self.lib.als_row_solve_refine(C.byref(p), C.byref(r), self._stream()), "als_row_solve_refine")
+                return
         self._check(self.lib.als_row_solve(C.byref(p), self._stream()), "als_row_solve")
 
     # -- K2 ------------------------------------------------------------------

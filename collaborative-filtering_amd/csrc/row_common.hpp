@@ -142,4 +142,47 @@ __device__ __forceinline__ void backward_solve(const float* __restrict__ Ls, con
     for (int rr = 0; rr < NR; ++rr) x[rr] = rs[rr];
 }
 
+// L y = b with L in LDS (block columns), the mirror of backward_solve for a right-hand side that arrives after the
+// factorisation (k_row_refine: the residual of a refinement step; inside the factorisation the forward substitution
+// rides along the panels).  Lane (+64 rr) owns unknown i = lane + 64 rr and reads its ROW of block column J - the
+// b128 reads of chol_panel, step 2 - one block column ahead of the 16 dependent steps.  The running right-hand side
+// is kept pre-scaled by 1 / L_ii, so a step is one v_readlane + one FMA per row group.  S.b is read, S.y written.
+template <int KB>
+__device__ __forceinline__ void forward_solve(const float* __restrict__ Ls, Chol<KB>& S, int lane) {
+    using C = KCfg<KB>;
+    constexpr int KP = C::KP, NR = C::NR;
+    const int si = (lane >> 2) & 3;
+    float rs[NR];
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) rs[rr] = S.b[rr] * S.di[rr];
+#pragma unroll
+    for (int J = 0; J < KB; ++J) {
+        float cf[NR][16];
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            if (64 * rr + 63 <= 16 * J) continue;                    // every row of the group is final
+            const int i = lane + 64 * rr;
+            const int rowi = min(max(i, 16 * J), KP - 1) - 16 * J;   // lanes above the panel: dummy row, masked below
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(Ls + C::lcol_off(J) + rowi * 16 + ((g ^ si) << 2));
+                cf[rr][4 * g] = v.x * S.di[rr]; cf[rr][4 * g + 1] = v.y * S.di[rr];
+                cf[rr][4 * g + 2] = v.z * S.di[rr]; cf[rr][4 * g + 3] = v.w * S.di[rr];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int p = 16 * J + t;
+            const float yp = readlane_f(rs[p >> 6], p & 63);
+#pragma unroll
+            for (int rr = 0; rr < NR; ++rr) {
+                if (64 * rr + 63 <= p) continue;
+                rs[rr] = fmaf((lane + 64 * rr > p) ? -cf[rr][t] : 0.f, yp, rs[rr]);
+            }
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) S.y[rr] = rs[rr];
+}
+
 }  // namespace

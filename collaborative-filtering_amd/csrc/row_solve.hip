@@ -25,6 +25,7 @@
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "row_common.hpp"
+#include "row_f64_common.hpp"
 #include "slot_fold.hpp"
 
 namespace {
@@ -1151,6 +1152,260 @@ int launch_row_solve(const als_row_solve_params* p, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
+// ---------------------------------------------------------------------------
+// solve_dtype "refine" (als_row_solve_refine): the flagged rows by fp64 iterative refinement on
+// their fp32 factor.  A fixed grid of one-wave workers walks redo_rows[0 .. *redo_count) as k_row_redo_f64 does.
+//
+// Per row: the fp32 Gram / regulariser / blocked Cholesky of the fp32 kernel (gram_accumulate, chol_panels - the
+// primal form whatever the row's class), x0 from the substitutions, then steps of
+//     r = F^T (rho - F x) - lambda x   in fp64 from the ratings,   d = (L L^T)^-1 (r / 2^e) 2^e   in fp32,   x += d.
+// The fp64 pass over the ratings (refine_pass) has two layouts per 64-rating chunk: lane per rating for the dots
+// f_j.x (the lane walks its own factor row, x broadcast from LDS in storage order), lane per unknown for F^T t
+// (rating by rating, t_j broadcast with v_readlane) - O(n k) fp64 FMAs a step against the O(k^3) of a factorisation.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t abs_bits(float v) { return (uint32_t)__float_as_int(v) & 0x7FFFFFFFu; }
+
+// se = sum_j e_j, se2 = sum_j e_j^2 with e_j = (vals_j - mu - bias_other_j) - f_j.x (wave totals); RES: also
+// r[rr] = sum_j F[j][col of perm position lane + 64 rr] (e_j - bold), this lane's part of F^T (rho - F x).
+// xs: x in storage order, fp64, in LDS.  Lanes past the end of the row gather the zero row with rho = 0.
+template <int KB, bool RES>
+__device__ __forceinline__ void refine_pass(const als_row_solve_params& P, int64_t beg, int len, double mu, double bold,
+                                            const double* __restrict__ xs, const int (&colp)[KCfg<KB>::NR],
+                                            double (&r)[KCfg<KB>::NR], double& se, double& se2, int lane) {
+    constexpr int KP = KCfg<KB>::KP, NR = KCfg<KB>::NR;
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) r[rr] = 0.0;
+    double s1 = 0.0, s2 = 0.0;
+    for (int base = 0; base < len; base += 64) {
+        const int t = base + lane;
+        const bool ok = t < len;
+        const int idx = ok ? P.indices[beg + t] : P.F_zero_row;
+        const float v = ok ? P.vals[beg + t] : 0.f;
+        const float bo = ok ? P.bias_other[idx] : 0.f;
+        const double rb = ok ? ((double)v - mu - (double)bo) : 0.0;        // as gram_pass_f64 forms it
+        const float* fr = P.F + (uint32_t)(idx * P.ld);                    // < 2^31 elements (checked by the launcher)
+        double u = 0.0;
+#pragma unroll 8
+        for (int c4 = 0; c4 < KP / 4; ++c4) {
+            const f32x4 f = *reinterpret_cast<const f32x4*>(fr + 4 * c4);
+            u = fma((double)f.x, xs[4 * c4], u);
+            u = fma((double)f.y, xs[4 * c4 + 1], u);
+            u = fma((double)f.z, xs[4 * c4 + 2], u);
+            u = fma((double)f.w, xs[4 * c4 + 3], u);
+        }
+        const double ej = ok ? rb - u : 0.0;
+        s1 += ej;
+        s2 = fma(ej, ej, s2);
+        if constexpr (RES) {
+            const double tl = ok ? ej - bold : 0.0;
+            const int nvalid = min(64, len - base);
+            for (int j0 = 0; j0 < nvalid; j0 += 8) {         // (a group may run past nvalid: zero rows, t = 0)
+                float fv[8][NR];
+                double tj[8];
+#pragma unroll
+                for (int w = 0; w < 8; ++w) {
+                    const int o = __builtin_amdgcn_readlane(idx, j0 + w) * P.ld;
+                    tj[w] = f64row::readlane_d(tl, j0 + w);
+#pragma unroll
+                    for (int rr = 0; rr < NR; ++rr) fv[w][rr] = P.F[(uint32_t)o + colp[rr]];
+                }
+#pragma unroll
+                for (int w = 0; w < 8; ++w)
+#pragma unroll
+                    for (int rr = 0; rr < NR; ++rr) r[rr] = fma((double)fv[w][rr], tj[w], r[rr]);
+            }
+        }
+    }
+    se = wave_sum_d(s1);
+    se2 = wave_sum_d(s2);
+}
+
+// One listed row.  Returns the number of steps after which it was accepted (outputs stored), or -1: nothing stored,
+// the row goes to the fp64 kernel.  Every decision is taken on wave-uniform values (v_readlane / ballot results).
+template <int KB, int MODE>
+__device__ __forceinline__ int refine_row(const als_row_solve_params& P, int max_steps, int row, double mu, float S,
+                                          float* __restrict__ Ls, double* __restrict__ xs, int lane) {
+    using C = KCfg<KB>;
+    constexpr int KP = C::KP, NR = C::NR;
+    const int c = lane & 15, q = lane >> 4;
+    const int64_t r64 = row;
+    const int64_t beg = P.indptr[row];
+    const int64_t nrat = P.indptr[row + 1] - beg;
+    if (nrat > ALS_SPLIT_CHUNK) return -1;               // (the fp32 Gram of a longer row is summed from segments)
+    const int len = (int)nrat;
+    const float bself = P.bias_self[row];                // read once: bias_out may alias bias_self
+    const float lamr = P.lambda_row ? P.lambda_row[row] : P.lambda_scalar;
+
+    // ---- the preconditioner: finish_row's fp32 system and factor (no by-products, no extra terms) ----
+    Chol<KB> Sx;
+    {
+        RowAcc<KB> A;
+        A.zero();
+        gram_accumulate<KB, MODE>(A, P.indices + beg, P.vals + beg, len, P.F, P.ld, P.F_zero_row, P.bias_other,
+                                  (float)mu, bself, lane, Ls, S);
+        if (MODE != 0) {
+            const float un = P.F_scale[1];
+#pragma unroll
+            for (int a = 0; a < C::NACC; ++a) A.acc[a] *= un;
+        }
+#pragma unroll
+        for (int b = 0; b < KB; ++b) { A.rhs[b] += __shfl_xor(A.rhs[b], 16, 64); A.rhs[b] += __shfl_xor(A.rhs[b], 32, 64); }
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            float bsel = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * rr + e < KB) bsel = (q == e) ? A.rhs[4 * rr + e] : bsel;
+            Sx.b[rr] = bsel; Sx.di[rr] = 0.f; Sx.y[rr] = 0.f;
+        }
+        const float lam = lamr + ALS_EPS;
+#pragma unroll
+        for (int J = 0; J < KB; ++J) {
+            const float dv = (perm_to_col<KB>(16 * J + c) < P.k) ? lam : 1.0f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) A.acc[blk_idx(J, J)][r] += (4 * q + r == c) ? dv : 0.f;
+        }
+        chol_panels<KB, 0, true>(A, Sx, Ls, lane);
+    }
+    if (!chol_spd<KB>(Sx, lane)) return -1;
+    float x0[NR];
+    backward_solve<KB>(Ls, Sx, x0, lane);
+
+    double x[NR];
+    int colp[NR];
+    bool in[NR];
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr) {
+        in[rr] = lane + 64 * rr < KP;
+        colp[rr] = perm_to_col<KB>(min(lane + 64 * rr, KP - 1));
+        x[rr] = in[rr] ? (double)x0[rr] : 0.0;
+    }
+    const double lam = (double)lamr + 1e-10;            // as finish_row_f64
+    const double bold = (double)bself;
+    const float inf = __builtin_inff();
+    double r[NR], se, se2, dprev = 0.0;
+    int accepted = -1;
+    for (int t = 1; t <= max_steps; ++t) {
+        wave_lds_sync();
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr)
+            if (in[rr]) xs[colp[rr]] = x[rr];
+        wave_lds_sync();
+        refine_pass<KB, true>(P, beg, len, mu, bold, xs, colp, r, se, se2, lane);
+        uint32_t mb = 0;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            r[rr] = in[rr] ? fma(-lam, x[rr], r[rr]) : 0.0;
+            mb = max(mb, abs_bits((float)r[rr]));
+        }
+        const float rm = wave_max_nonneg(__int_as_float((int)mb));
+        if (!(rm < inf)) return -1;
+        // r / 2^e with 2^e <= max|r| < 2^(e+1): an exact scaling, the fp32 solve sees a right-hand side of size 1
+        const int e = (rm > 0.f) ? (int)((__float_as_int(rm) >> 23) & 0xff) - 127 : 0;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) Sx.b[rr] = (float)__builtin_ldexp(r[rr], -e);
+        forward_solve<KB>(Ls, Sx, lane);
+        float d[NR];
+        backward_solve<KB>(Ls, Sx, d, lane);
+        uint32_t db = 0, xb = 0;
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            const float dr = in[rr] ? d[rr] : 0.f;
+            x[rr] += __builtin_ldexp((double)dr, e);
+            db = max(db, abs_bits(dr));
+            xb = max(xb, abs_bits((float)x[rr]));
+        }
+        const float dm = wave_max_nonneg(__int_as_float((int)db));
+        const float xm = wave_max_nonneg(__int_as_float((int)xb));
+        if (!(dm < inf) || !(xm < inf)) return -1;
+        const double dn = __builtin_ldexp((double)dm, e);
+        const double pred = (t == 1) ? dn : dn * dn / dprev;     // (dprev == 0 was accepted a step earlier)
+        if (pred <= 0x1p-29 * (double)xm) { accepted = t; break; }
+        if (t > 1 && dn > 0.25 * dprev) return -1;
+        dprev = dn;
+    }
+    if (accepted < 0) return -1;
+
+    // ---- epilogue: bias and statistics in fp64 from the ratings with the final x (finish_row_f64's formulas with
+    // sum rho - (F^T 1).x and the quadratic form evaluated rating by rating) ----
+    wave_lds_sync();
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr)
+        if (in[rr]) xs[colp[rr]] = x[rr];
+    wave_lds_sync();
+    refine_pass<KB, false>(P, beg, len, mu, bold, xs, colp, r, se, se2, lane);
+    const double nnz = (double)len;
+    const double lb = (double)(P.lambda_bias_row ? P.lambda_bias_row[row] : P.lambda_bias_scalar);
+    const double bnew = se / (nnz + lb + 1e-10);
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr)
+        if (in[rr]) P.X_out[r64 * P.ld + colp[rr]] = (float)x[rr];
+    if (lane == 0) {
+        P.bias_out[row] = (float)bnew;
+        if (P.stat_out) {
+            P.stat_out[2 * r64] = (float)(se - nnz * bnew);
+            P.stat_out[2 * r64 + 1] = (float)(se2 - 2.0 * bnew * se + nnz * bnew * bnew);
+        }
+    }
+    return accepted;
+}
+
+template <int KB, int MODE>
+__global__ __launch_bounds__(64, KCfg<KB>::MINW)
+void k_row_refine(const als_row_solve_params P, const als_refine_params R) {
+    using C = KCfg<KB>;
+    __shared__ __attribute__((aligned(16))) float Ls[C::LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) double xs[C::KP];
+    const int lane = threadIdx.x & 63;
+    const int count = *P.redo_count;
+    const double mu = *P.mu;
+    const float S = (MODE != 0) ? P.F_scale[0] : 1.f;
+    for (int e = blockIdx.x; e < count; e += gridDim.x) {
+        const int row = P.redo_rows[e];
+        const int steps = refine_row<KB, MODE>(P, R.max_steps, row, mu, S, Ls, xs, lane);
+        if (lane == 0) {
+            if (steps < 0) R.fallback_rows[atomicAdd(R.fallback_count, 1)] = row;
+            else if (R.step_hist) atomicAdd(R.step_hist + steps, 1);
+        }
+        wave_lds_sync();                    // the images are reused by the next row
+    }
+}
+
+// both lists of the refine call start empty; `mirror`: the call is not a plain solve, every flagged row went to fp64
+__global__ void k_refine_lists(const int32_t* __restrict__ redo_count, const int32_t* __restrict__ redo_rows,
+                               als_refine_params R, int mirror) {
+    const int n = mirror ? *redo_count : 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) R.fallback_rows[i] = redo_rows[i];
+    if (threadIdx.x == 0) *R.fallback_count = n;
+    if (R.step_hist && threadIdx.x < 9) R.step_hist[threadIdx.x] = 0;
+}
+
+template <int KB, int MODE>
+int launch_row_refine(const als_row_solve_params* p, const als_refine_params* r, hipStream_t st) {
+    // as launch_row_redo_f64: enough waves to fill the device when many rows were flagged, cheap when none was
+    static int grid_of[64];
+    auto kern = k_row_refine<KB, MODE>;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return ALS_E_LAUNCH;
+    if (grid_of[dev] == 0) {
+        int nb = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 64, 0) != hipSuccess || nb < 1)
+            return ALS_E_LAUNCH;
+        grid_of[dev] = prop.multiProcessorCount * (nb > 8 ? 8 : nb);
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid_of[dev]), dim3(64), 0, st, *p, *r);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+template <int KB>
+int launch_row_refine_mode(const als_row_solve_params* p, const als_refine_params* r, hipStream_t st) {
+    // (pre-split operands are a property of the fp32 launch: the same fp16 terms, so the same Gram, come out of the
+    // in-kernel split; its less exact right-hand side only moves the starting point x0)
+    return p->gram_mode == ALS_GRAM_F16X2 ? launch_row_refine<KB, 1>(p, r, st) : launch_row_refine<KB, 0>(p, r, st);
+}
+
 }  // namespace
 
 int als_row_solve_f64_dispatch(const als_row_solve_params* p, hipStream_t st);     // row_solve_f64.hip
@@ -1176,7 +1431,8 @@ extern "C" int als_factor_scale(const float* F, int64_t nfloats, float* scale, v
     return launch_factor_scale(F, nfloats, scale, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int als_row_solve(const als_row_solve_params* p, void* stream) {
+// the fp32 launches of a call and - `with_redo` - the fp64 kernel on the rows they flagged
+static int row_solve_checked(const als_row_solve_params* p, void* stream, bool with_redo) {
     if (!p) return ALS_E_BADARG;
     const int ld = als_padded_k(p->k);
     if (ld < 0) return ALS_E_BADK;
@@ -1214,6 +1470,33 @@ extern "C" int als_row_solve(const als_row_solve_params* p, void* stream) {
     ALS_DISPATCH_KB(ld / 16, rc = launch_row_solve<KB>(p, st));
 #endif
     // rows the fp32 kernels flagged (condition estimate above the limit, or a broken-down factorisation): fp64
-    if (rc == 0 && redo) rc = als_row_redo_f64_dispatch(p, st);
+    if (rc == 0 && redo && with_redo) rc = als_row_redo_f64_dispatch(p, st);
     return rc;
+}
+
+extern "C" int als_row_solve(const als_row_solve_params* p, void* stream) { return row_solve_checked(p, stream, true); }
+
+extern "C" int als_row_solve_refine(const als_row_solve_params* p, const als_refine_params* r, void* stream) {
+    if (!p || !r || !(p->cond_limit > 0.f) || (p->gram_mode != ALS_GRAM_F32 && p->gram_mode != ALS_GRAM_F16X2) ||
+        r->max_steps < 1 || r->max_steps > 8 || !r->fallback_count || !r->fallback_rows)
+        return ALS_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const bool plain = p->reserved0 == 0 && p->X_out && p->bias_out && !p->gram_out && !p->factor_out && !p->rhs_out &&
+                       !p->colsum_out && !p->sumr_out && !p->sumr2_out && !p->rhs_extra && !p->diag_extra;
+    int rc = row_solve_checked(p, stream, !plain);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(k_refine_lists, dim3(1), dim3(64), 0, st, p->redo_count, p->redo_rows, *r, plain ? 0 : 1);
+    if (!plain) return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    rc = ALS_E_BADK;
+#ifdef ALS_KB_ONLY
+    if (p->ld / 16 == ALS_KB_ONLY) rc = launch_row_refine_mode<ALS_KB_ONLY>(p, r, st);
+#else
+    ALS_DISPATCH_KB(p->ld / 16, rc = launch_row_refine_mode<KB>(p, r, st));
+#endif
+    if (rc != 0) return rc;
+    // what the refinement gave up on: the fp64 kernel, unchanged, on the fallback list
+    als_row_solve_params q = *p;
+    q.redo_count = r->fallback_count;
+    q.redo_rows = r->fallback_rows;
+    return als_row_redo_f64_dispatch(&q, st);
 }

@@ -103,13 +103,13 @@ class _Engine(_Serving):
         self.has_item_stats = hasattr(be, "item_stats")
         has_sum_pairs = hasattr(be, "sum_pairs")
         # The V-step in fp64 with fp64 by-products (item Grams, right-hand sides, Cholesky factors, column sums) for
-        # the W-step / the sweep / the item statistics: always under solve_dtype="float64"; under "auto" when a
+        # the W-step / the sweep / the item statistics: always under solve_dtype="float64"; under "auto" / "refine" when a
         # feature's ridge parameter is (nearly) absent - lambda_w missing means 0 (scripts/als.py:497) - because the
         # (d k)^2 system is then singular up to the 1e-10 the reference adds and normal equations assembled from
         # fp32 Grams (rounding ~3e-7 |A|) are no longer positive definite, let alone accurate.
         lw_min = min((float(model.lambda_w.get(f, 0.0)) for f in self.feat_names), default=float("inf"))
         mode = getattr(be, "solve_dtype", "float32")
-        self.v_f64 = bool(self.native and (mode == "float64" or (mode == "auto" and lw_min + EPS < W_F64_BELOW)))
+        self.v_f64 = bool(self.native and (mode == "float64" or (mode in ("auto", "refine") and lw_min + EPS < W_F64_BELOW)))
         self.f64kw = {"f64": True} if self.v_f64 else {}        # what the V-step-side backend calls are given then
         self.use_graph = S_csr is not None
         # Sweep modes with several ranks (one rank: all the same thing):

@@ -173,7 +173,11 @@ typedef struct als_row_solve_params {
      * whose closed-form statistics would cancel) writes none of its results - its row id is appended to redo_rows
      * (order irrelevant) and the call then redoes exactly those rows in fp64 (Gram, factorisation, substitutions:
      * the kernel of ALS_GRAM_F64 on the whole row).  The relative error of an fp32 row is then bounded by about
-     * cond_limit * 3e-7 (the fp32 rounding of its Gram).  f32 / f16x2 modes only. */
+     * cond_limit * 3e-7 (the fp32 rounding of its Gram).  f32 / f16x2 modes only.
+     * The fp64 redo costs about 20 fp32 rows per row: over a long fit at small lambda most user rows end up flagged and
+     * the U-step grows 20-fold (profiles/r03_auto_redo_over_a_long_fit.txt).  als_row_solve_refine (solve_dtype
+     * "refine") takes the same flagged rows through fp64 iterative refinement on their fp32 factor instead and leaves
+     * only those that do not converge to the fp64 kernel. */
     float          cond_limit;          /* 0 = off */
     int32_t        byproducts_f64;      /* ALS_GRAM_F64 only, != 0: gram_out, rhs_out, colsum_out, sumr_out, sumr2_out are
                                            arrays of DOUBLE (same shapes) - for the W-step / item statistics in fp64
@@ -196,6 +200,35 @@ typedef struct als_row_solve_params {
 } als_row_solve_params;
 
 int als_row_solve(const als_row_solve_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * als_row_solve_refine - als_row_solve with cond_limit > 0 (solve_dtype "refine"), the flagged rows by fp64
+ * ITERATIVE REFINEMENT on their fp32 factor instead of an fp64 factorisation.
+ *
+ * The fp32 launches and the list of flagged rows (redo_rows / redo_count) are those of als_row_solve.  A PLAIN solve
+ * call (X_out and bias_out; gram_out, factor_out, rhs_out, colsum_out, sumr_out, sumr2_out, rhs_extra and diag_extra
+ * all NULL; reserved0 == 0) then hands the list to k_row_refine: per row the fp32 Gram (f32 or f16x2 as the call
+ * says, always the primal k x k form) and its Cholesky factor L, x0 from the fp32 substitutions, and at most
+ * max_steps times
+ *     r = F^T (rho - F x) - lambda x      fp64, from the ratings (rho = vals - mu - bias_other - bias_self)
+ *     d = (L L^T)^-1 r                    fp32, r scaled by a power of two
+ *     x += d                              fp64
+ * until the predicted remaining error |d_t|^2 / |d_t-1| (max norms; |d_1| at the first step) is at most
+ * 2^-29 |x|.  Bias and stat_out of an accepted row are evaluated in fp64 from the ratings with the final x; x and
+ * the bias are rounded to fp32 once.  A row that does not contract (|d_t| > |d_t-1| / 4), that runs out of steps,
+ * whose fp32 factorisation breaks down or that has more than ALS_SPLIT_CHUNK ratings is appended to fallback_rows
+ * and redone by the fp64 kernel of als_row_solve, as every flagged row of any other call is (fallback_count ==
+ * redo_count then).  *p->redo_count keeps its meaning: the number of rows flagged.
+ * Needs cond_limit > 0 and gram_mode ALS_GRAM_F32 or ALS_GRAM_F16X2 (ALS_E_BADARG otherwise).
+ * ------------------------------------------------------------------------- */
+typedef struct als_refine_params {
+    int32_t  max_steps;         /* 1 ... 8 */
+    int32_t* fallback_count;    /* device int32[1]; the call resets it; afterwards: rows redone by the fp64 kernel */
+    int32_t* fallback_rows;     /* device int32[rows of this orientation] (only the first fallback_count are used) */
+    int32_t* step_hist;         /* nullable device int32[9]: rows accepted after s steps, reset by the call */
+} als_refine_params;
+
+int als_row_solve_refine(const als_row_solve_params* p, const als_refine_params* r, void* stream);
 
 /* Operand scale of the f16x2 Gram for a factor matrix F of `nfloats` floats (a multiple of 4, F 16-byte aligned):
  * scale[0] = S = 2^j with S max|F| in [2^14, 2^15) (clamped to 2^-60 ... 2^60), scale[1] = 1 / S^2; scale[2 .. 3]
