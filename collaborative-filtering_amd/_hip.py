@@ -25,7 +25,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_recommend_topk_masked", "als_rank_count_masked",
            "als_fold_in", "als_fold_in_items", "als_explain", "als_mmr_rerank", "als_list_diversity",
            "als_row_inv_norms", "als_similar_workspace_bytes", "als_similar_topk",
-           "als_audience_workspace_bytes", "als_audience_topk", "als_group_workspace_bytes", "als_group_topk")
+           "als_audience_workspace_bytes", "als_audience_topk", "als_group_workspace_bytes", "als_group_topk",
+           "als_row_whitener", "als_explore_workspace_bytes", "als_explore_topk")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -192,6 +193,10 @@ def load():
     lib.als_group_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
     lib.als_group_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_row_whitener.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp]
+    lib.als_explore_workspace_bytes.argtypes = [C.c_int, _i64, _i64, C.c_int, C.c_int]
+    lib.als_explore_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp,
+                                     _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]
@@ -201,7 +206,8 @@ def load():
     for name in EXPORTS:
         if name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64", "als_spd_solve_workspace_bytes",
                         "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
-                        "als_similar_workspace_bytes", "als_audience_workspace_bytes", "als_group_workspace_bytes"):
+                        "als_similar_workspace_bytes", "als_audience_workspace_bytes", "als_group_workspace_bytes",
+                        "als_explore_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     lib.als_spd_solve_workspace_bytes.restype = C.c_size_t
     lib.als_recommend_workspace_bytes.restype = C.c_size_t
@@ -209,5 +215,6 @@ def load():
     lib.als_similar_workspace_bytes.restype = C.c_size_t
     lib.als_audience_workspace_bytes.restype = C.c_size_t
     lib.als_group_workspace_bytes.restype = C.c_size_t
+    lib.als_explore_workspace_bytes.restype = C.c_size_t
     _lib = lib
     return lib

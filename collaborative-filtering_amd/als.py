@@ -538,6 +538,66 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.recommend_group(g_ptr, g_users, N, aggregate, features, exclude_seen, new_items, filters)
 
+    # ---------------------------------------------------------- exploration
+    def recommend_explore(self, users=None, N: int = 10, *, beta: float = 1.0, mode: str = "ucb", seed=None,
+                          features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True, items=None,
+                          filter_items=None, return_leverage: bool = False, new_items=None):
+        """Uncertainty-aware top-N over the whole catalogue: `recommend` with every item ranked by
+
+          key(u, i) = score(u, i) + beta * sigma(u, i),   sigma^2 = z_i^T A_u^-1 z_i  (the leverage of `explain`),
+
+        A_u = Z_S^T Z_S + (lambda_u + 1e-10) I over the items S the user rated in the last fit: up to the noise
+        variance sigma^2 is the posterior variance of the latent score under the user's own ridge problem.  beta > 0
+        explores (LinUCB: items the history says little about get a bonus), beta < 0 plays safe, beta = 0 is
+        `recommend` bit for bit.  Returns (items int64 [B, N], keys float64 [B, N]) ordered by key descending, ties to
+        the lower item id, unused slots -1 / -inf; with `return_leverage` also leverage float64 [B, N] (0 in unused
+        slots).  `users`, `features`, `exclude_seen`, `items`, `filter_items` as in `recommend`; `new_items` is not
+        supported.
+
+        Contract (mode="ucb"): keys[b, j] == np.float32(score + np.float32(np.float32(beta) *
+        np.sqrt(np.float32(leverage[b, j])))) with score the float32 of `predict` - leverage is the fp32 value the
+        kernel formed on the matrix cores from W = float32(L^-1), L the fp64 Cholesky factor of A_u; it agrees with
+        `explain(...).leverage` to fp32 rounding of a k-term sum.  A user without ratings has sigma^2 = |z_i|^2 /
+        (lambda_u + 1e-10).  One fused kernel scores, forms the leverages and selects (als_row_whitener,
+        als_explore_topk); nothing m x n or k x n is formed.
+
+        mode="thompson": instead of a bonus, one posterior sample per batch row - with eps =
+        np.random.default_rng(seed).standard_normal((B, k)).astype(np.float32), row b is ranked by the scores of
+        u_b + beta * W_b^T eps_b (cov = beta^2 A_u^-1) through `recommend`'s kernel; `seed` is required, the keys are
+        the sampled scores, and the leverage returned is that of the listed items.  Local to the calling rank."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        beta, seed = validate.explore_args(beta, mode, seed, new_items)
+        u = validate.user_ids(users, self.U.shape[0])
+        filters = validate.item_filters(items, filter_items, self.V.shape[0])
+        if u.size == 0:
+            out = (np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64), np.empty((0, N)))
+        else:
+            with _on(self._eng.dev):
+                out = self._eng.recommend_explore(self._dev_i32(u), N, beta, seed, features, exclude_seen, filters)
+        return out if return_leverage else out[:2]
+
+    def recommend_new_explore(self, R_new, N: int = 10, *, beta: float = 1.0, mode: str = "ucb", seed=None,
+                              features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                              exclude_seen: bool = True, items=None, filter_items=None,
+                              return_leverage: bool = False, new_items=None):
+        """`recommend_explore` for users outside the fit: the rows of `R_new` are folded in as in `recommend_new`
+        (`n_sweeps`), A is formed from the same rows, and base score, leverage and key are those of the folded user -
+        the case exploration is made for: a short history pins down few directions, and sigma says which."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        T = validate.sweeps(n_sweeps)
+        beta, seed = validate.explore_args(beta, mode, seed, new_items)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        filters = validate.item_filters(items, filter_items, self.V.shape[0])
+        if indptr.size == 1:
+            out = (np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64), np.empty((0, N)))
+        else:
+            with _on(self._eng.dev):
+                out = self._eng.recommend_new_explore(indptr, indices, vals, N, beta, seed, features, T, exclude_seen,
+                                                      filters)
+        return out if return_leverage else out[:2]
+
     # ---------------------------------------------------------- evaluation
     def rank_of(self, users, items, *, features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
                 allow_items=None, filter_items=None):

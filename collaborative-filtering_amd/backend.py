@@ -54,6 +54,7 @@ class HipBackend:
         self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
         self._aud_ws: Optional[torch.Tensor] = None        # slice lists of als_audience_topk
         self._grp_ws: Optional[torch.Tensor] = None        # slice lists of als_group_topk
+        self._exp_ws: Optional[torch.Tensor] = None        # slice lists of als_explore_topk
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -503,3 +504,35 @@ class HipBackend:
                                             self.GROUP_AGGREGATES[aggregate], topn, nsl, _p(top_val), _p(top_idx),
                                             _p(top_cnt), _p(self._grp_ws) if need > 0 else None, need,
                                             self._stream()), "als_group_topk")
+
+    # -- K16 -------------------------------------------------------------------
+    def row_whitener(self, *, k, ld, indptr, indices, rows, n, Z, lam_u, W_out, status):
+        """W_out fp32 [rows, ld, ld] = float32(L^-1), L the lower Cholesky factor of Z_S^T Z_S + (lam_u + 1e-10) I
+        of every work row (work row w reads CSR row rows[w], or row w when `rows` is None): als_row_whitener."""
+        nrows = indptr.numel() - 1 if rows is None else rows.numel()
+        assert W_out.is_contiguous() and W_out.shape[1:] == (ld, ld) and W_out.shape[0] >= nrows
+        self._check(self.lib.als_row_whitener(k, ld, nrows, _p(indptr), _p(indices), _p(rows), int(n), _p(Z),
+                                              float(lam_u), _p(W_out), _p(status), self._stream()),
+                    "als_row_whitener")
+
+    def explore_topk(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, W, beta, seen_ptr, seen_idx, allow, topn, top_val,
+                     top_idx, top_cnt, top_lev):
+        """`recommend_topk_masked` (allow None: every item) with the key score + beta * sqrt(|W_b z_i|^2), W fp32
+        [B, ld, ld] by batch row (`row_whitener`); top_lev fp32 [B, topn] receives the leverages of the returned
+        items: als_explore_topk.  The slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES
+        applies."""
+        if allow is not None:
+            self._check_bitmap(allow, n)
+        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
+            seen_ptr = seen_idx = None
+        B = users.numel()
+        assert W.is_contiguous() and W.shape[1:] == (ld, ld) and W.shape[0] >= B
+        nsl = self.recommend_slices()
+        need = int(self.lib.als_explore_workspace_bytes(k, B, n, topn, nsl))
+        if need > 0 and (self._exp_ws is None or self._exp_ws.numel() < need):
+            self._exp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_explore_topk(k, ld, B, _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(W),
+                                              float(beta), _p(seen_ptr), _p(seen_idx), _p(allow), topn, nsl,
+                                              _p(top_val), _p(top_idx), _p(top_cnt), _p(top_lev),
+                                              _p(self._exp_ws) if need > 0 else None, need, self._stream()),
+                    "als_explore_topk")

@@ -320,4 +320,70 @@ __device__ __forceinline__ void solve_l_f64(const double* img, double (&xs)[F64C
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The Gram alone in NATURAL column order (explore.hip: a factor that is triangular in the columns as numbered):
+// gram_pass_f64's loop with block b, position c = column 16 b + c of F - one dword per block and lane instead of
+// the lane's contiguous KB floats - no right-hand side, and the tail lanes masked (they gather row 0).
+// ---------------------------------------------------------------------------------------------------------
+template <int KB, int I0, int I1>
+__device__ __forceinline__ void gram_pass_nat_f64(const float* __restrict__ F, int ld,
+                                                  const int32_t* __restrict__ indices, int64_t beg, int len,
+                                                  double* __restrict__ img, int lane) {
+    constexpr int NB = blk64(I1, 0) - blk64(I0, 0);
+    constexpr int GS = 4;
+    const int c = lane & 15, q = lane >> 4;
+    const float* Fc = F + c;
+    f64x4 acc[NB];
+#pragma unroll
+    for (int a = 0; a < NB; ++a) acc[a] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int base = 0; base < len; base += 64) {
+        const int t = base + lane;
+        const int idx = t < len ? indices[beg + t] : 0;
+        const int off_l = idx * ld;
+        const int nvalid = min(64, len - base);
+#pragma unroll 1
+        for (int g0 = 0; g0 < 16; g0 += GS) {
+            if (4 * g0 >= nvalid) break;
+            float f[GS][KB];
+#pragma unroll
+            for (int s = 0; s < GS; ++s) {
+                const int off = bperm_i(off_l, 4 * (g0 + s) + q);
+#pragma unroll
+                for (int b = 0; b < KB; ++b) f[s][b] = Fc[(uint32_t)off + 16 * b];
+            }
+#pragma unroll
+            for (int s = 0; s < GS; ++s) {
+                const bool live = 4 * (g0 + s) + q < nvalid;
+                double fd[KB];
+#pragma unroll
+                for (int b = 0; b < KB; ++b) fd[b] = live ? (double)f[s][b] : 0.0;
+#pragma unroll
+                for (int I = I0; I < I1; ++I)
+#pragma unroll
+                    for (int K = 0; K <= I; ++K)
+                        acc[blk64(I, K) - blk64(I0, 0)] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                            fd[I], fd[K], acc[blk64(I, K) - blk64(I0, 0)], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int I = I0; I < I1; ++I)
+#pragma unroll
+        for (int K = 0; K <= I; ++K)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                img[blk64(I, K) * 256 + (q + 4 * i) * 16 + c] = acc[blk64(I, K) - blk64(I0, 0)][i];
+}
+
+template <int KB, int I0>
+__device__ __forceinline__ void gram_passes_nat_f64(const float* __restrict__ F, int ld,
+                                                    const int32_t* __restrict__ indices, int64_t beg, int len,
+                                                    double* __restrict__ img, int lane) {
+    if constexpr (I0 < KB) {
+        constexpr int I1 = F64Cfg<KB>::pass_end(I0);
+        gram_pass_nat_f64<KB, I0, I1>(F, ld, indices, beg, len, img, lane);
+        gram_passes_nat_f64<KB, I1>(F, ld, indices, beg, len, img, lane);
+    }
+}
+
 }  // namespace f64row

@@ -189,6 +189,35 @@ def diversity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, diversity:
             "coverage@K": np.unique(top[top >= 0]).size / n_allowed if n_allowed else float("nan"), **extra}
 
 
+def explore_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, betas: Sequence[float] = (0.0, 1.0),
+                 min_rating: Optional[float] = None, features: Optional[Dict[str, np.ndarray]] = None, items=None,
+                 filter_items=None) -> Dict[str, Any]:
+    """What exploration costs and buys: `model.recommend_explore(users, K, beta=beta)` on held-out (user, item)
+    pairs for every beta of `betas` - {"users", "betas": [{"beta", "recall@K", "ndcg@K", "leverage@K",
+    "coverage@K"}, ...]} (plus "filtered_out" with `items` / `filter_items`).
+
+    users, rel(u), recall@K, NDCG@K and coverage@K are `diversity_at_k`'s (same arguments, same pairs left out), so
+    the entry of beta = 0 equals `ranking_at_k`; leverage@K is the mean leverage over all filled slots of all lists
+    (NaN when every list is empty) - it rises with beta as the lists move to what the histories do not cover."""
+    betas = [float(b) for b in betas]
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
+    nan = float("nan")
+    if users.size == 0:
+        return {"users": 0, "betas": [{"beta": b, "recall@K": nan, "ndcg@K": nan, "leverage@K": nan,
+                                       "coverage@K": nan} for b in betas], **extra}
+    n = model.V.shape[0]
+    n_allowed = int(validate.allowed_mask(validate.item_filters(items, filter_items, n), n).sum()) if kw else n
+    out = []
+    for b in betas:
+        top, _, lev = model.recommend_explore(users, K, beta=b, features=features, return_leverage=True, **kw)
+        m = _ranking_metrics(top, ub, cols, n, K)
+        filled = top >= 0
+        out.append({"beta": b, "recall@K": m["recall@K"], "ndcg@K": m["ndcg@K"],
+                    "leverage@K": float(lev[filled].mean()) if filled.any() else nan,
+                    "coverage@K": np.unique(top[filled]).size / n_allowed if n_allowed else nan})
+    return {"users": int(users.size), "betas": out, **extra}
+
+
 def audience_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
                   features: Optional[Dict[str, np.ndarray]] = None, users=None, filter_users=None) -> Dict[str, Any]:
     """recall@K and NDCG@K of `model.recommend_users` on held-out (user, item) pairs: `ranking_at_k` per ITEM - is

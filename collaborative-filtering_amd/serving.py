@@ -1,6 +1,6 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
-`fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users` and
-`recommend_group`.
+`fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
+`recommend_group` and `recommend*_explore`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -97,6 +97,10 @@ class _Serving:
     # workspace.  Looked up through the instance at call time (tests shrink it to cross chunk boundaries).
     REC_BATCH = 1 << 16
     GRAPH_ROWS_MAX_D = 160      # sim feature width the top-k kernel takes (its k)
+    # rows per als_row_whitener / als_explore_topk call: W costs 4 ld^2 bytes per row, so the chunk is what
+    # EXPLORE_W_BYTES hold (4096 rows at k = 64, 655 at k = 160), at most REC_BATCH; EXPLORE_BATCH overrides (tests)
+    EXPLORE_W_BYTES = 64 << 20
+    EXPLORE_BATCH: Optional[int] = None
 
     # ------------------------------------------------------------- helpers
     def _concat_w(self, names, dims, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -739,3 +743,98 @@ class _Serving:
         if total == 0:
             return None, None
         return out_ptr, out_idx
+
+    # ----------------------------------------------------------- exploration
+    @staticmethod
+    def thompson_table(U: torch.Tensor, W: torch.Tensor, eps: torch.Tensor, beta: float) -> torch.Tensor:
+        """One posterior sample per row: u + beta W^T eps (fp32 [B, ld]; U [B, ld], W [B, ld, ld] the whiteners,
+        eps [B, ld] standard normal, zero in the padding columns) - cov(W^T eps) = W^T W = A^-1."""
+        return U + beta * torch.bmm(W.transpose(1, 2), eps.unsqueeze(2)).squeeze(2)
+
+    def _explore_chunks(self, B: int, N: int, beta: float, eps, rows, table_rows, wrows, items: dict, allow, row_name):
+        """als_row_whitener + als_explore_topk over B batch rows in chunks of `EXPLORE_BATCH` rows.  rows(b0, nb) as in
+        `_topk_chunks` (the seen CSR by USER ID); wrows(b0, nb) -> (indptr, indices, rows) of the whitener's work
+        rows; `eps` (fp32 [B, ld], device) switches to Thompson sampling: table_rows(b0, nb) -> (U, b_u, seen_ptr,
+        seen_idx) gathered by BATCH ROW, the sampled table of `thompson_table` goes through als_recommend_topk and the
+        leverages of the returned items are formed from W in torch.  Returns host (items int64, keys float64,
+        leverage float64), each [B, N], unused slots -1 / -inf / 0."""
+        md, ld = self.model, self.ld
+        cb = min(self.REC_BATCH, self.EXPLORE_BATCH or max(1, self.EXPLORE_W_BYTES // (4 * ld * ld)))
+        W = torch.empty(min(B, cb), ld, ld, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        out_items = np.empty((B, N), dtype=np.int64)
+        out_keys = np.empty((B, N), dtype=np.float64)
+        out_lev = np.empty((B, N), dtype=np.float64)
+        for b0 in range(0, B, cb):
+            nb = min(cb, B - b0)
+            indptr, indices, wr = wrows(b0, nb)
+            self.be.row_whitener(k=self.k, ld=ld, indptr=indptr, indices=indices, rows=wr, n=self.n, Z=items["Z"],
+                                 lam_u=md.lambda_u, W_out=W, status=status)
+            _raise_unless_solved(status, "explore", lambda r: row_name(b0 + r))
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            if eps is None:
+                tl = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+                users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+                self.be.explore_topk(users=users, U=U, b_u=b_u, W=W, beta=beta, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                                     allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_lev=tl, **items)
+            else:
+                U, b_u, seen_ptr, seen_idx = table_rows(b0, nb)
+                kw = dict(users=torch.arange(nb, dtype=torch.int32, device=self.dev),
+                          U=self.thompson_table(U[:nb], W[:nb], eps[b0: b0 + nb], beta).contiguous(), b_u=b_u,
+                          seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
+                if allow is None:
+                    self.be.recommend_topk(**kw)
+                else:
+                    self.be.recommend_topk_masked(allow=allow, **kw)
+                y = torch.bmm(items["Z"][ti.clamp(min=0).to(torch.int64)], W[:nb].transpose(1, 2))     # [nb, N, ld]
+                tl = torch.where(ti >= 0, (y * y).sum(dim=2), torch.zeros((), device=self.dev))
+            out_items[b0: b0 + nb] = ti.cpu().numpy()
+            out_keys[b0: b0 + nb] = tv.cpu().numpy()
+            out_lev[b0: b0 + nb] = tl.cpu().numpy()
+        return out_items, out_keys, out_lev
+
+    def _thompson_eps(self, B: int, seed) -> Optional[torch.Tensor]:
+        """default_rng(seed).standard_normal((B, k)) as fp32 on the device, zero padded to ld; None without a seed."""
+        if seed is None:
+            return None
+        eps = np.zeros((B, self.ld), dtype=np.float32)
+        eps[:, : self.k] = np.random.default_rng(seed).standard_normal((B, self.k)).astype(np.float32)
+        return torch.from_numpy(eps).to(self.dev)
+
+    def recommend_explore(self, users_t: torch.Tensor, N: int, beta: float, seed, features, exclude_seen: bool,
+                          filters=None):
+        """Top-N of the users in `users_t` (int32, device) by score + beta * sigma, sigma^2 the leverage of the item
+        under the user's training row; `seed` not None: one Thompson sample per batch row instead.  See
+        `_explore_chunks` for the return."""
+        Z = self._compose_for(features)
+        B = users_t.numel()
+        ptr_d, idx_d, _ = self._csr_dev(self.csr.indptr, self.csr.indices, self.csr.vals)
+        with_seen = exclude_seen and self.nnz > 0
+        none_u = torch.empty(0, dtype=torch.int64, device=self.dev)
+        none_i = torch.empty(0, dtype=torch.int32, device=self.dev)
+
+        def table_rows(b0, nb):
+            us = users_t[b0: b0 + nb].to(torch.int64)
+            seen = self._merged_seen(us, none_u, none_i) if with_seen else (None, None)
+            return (self.U.index_select(0, us), self.b_u.index_select(0, us), *seen)
+        return self._explore_chunks(B, N, beta, self._thompson_eps(B, seed), self._fitted_rows(users_t, exclude_seen),
+                                    table_rows, lambda b0, nb: (ptr_d, idx_d, users_t[b0: b0 + nb]),
+                                    self._item_side(Z), self.allow_bitmap(filters, self.n),
+                                    lambda w: f"user {int(users_t[w])}")
+
+    def recommend_new_explore(self, indptr, indices, vals, N: int, beta: float, seed, features, n_sweeps: int,
+                              exclude_seen: bool, filters=None):
+        """`recommend_explore` for rows outside the fit (host CSR, rows sorted): fold in, whiten the same rows, rank."""
+        Z = self._compose_for(features)
+        B = indptr.size - 1
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        rows = self._table_rows(B, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
+
+        def table_rows(b0, nb):
+            _, Uc, bc, seen_ptr, seen_idx = rows(b0, nb)
+            return Uc, bc, seen_ptr, seen_idx
+        return self._explore_chunks(B, N, beta, self._thompson_eps(B, seed), rows, table_rows,
+                                    lambda b0, nb: (ptr_d[b0: b0 + nb + 1], idx_d, None), self._item_side(Z),
+                                    self.allow_bitmap(filters, self.n), lambda w: f"row {w}")

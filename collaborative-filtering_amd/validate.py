@@ -155,6 +155,28 @@ def group_aggregate(aggregate) -> str:
     return aggregate
 
 
+EXPLORE_MODES = ("ucb", "thompson")
+
+
+def explore_args(beta, mode, seed, new_items=None):
+    """(beta float, seed int or None) of `ALS.recommend_explore`: beta a finite real of either sign, mode one of
+    EXPLORE_MODES, seed a non-negative integer - required for "thompson" (the draw is the caller's to reproduce),
+    not accepted for "ucb" (nothing is drawn).  The returned seed is None exactly for "ucb"."""
+    if new_items is not None:
+        raise ValueError("new_items is not supported by recommend_explore")
+    if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not np.isfinite(beta):
+        raise ValueError(f"beta must be a finite number, got {beta!r}")
+    if not isinstance(mode, str) or mode not in EXPLORE_MODES:
+        raise ValueError(f"mode must be one of {EXPLORE_MODES}, got {mode!r}")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0):
+        raise ValueError(f"seed must be a non-negative integer, got {seed!r}")
+    if mode == "thompson" and seed is None:
+        raise ValueError('mode="thompson" needs a seed')
+    if mode == "ucb" and seed is not None:
+        raise ValueError('seed is only used with mode="thompson"')
+    return float(beta), (None if seed is None else int(seed))
+
+
 def id_pairs(users, items, m: int, n: int):
     u, i = _ids(users, "user"), _ids(items, "item")
     if u.shape != i.shape:

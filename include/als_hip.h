@@ -753,6 +753,44 @@ int als_group_topk(int k, int ld, int64_t ngroups, const int64_t* g_ptr, const i
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Uncertainty-aware top-N.  For a row of ratings with items S, A = Z_S^T Z_S +
+ * (lambda_u + 1e-10) I is als_fold_in's / als_explain's ridge system, L its lower Cholesky factor (columns in their
+ * natural order), and the leverage z_i^T A^-1 z_i = |L^-1 z_i|^2 of als_explain is, up to the noise variance, the
+ * posterior variance of the latent score of item i.
+ *
+ * als_row_whitener: W_out [nrows][ld][ld] (fp32, row-major) = float32(L^-1) of every work row w < nrows - CSR row
+ *   rows[w], or row w when rows == NULL (indptr / indices as als_explain; no ratings are read, any row length).  W
+ *   is lower triangular: the upper triangle and the padding rows / columns k .. ld-1 are written 0.  fp64 Gram on
+ *   the matrix cores, Cholesky and the inversion (forward substitution on the identity) in fp64, rounded once.  A
+ *   row without ratings gets I / sqrt(lambda_u + 1e-10).  Sizes and status as als_fold_in (status: max(status,
+ *   w + 1), the WORK row); nrows == 0 is a no-op.
+ *
+ * als_explore_topk: als_recommend_topk_masked with every item i of batch row b (user users[b]) keyed by
+ *   key(i) = base(i) + beta * sqrt(lev(i)),   lev(i) = |W_b z_i|^2   (W [nusers][ld][ld], indexed by BATCH ROW),
+ *   base(i) bitwise the fp32 value als_predict_dense writes at (users[b], i); lev(i) is formed in fp32 on the matrix
+ *   cores over the lower 16 x 16 blocks of W_b and depends on (W_b, z_i) alone - not on the slice, the position in the
+ *   batch or the neighbouring items; the key is sqrt, product and sum in fp32, each correctly rounded, never
+ *   contracted: top_val == base + beta * sqrtf(top_lev) evaluated in float32.  beta: finite, either sign; beta == 0
+ *   gives als_recommend_topk_masked's lists for finite leverages.
+ *   Candidates: the items allowed (allow == NULL: all), not in the user's seen row (CSR by USER ID), whose base and
+ *   key are not NaN.  top_val [nusers][topn] = the keys, top_idx, top_cnt, the order (key descending, item
+ *   ascending), ties, unused slots (-inf / -1) and the slice independence as als_recommend_topk; top_lev
+ *   [nusers][topn] = lev of every returned item (recomputed by the same instruction chain), 0 in unused slots.
+ *   nslices / workspace: as als_recommend_topk, als_explore_workspace_bytes(k, nusers, n, topn, nslices) bytes.
+ *   One wave serves one batch row; as many rows per workgroup as their W images leave room in the LDS share one
+ *   staged chunk of Z (8 at k <= 80 ... 2 at k = 160).
+ * ------------------------------------------------------------------------- */
+int als_row_whitener(int k, int ld, int64_t nrows, const int64_t* indptr, const int32_t* indices,
+                     const int32_t* rows, int64_t n, const float* Z, float lambda_u, float* W_out,
+                     int32_t* status, void* stream);
+size_t als_explore_workspace_bytes(int k, int64_t nusers, int64_t n, int topn, int nslices);
+int als_explore_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                     const float* Z, const float* b_u, const float* b_i, const double* mu, const float* W,
+                     float beta, const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                     int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt,
+                     float* top_lev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
