@@ -26,7 +26,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_fold_in", "als_fold_in_items", "als_explain", "als_mmr_rerank", "als_list_diversity",
            "als_row_inv_norms", "als_similar_workspace_bytes", "als_similar_topk",
            "als_audience_workspace_bytes", "als_audience_topk", "als_group_workspace_bytes", "als_group_topk",
-           "als_row_whitener", "als_explore_workspace_bytes", "als_explore_topk")
+           "als_row_whitener", "als_explore_workspace_bytes", "als_explore_topk",
+           "als_category_profile", "als_calibrated_rerank", "als_list_miscalibration")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -197,7 +198,11 @@ def load():
     lib.als_explore_workspace_bytes.argtypes = [C.c_int, _i64, _i64, C.c_int, C.c_int]
     lib.als_explore_topk.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp,
                                      _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
-    lib.als_graph_classify.argtypes = [_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.als_category_profile.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]
+    lib.als_calibrated_rerank.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _f32, _f32,
+                                          C.c_int, _vp, _vp, _vp, _vp, _vp]
+    lib.als_list_miscalibration.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _f32, _vp, _vp]
+    lib.als_graph_classify.argtypes =[_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]
     lib.als_host_coo_to_sides.argtypes = [_i64, _i64, _i64] + [_vp] * 9

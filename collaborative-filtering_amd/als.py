@@ -428,6 +428,125 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.list_diversity(torch.from_numpy(lists).to(self._eng.dev), features, new_items)
 
+    # ---------------------------------------------------------- calibration
+    def recommend_calibrated(self, users=None, N: int = 10, *, categories, calibration: float = 0.5,
+                             pool: Optional[int] = None, target=None, smoothing: float = 0.01,
+                             features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                             new_items: Optional[FoldedItems] = None, items=None, filter_items=None,
+                             return_miscalibration: bool = False):
+        """Calibrated top-N (Steck, RecSys 2018): a list whose categories follow the proportions of the user's
+        history, chosen greedily from each user's `pool` best items.  Returns (items int64 [B, N], scores float64
+        [B, N]) in pick order, unused slots -1 / -inf; with `return_miscalibration` also float64 [B], the KL
+        divergence below of every returned list.
+
+        `categories`: a real array [n, ncat <= 64], finite and >= 0 - a multi-hot genre matrix or weights; with
+        `new_items` it has n + B rows.  Row i divided by its sum is p(c | i); an all-zero row is an item without a
+        category, which is neutral.  The target p(c | u) of a user is the mean of p(c | i) over the categorised items
+        of the user's ratings in the last fit (`category_profile`), independent of `exclude_seen`; `target` - a real
+        array [B, ncat], rows >= 0, normalised the same way - replaces it (e.g. for rating- or recency-weighted
+        profiles).  A user with an all-zero target gets `recommend`'s list.
+
+        The pool is `recommend(users, pool, ...)` as in `recommend_diverse`, with that method's relevance rel_j.  With
+        lambda = `calibration` in [0, 1] and alpha = `smoothing` in (0, 1), in fp32: the list so far has q(c) = the
+        mean of p(c | i) over its categorised items (0 without one), and step t = 0 .. N-1 picks, among the pool
+        entries not yet chosen, the one maximising
+
+          (1 - lambda) rel_j - lambda KL(p || (1 - alpha) q_{+j} + alpha p),    q_{+j}: q with j added,
+
+        ties to the lower pool position.  The scores returned are the pool's (copied); min(N, M) slots are filled.
+        `calibration=0` returns `recommend(users, N, ...)` bit for bit.  The pool never leaves the device: one kernel
+        forms the profiles (als_category_profile), one gathers the pool's category rows and runs the greedy selection
+        (als_calibrated_rerank)."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        N = validate.top_count(N, "N")
+        lam, pool, alpha = validate.calibration_args(calibration, N, pool, smoothing)
+        u = validate.user_ids(users, self.U.shape[0])
+        n_total = self.V.shape[0] + (new_items.n_items if new_items is not None else 0)
+        table = validate.category_table(categories, n_total)
+        ncat = np.shape(categories)[1]
+        tgt = None if target is None else validate.target_rows(target, u.size, ncat)
+        filters = validate.item_filters(items, filter_items, n_total)
+        if u.size == 0:
+            out = (np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64), np.empty(0, dtype=np.float64))
+        else:
+            with _on(self._eng.dev):
+                out = self._eng.recommend_calibrated(self._dev_i32(u), N, pool, lam, alpha, table, ncat, tgt, features,
+                                                     exclude_seen, new_items, filters, return_miscalibration)
+        return out if return_miscalibration else out[:2]
+
+    def recommend_new_calibrated(self, R_new, N: int = 10, *, categories, calibration: float = 0.5,
+                                 pool: Optional[int] = None, target=None, smoothing: float = 0.01,
+                                 features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                                 exclude_seen: bool = True, items=None, filter_items=None,
+                                 return_miscalibration: bool = False):
+        """`recommend_calibrated` for users outside the fit: the pool is `recommend_new(R_new, pool, ...)` and the
+        target of row b is the profile of the items rated in row b of `R_new`; everything else as there."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        lam, pool, alpha = validate.calibration_args(calibration, N, pool, smoothing)
+        T = validate.sweeps(n_sweeps)
+        n = self.V.shape[0]
+        indptr, indices, vals = fold_in_csr(R_new, n)
+        table = validate.category_table(categories, n)
+        ncat = np.shape(categories)[1]
+        tgt = None if target is None else validate.target_rows(target, indptr.size - 1, ncat)
+        filters = validate.item_filters(items, filter_items, n)
+        if indptr.size == 1:
+            out = (np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64), np.empty(0, dtype=np.float64))
+        else:
+            with _on(self._eng.dev):
+                out = self._eng.recommend_new_calibrated(indptr, indices, vals, N, pool, lam, alpha, table, ncat, tgt,
+                                                         features, T, exclude_seen, filters, return_miscalibration)
+        return out if return_miscalibration else out[:2]
+
+    def category_profile(self, users=None, *, categories) -> np.ndarray:
+        """The category profiles p(c | u) that `recommend_calibrated` aims at: float64 [B, ncat], the mean of the
+        normalised rows of `categories` ([n, ncat]) over the categorised items of the user's ratings in the last fit,
+        summed in float64 and rounded once to float32; all zero for a user without such an item
+        (als_category_profile).  `users` as in `recommend`."""
+        validate.fitted(self)
+        u = validate.user_ids(users, self.U.shape[0])
+        table = validate.category_table(categories, self.V.shape[0])
+        ncat = np.shape(categories)[1]
+        if u.size == 0:
+            return np.empty((0, ncat), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.category_profile(self._dev_i32(u), table, ncat)
+
+    def list_miscalibration(self, item_lists, *, categories, users=None, target=None,
+                            smoothing: float = 0.01) -> np.ndarray:
+        """Miscalibration of id lists: float64 [B], KL(p || (1 - alpha) q + alpha p) in fp32 with q the mean of
+        p(c | i) over the categorised items of a list (0 without one) and alpha = `smoothing` - 0 for a perfectly
+        proportional list, and for an all-zero p.
+
+        `item_lists`: an integer array [B, L <= 128]; a list ends at its first -1.  Exactly one of `users` (list b is
+        measured against `category_profile(users)[b]`) and `target` (a real array [B, ncat] as in
+        `recommend_calibrated`) is given.  On the lists `recommend_calibrated` returns, the value is bitwise the one
+        its kernel computes for them (als_list_miscalibration)."""
+        validate.fitted(self)
+        n = self.V.shape[0]
+        lists = validate.item_lists(item_lists, n)
+        table = validate.category_table(categories, n)
+        ncat = np.shape(categories)[1]
+        alpha = validate.smoothing_arg(smoothing)
+        if (users is None) == (target is None):
+            raise ValueError("list_miscalibration needs exactly one of users and target")
+        B = lists.shape[0]
+        u = tgt = None
+        if users is not None:
+            u = validate.user_ids(users, self.U.shape[0])
+            if u.size != B:
+                raise ValueError(f"users names {u.size} users for {B} lists")
+        else:
+            tgt = validate.target_rows(target, B, ncat)
+        if B == 0:
+            return np.empty(0, dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.list_miscalibration(torch.from_numpy(lists).to(self._eng.dev), table, ncat, alpha,
+                                                 None if u is None else self._dev_i32(u), tgt)
+
     # ----------------------------------------------------------- neighbours
     def similar_items(self, items=None, N: int = 10, *, features: Optional[Dict[str, np.ndarray]] = None,
                       allow_items=None, filter_items=None):

@@ -536,3 +536,36 @@ class HipBackend:
                                               _p(top_val), _p(top_idx), _p(top_cnt), _p(top_lev),
                                               _p(self._exp_ws) if need > 0 else None, need, self._stream()),
                     "als_explore_topk")
+
+    # -- K17 -------------------------------------------------------------------
+    def category_profile(self, *, ncat, indptr, indices, rows, n, C, P_out):
+        """P_out fp32 [B, ldc] = the mean category row of the categorised items of every batch row's CSR row (batch
+        row b reads row rows[b], or row b when `rows` is None; the sum in fp64), all zero without one:
+        als_category_profile.  C fp32 [n, ldc] is the category table (validate.category_table)."""
+        B = indptr.numel() - 1 if rows is None else rows.numel()
+        ldc = C.shape[1]
+        assert C.is_contiguous() and C.shape[0] == n and P_out.is_contiguous() and P_out.shape == (B, ldc)
+        self._check(self.lib.als_category_profile(ncat, ldc, B, _p(rows), _p(indptr), _p(indices), int(n), _p(C),
+                                                  _p(P_out), self._stream()), "als_category_profile")
+
+    def calibrated_rerank(self, *, ncat, n, C, P, cand_val, cand_idx, lam, alpha, topn, top_val, top_idx, top_cnt,
+                          top_kl=None):
+        """Greedy calibrated re-ranking of the pools cand_val fp32 / cand_idx int32 [B, pool] (the outputs of
+        `recommend_topk` with topn = pool) towards the targets P fp32 [B, ldc] over the category table C [n, ldc]:
+        top_val / top_idx [B, topn], top_cnt [B], top_kl fp32 [B] or None: als_calibrated_rerank."""
+        B, pool = cand_idx.shape
+        ldc = C.shape[1]
+        assert cand_val.shape == (B, pool) and cand_val.is_contiguous() and cand_idx.is_contiguous()
+        assert C.is_contiguous() and C.shape[0] == n and P.is_contiguous() and P.shape == (B, ldc)
+        self._check(self.lib.als_calibrated_rerank(ncat, ldc, B, n, _p(C), _p(P), pool, _p(cand_val), _p(cand_idx),
+                                                   float(lam), float(alpha), topn, _p(top_val), _p(top_idx),
+                                                   _p(top_cnt), _p(top_kl), self._stream()), "als_calibrated_rerank")
+
+    def list_miscalibration(self, *, ncat, n, C, P, idx, alpha, kl):
+        """kl fp32 [B] = the smoothed KL divergence of the targets P [B, ldc] from the category distribution of the id
+        lists idx int32 [B, L] (-1 padded): als_list_miscalibration."""
+        B, L = idx.shape
+        ldc = C.shape[1]
+        assert idx.is_contiguous() and C.is_contiguous() and C.shape[0] == n and P.is_contiguous() and P.shape == (B, ldc)
+        self._check(self.lib.als_list_miscalibration(ncat, ldc, B, n, _p(C), _p(P), L, _p(idx), float(alpha), _p(kl),
+                                                     self._stream()), "als_list_miscalibration")

@@ -218,6 +218,39 @@ def explore_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, betas: Seque
     return {"users": int(users.size), "betas": out, **extra}
 
 
+def calibration_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, categories,
+                     calibrations: Sequence[float] = (0.0, 0.5), pool: Optional[int] = None, smoothing: float = 0.01,
+                     min_rating: Optional[float] = None, features: Optional[Dict[str, np.ndarray]] = None, items=None,
+                     filter_items=None) -> Dict[str, Any]:
+    """What calibration costs and buys: `model.recommend_calibrated(users, K, categories=categories, calibration=c)`
+    on held-out (user, item) pairs for every c of `calibrations` - {"users", "profiled_users", "calibrations":
+    [{"calibration", "recall@K", "ndcg@K", "miscalibration@K"}, ...]} (plus "filtered_out" with `items` /
+    `filter_items`).
+
+    users, rel(u), recall@K and NDCG@K are `ranking_at_k`'s (same arguments, same pairs left out), so the entry of
+    calibration 0 equals `ranking_at_k`.  miscalibration@K is the mean, over the "profiled_users" - those whose
+    category profile (`ALS.category_profile`) is not all zero -, of the KL divergence of the user's list from the
+    profile as the re-ranking kernel itself reports it (NaN when there is no such user); it falls as the calibration
+    rises."""
+    calibrations = [float(c) for c in calibrations]
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
+    nan = float("nan")
+    if users.size == 0:
+        return {"users": 0, "profiled_users": 0,
+                "calibrations": [{"calibration": c, "recall@K": nan, "ndcg@K": nan, "miscalibration@K": nan}
+                                 for c in calibrations], **extra}
+    known = (model.category_profile(users, categories=categories) > 0).any(axis=1)
+    out = []
+    for c in calibrations:
+        top, _, kl = model.recommend_calibrated(users, K, categories=categories, calibration=c, pool=pool,
+                                                smoothing=smoothing, features=features, return_miscalibration=True,
+                                                **kw)
+        m = _ranking_metrics(top, ub, cols, model.V.shape[0], K)
+        out.append({"calibration": c, "recall@K": m["recall@K"], "ndcg@K": m["ndcg@K"],
+                    "miscalibration@K": float(np.mean(kl[known])) if known.any() else nan})
+    return {"users": int(users.size), "profiled_users": int(known.sum()), "calibrations": out, **extra}
+
+
 def audience_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
                   features: Optional[Dict[str, np.ndarray]] = None, users=None, filter_users=None) -> Dict[str, Any]:
     """recall@K and NDCG@K of `model.recommend_users` on held-out (user, item) pairs: `ranking_at_k` per ITEM - is

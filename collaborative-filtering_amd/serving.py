@@ -1,6 +1,6 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
-`recommend_group` and `recommend*_explore`.
+`recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile` and `list_miscalibration`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -521,28 +521,35 @@ class _Serving:
                                  allow=self.allow_bitmap(filters, side["n"]))
 
     # ------------------------------------------------------------ diversity
-    def _rerank_chunks(self, B: int, N: int, pool: int, lam: float, rows, items: dict, allow, with_ild: bool):
-        """The pool - `_topk_chunks` with N = pool, kept on the device - re-ranked by als_mmr_rerank against the Z it
-        was scored with, in REC_BATCH chunks; only the [B, N] results come back: (items int64, scores float64, and
-        ild float64 [B] or None)."""
+    def _pool_chunks(self, B: int, N: int, pool: int, rows, items: dict, allow, with_stat: bool, rerank):
+        """The pool - `_topk_chunks` with N = pool, kept on the device - re-ranked in REC_BATCH chunks by
+        rerank(b0, nb, cand_val, cand_idx, top_val, top_idx, top_cnt, stat): the chunk's pool rows, its [nb, N] outputs
+        and `stat`, a fp32 [nb] per-list statistic the kernel writes (None without `with_stat`).  Only the [B, N]
+        results come back: (items int64, scores float64, and the statistic float64 [B] or None)."""
         pool_val, pool_idx = self._topk_chunks(B, pool, rows, items, on_device=True, allow=allow)
         out_items = np.empty((B, N), dtype=np.int64)
         out_scores = np.empty((B, N), dtype=np.float64)
-        out_ild = np.empty(B, dtype=np.float64) if with_ild else None
+        out_stat = np.empty(B, dtype=np.float64) if with_stat else None
         for b0 in range(0, B, self.REC_BATCH):
             nb = min(self.REC_BATCH, B - b0)
             tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
             ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
             tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            ild = torch.empty(nb, dtype=torch.float32, device=self.dev) if with_ild else None
-            self.be.mmr_rerank(k=items["k"], ld=items["ld"], n=items["n"], Z=items["Z"],
-                               cand_val=pool_val[b0: b0 + nb], cand_idx=pool_idx[b0: b0 + nb], lam=lam, topn=N,
-                               top_val=tv, top_idx=ti, top_cnt=tc, top_ild=ild)
+            stat = torch.empty(nb, dtype=torch.float32, device=self.dev) if with_stat else None
+            rerank(b0, nb, pool_val[b0: b0 + nb], pool_idx[b0: b0 + nb], tv, ti, tc, stat)
             out_items[b0: b0 + nb] = ti.cpu().numpy()
             out_scores[b0: b0 + nb] = tv.cpu().numpy()
-            if with_ild:
-                out_ild[b0: b0 + nb] = ild.cpu().numpy()
-        return out_items, out_scores, out_ild
+            if with_stat:
+                out_stat[b0: b0 + nb] = stat.cpu().numpy()
+        return out_items, out_scores, out_stat
+
+    def _rerank_chunks(self, B: int, N: int, pool: int, lam: float, rows, items: dict, allow, with_ild: bool):
+        """`_pool_chunks` with als_mmr_rerank against the Z the pool was scored with: (items int64, scores float64,
+        and ild float64 [B] or None)."""
+        def rerank(b0, nb, cand_val, cand_idx, tv, ti, tc, ild):
+            self.be.mmr_rerank(k=items["k"], ld=items["ld"], n=items["n"], Z=items["Z"], cand_val=cand_val,
+                               cand_idx=cand_idx, lam=lam, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_ild=ild)
+        return self._pool_chunks(B, N, pool, rows, items, allow, with_ild, rerank)
 
     def recommend_diverse(self, users_t: torch.Tensor, N: int, pool: int, lam: float, features, exclude_seen: bool,
                           folded: Optional["FoldedItems"] = None, filters=None, with_ild: bool = False):
@@ -576,6 +583,98 @@ class _Serving:
             self.be.list_diversity(k=side["k"], ld=side["ld"], n=side["n"], Z=side["Z"], idx=lists[b0: b0 + nb],
                                    ild=ild)
             out[b0: b0 + nb] = ild.cpu().numpy()
+        return out
+
+    # ---------------------------------------------------------- calibration
+    def _fitted_history(self, users_t: torch.Tensor):
+        """History source of the calibration drivers for users of the fit: hist(b0, nb) -> (indptr, indices, rows)
+        of als_category_profile - the training CSR, batch row b = its row users_t[b]."""
+        ptr, idx, _ = self._csr_dev(self.csr.indptr, self.csr.indices, self.csr.vals)
+        return lambda b0, nb: (ptr, idx, users_t[b0: b0 + nb])
+
+    @staticmethod
+    def _table_history(ptr_d: torch.Tensor, idx_d: torch.Tensor):
+        """History source for a CSR made for the call (batch row b = its row b): a view of the row pointers, the
+        offsets stay absolute."""
+        return lambda b0, nb: (ptr_d[b0: b0 + nb + 1], idx_d, None)
+
+    def _profile_chunk(self, C: torch.Tensor, ncat: int, hist, b0: int, nb: int) -> torch.Tensor:
+        """als_category_profile of the batch rows [b0, b0 + nb): fp32 [nb, ldc] on the device."""
+        P = torch.empty(nb, C.shape[1], dtype=torch.float32, device=self.dev)
+        indptr, indices, rows = hist(b0, nb)
+        self.be.category_profile(ncat=ncat, indptr=indptr, indices=indices, rows=rows, n=C.shape[0], C=C, P_out=P)
+        return P
+
+    def _calibrate_chunks(self, B: int, N: int, pool: int, lam: float, alpha: float, rows, items: dict, allow,
+                          table: np.ndarray, ncat: int, hist, target: Optional[np.ndarray], with_kl: bool):
+        """`_pool_chunks` with als_calibrated_rerank over the category table `table` (validate.category_table of the
+        catalogue scored, uploaded once): per chunk the targets are the rows of `target` (validate.target_rows) or,
+        without one, the profiles of the histories `hist` (als_category_profile).  Returns (items int64, scores
+        float64, and the lists' miscalibration float64 [B] or None)."""
+        C = torch.from_numpy(table).to(self.dev)
+        T = None if target is None else torch.from_numpy(target).to(self.dev)
+
+        def rerank(b0, nb, cand_val, cand_idx, tv, ti, tc, kl):
+            P = T[b0: b0 + nb] if T is not None else self._profile_chunk(C, ncat, hist, b0, nb)
+            self.be.calibrated_rerank(ncat=ncat, n=items["n"], C=C, P=P, cand_val=cand_val, cand_idx=cand_idx,
+                                      lam=lam, alpha=alpha, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_kl=kl)
+        return self._pool_chunks(B, N, pool, rows, items, allow, with_kl, rerank)
+
+    def recommend_calibrated(self, users_t: torch.Tensor, N: int, pool: int, lam: float, alpha: float,
+                             table: np.ndarray, ncat: int, target, features, exclude_seen: bool,
+                             folded: Optional["FoldedItems"] = None, filters=None, with_kl: bool = False):
+        """`recommend(N=pool)` (or `recommend_with_items` with `folded`) on the device, then the calibrated re-rank
+        towards the profile of the user's training row (or `target`)."""
+        if folded is None:
+            side = self._item_side(self._compose_for(features))
+            rows = self._fitted_rows(users_t, exclude_seen)
+        else:
+            side = self._joint_side(features, folded)
+            rows = self._joint_rows(users_t, exclude_seen, folded)
+        return self._calibrate_chunks(users_t.numel(), N, pool, lam, alpha, rows, side,
+                                      self.allow_bitmap(filters, side["n"]), table, ncat,
+                                      self._fitted_history(users_t), target, with_kl)
+
+    def recommend_new_calibrated(self, indptr, indices, vals, N: int, pool: int, lam: float, alpha: float,
+                                 table: np.ndarray, ncat: int, target, features, n_sweeps: int, exclude_seen: bool,
+                                 filters=None, with_kl: bool = False):
+        """`recommend_new(N=pool)` on the device, then the calibrated re-rank towards the profile of the given
+        ratings (or `target`)."""
+        Z = self._compose_for(features)
+        B = indptr.size - 1
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        rows = self._table_rows(B, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
+        return self._calibrate_chunks(B, N, pool, lam, alpha, rows, self._item_side(Z),
+                                      self.allow_bitmap(filters, self.n), table, ncat,
+                                      self._table_history(ptr_d, idx_d), target, with_kl)
+
+    def category_profile(self, users_t: torch.Tensor, table: np.ndarray, ncat: int) -> np.ndarray:
+        """float64 [B, ncat]: the category profiles of the training rows of `users_t` (int32, device),
+        als_category_profile in REC_BATCH chunks."""
+        C = torch.from_numpy(table).to(self.dev)
+        hist = self._fitted_history(users_t)
+        B = users_t.numel()
+        out = np.empty((B, ncat), dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            out[b0: b0 + nb] = self._profile_chunk(C, ncat, hist, b0, nb)[:, :ncat].cpu().numpy()
+        return out
+
+    def list_miscalibration(self, lists: torch.Tensor, table: np.ndarray, ncat: int, alpha: float,
+                            users_t: Optional[torch.Tensor], target: Optional[np.ndarray]) -> np.ndarray:
+        """Miscalibration float64 [B] of the id lists `lists` (int32 [B, L], -1 padded, device) against the profiles
+        of the users `users_t` or the rows of `target`: als_list_miscalibration in REC_BATCH chunks."""
+        C = torch.from_numpy(table).to(self.dev)
+        T = None if target is None else torch.from_numpy(target).to(self.dev)
+        hist = None if users_t is None else self._fitted_history(users_t)
+        B = lists.shape[0]
+        out = np.empty(B, dtype=np.float64)
+        for b0 in range(0, B, self.REC_BATCH):
+            nb = min(self.REC_BATCH, B - b0)
+            P = T[b0: b0 + nb] if T is not None else self._profile_chunk(C, ncat, hist, b0, nb)
+            kl = torch.empty(nb, dtype=torch.float32, device=self.dev)
+            self.be.list_miscalibration(ncat=ncat, n=C.shape[0], C=C, P=P, idx=lists[b0: b0 + nb], alpha=alpha, kl=kl)
+            out[b0: b0 + nb] = kl.cpu().numpy()
         return out
 
     # ----------------------------------------------------------- neighbours

@@ -61,6 +61,76 @@ def diversity_args(diversity, N: int, pool):
     return float(diversity), int(pool)
 
 
+CALIBRATE_MAX_CATEGORIES = 64      # one lane per category in als_calibrated_rerank
+TARGET_MIN = 2.0 ** -100           # a target entry below this counts as 0 (the hardware log2 takes no subnormals)
+
+
+def _distribution_rows(a: np.ndarray, min_entry: float = 0.0) -> np.ndarray:
+    """Non-negative rows [rows, ncat] -> fp32 [rows, ldc]: every row divided by its sum in float64 (an all-zero row
+    stays zero) and rounded once, ldc = ncat rounded up to a multiple of 16, padding columns zero; entries that end
+    up below `min_entry` are set to 0."""
+    a = a.astype(np.float64)
+    s = a.sum(axis=1, keepdims=True)
+    out = np.zeros((a.shape[0], 16 * ((a.shape[1] + 15) // 16)), dtype=np.float32)
+    with np.errstate(over="ignore"):
+        out[:, : a.shape[1]] = np.divide(a, s, out=np.zeros_like(a), where=s > 0)
+    if min_entry:
+        out[out < min_entry] = 0.0
+    return out
+
+
+def _real_2d(x, name: str) -> np.ndarray:
+    a = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+    if a.ndim != 2 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"{name} must be a real 2-D array")
+    return a
+
+
+def category_table(categories, n_total: int) -> np.ndarray:
+    """The category table of `recommend_calibrated`: `categories` a real array [n_total, 1 .. 64], finite and >= 0
+    (multi-hot or weighted; an all-zero row is an item without a category) -> the rows as distributions p(c | i),
+    fp32 [n_total, ldc] (`_distribution_rows`)."""
+    a = _real_2d(categories, "categories")
+    if a.shape[0] != n_total:
+        raise ValueError(f"categories has {a.shape[0]} rows. Expected number of rows: {n_total}.")
+    if not 1 <= a.shape[1] <= CALIBRATE_MAX_CATEGORIES:
+        raise ValueError(f"categories must have 1 to {CALIBRATE_MAX_CATEGORIES} columns, got {a.shape[1]}")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("categories must be finite and non-negative")
+    return _distribution_rows(a)
+
+
+def calibration_args(calibration, N: int, pool, smoothing):
+    """(lambda, pool, alpha) of `recommend_calibrated`: `calibration` a real number in [0, 1]; `pool` as
+    `diversity_args` (None = min(128, 4 N), else an integer with N <= pool <= 128); `smoothing` a real number in
+    (0, 1)."""
+    if (isinstance(calibration, (bool, np.bool_)) or not isinstance(calibration, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(calibration) <= 1.0):                     # NaN fails the comparison
+        raise ValueError(f"calibration must be a real number in [0, 1], got {calibration!r}")
+    _, pool = diversity_args(0.0, N, pool)
+    return float(calibration), pool, smoothing_arg(smoothing)
+
+
+def smoothing_arg(smoothing) -> float:
+    if (isinstance(smoothing, (bool, np.bool_)) or not isinstance(smoothing, (int, float, np.integer, np.floating))
+            or not 0.0 < float(np.float32(smoothing)) < 1.0):             # as the kernel sees it
+        raise ValueError(f"smoothing must be a real number in (0, 1), got {smoothing!r}")
+    return float(smoothing)
+
+
+def target_rows(target, B: int, ncat: int) -> np.ndarray:
+    """Explicit targets of `recommend_calibrated` / `list_miscalibration`: a real array [B, ncat], finite and >= 0
+    -> the rows as distributions, fp32 [B, ldc], normalised like the category table; entries below TARGET_MIN
+    count as 0."""
+    a = _real_2d(target, "target")
+    if a.shape != (B, ncat):
+        raise ValueError(f"target has shape {a.shape}; expected ({B}, {ncat}) (one row per user, one column per "
+                         "category)")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("target must be finite and non-negative")
+    return _distribution_rows(a, TARGET_MIN)
+
+
 def item_lists(lists, n_total: int) -> np.ndarray:
     """Id lists of `list_diversity`: an integer array [B, L], 1 <= L <= 128, entries -1 (padding) or item ids in
     [0, n_total) -> int32 [B, L]."""

@@ -791,6 +791,48 @@ int als_explore_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_
                      float* top_lev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Calibrated top-N (Steck, RecSys 2018): a list whose categories follow the proportions of a
+ * target distribution.
+ *
+ * Category table C [n][ldc], fp32: ncat (1 .. 64) real columns, ldc = ncat rounded up to a multiple of 16, padding
+ *   columns zero.  Row i is p(c | i): non-negative, summing to 1, or all zero (an item without a category);
+ *   has_i = 1 when any entry of row i is > 0.
+ * Target P [nrows][ldc], fp32, same shape rules: row b is p(c | b), or all zero when nothing is known of the row.
+ *   P entries and alpha * P entries are expected to be zero or normal fp32 numbers (the hardware log2 does not take
+ *   subnormals).
+ *
+ * als_category_profile: P_out[b] = (sum_{i in H_b} C_i) / #{i in H_b : has_i}, H_b the CSR row rows[b] (rows == NULL:
+ *   row b) of indptr (int64) / indices (int32): the sum in fp64 in CSR order, rounded once to fp32; all zero when
+ *   the count is 0.  An index outside [0, n) is skipped.  rows may name a row more than once.
+ *
+ * als_calibrated_rerank: per row a pool cand_idx / cand_val [nrows][pool] in als_recommend_topk's output form (as
+ *   als_mmr_rerank: a list ends at the first -1 or at the first id outside [0, n), never dereferenced, or at its full
+ *   width; rel_j is als_mmr_rerank's min-max relevance).  State: S_c = fp32 sum of the chosen items' rows in pick
+ *   order, cnt = chosen items with has = 1.  For an open candidate j, in fp32:
+ *     cnt_j = cnt + has_j,  q_c = (S_c + C_jc) / cnt_j (0 when cnt_j = 0),  q~_c = (1 - alpha) q_c + alpha p_c,
+ *     KL_j = ln 2 * sum_{c : p_c > 0} p_c (log2 p_c - log2 q~_c)   (c ascending, v_log_f32),
+ *     obj_j = (1 - lambda) rel_j - lambda KL_j;
+ *   step t = 0 .. topn-1 picks the open candidate with the largest objective, ties to the lower pool position.
+ *   top_idx / top_val [nrows][topn]: the picks in pick order with their cand_val (copied), unused slots -1 / -inf;
+ *   top_cnt [nrows] = min(topn, entries of the pool); top_kl [nrows] (nullable): the KL of the final state (q from S
+ *   and cnt alone).  lambda = 0, or an all-zero target row at any lambda, returns the first topn pool entries of a
+ *   pool ordered by score; items without a category leave q unchanged.
+ * als_list_miscalibration: kl [nrows] = the KL of the state reached by adding the items of the list idx [nrows][len]
+ *   in list order; on a list als_calibrated_rerank returned it is bitwise that call's top_kl.
+ *
+ * ncat outside 1 .. 64 or ldc != 16 ceil(ncat / 16): ALS_E_BADK.  1 <= pool, len <= ALS_TOPK_MAX, 1 <= topn <= pool,
+ * 0 <= lambda <= 1, 0 < alpha < 1, n < 2^31 (ALS_E_BADARG otherwise, as for a NULL required pointer); asynchronous
+ * on the stream, no workspace; nrows == 0 is a no-op.
+ * ------------------------------------------------------------------------- */
+int als_category_profile(int ncat, int ldc, int64_t nrows, const int32_t* rows, const int64_t* indptr,
+                         const int32_t* indices, int64_t n, const float* C, float* P_out, void* stream);
+int als_calibrated_rerank(int ncat, int ldc, int64_t nrows, int64_t n, const float* C, const float* P, int pool,
+                          const float* cand_val, const int32_t* cand_idx, float lambda, float alpha, int topn,
+                          float* top_val, int32_t* top_idx, int32_t* top_cnt, float* top_kl, void* stream);
+int als_list_miscalibration(int ncat, int ldc, int64_t nrows, int64_t n, const float* C, const float* P, int len,
+                            const int32_t* idx, float alpha, float* kl, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
