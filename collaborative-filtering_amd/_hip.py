@@ -27,7 +27,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_row_inv_norms", "als_similar_workspace_bytes", "als_similar_topk",
            "als_audience_workspace_bytes", "als_audience_topk", "als_group_workspace_bytes", "als_group_topk",
            "als_row_whitener", "als_explore_workspace_bytes", "als_explore_topk",
-           "als_category_profile", "als_calibrated_rerank", "als_list_miscalibration")
+           "als_category_profile", "als_calibrated_rerank", "als_list_miscalibration",
+           "als_recommend_deep_workspace_bytes", "als_recommend_deep")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -173,6 +174,9 @@ def load():
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_recommend_topk_masked.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_recommend_deep_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
+    lib.als_recommend_deep.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_rank_count_workspace_bytes.argtypes = [C.c_int, _i64, _i64, _i64, C.c_int]
     lib.als_rank_count.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                    _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
@@ -212,7 +216,7 @@ def load():
         if name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64", "als_spd_solve_workspace_bytes",
                         "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
                         "als_similar_workspace_bytes", "als_audience_workspace_bytes", "als_group_workspace_bytes",
-                        "als_explore_workspace_bytes"):
+                        "als_explore_workspace_bytes", "als_recommend_deep_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     lib.als_spd_solve_workspace_bytes.restype = C.c_size_t
     lib.als_recommend_workspace_bytes.restype = C.c_size_t
@@ -221,5 +225,6 @@ def load():
     lib.als_audience_workspace_bytes.restype = C.c_size_t
     lib.als_group_workspace_bytes.restype = C.c_size_t
     lib.als_explore_workspace_bytes.restype = C.c_size_t
+    lib.als_recommend_deep_workspace_bytes.restype = C.c_size_t
     _lib = lib
     return lib

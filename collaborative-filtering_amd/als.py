@@ -37,7 +37,7 @@ from . import layout, validate
 from .als_config import ALSConfig
 from .containers import FitCache, _SideDev, _TasksDev, _side_to_dev, _tasks_to_dev  # noqa: F401
 from .engine import EPS, SCALE_FACTOR, W_F64_BELOW, SweepNotResident, _Engine  # noqa: F401
-from .serving import RECOMMEND_MAX_N, Explanation, FoldedItems, _Serving, concat_features  # noqa: F401
+from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, Explanation, FoldedItems, _Serving, concat_features  # noqa: F401
 from .validate import _as_side, _check_csr, _validate_graph  # noqa: F401
 from .validate import fold_in_csr, new_item_features, new_item_graph_csr  # noqa: F401
 from .validate import host_features as _host_features
@@ -347,6 +347,55 @@ class ALS:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen, filters)
+
+    # ----------------------------------------------------------- deep lists
+    def recommend_deep(self, users=None, N: int = 500, *, features: Optional[Dict[str, np.ndarray]] = None,
+                       exclude_seen: bool = True, new_items: Optional[FoldedItems] = None, items=None,
+                       filter_items=None, after=None):
+        """`recommend` for long lists and for paging: the exact top N, 1 <= N <= RECOMMEND_DEEP_MAX_N = 1024, as
+        (items int64 [B, N], scores float64 [B, N]), unused slots -1 / -inf.
+
+        Everything means what it means in `recommend` - scores bitwise those of `predict`, order (score descending,
+        item ascending), NaN scores never candidates, seen items and the allow / block lists applied in the kernel,
+        `new_items` as ids n + b - and for N <= 128 without `after` the result is `recommend`'s, element for element.
+
+        `after` = (after_items [B], after_scores [B]) is a cursor, the last entry of the page the caller already
+        has for each row: the call returns the N best candidates that come strictly after that entry in the order
+        above.  after_items[b] = -1 (the padding of an exhausted list) gives an empty row.  Paging until a row comes
+        back short enumerates the row's candidates once, in order, without a duplicate or a gap, also across equal
+        scores.  The other arguments must stay the same from page to page.
+
+        The catalogue is scored in rounds of 128 keys per item slice; a round that leaves nothing open ends the
+        call, which is the rule (als_recommend_deep).  The result costs 16 bytes of host
+        memory per slot: all users x N = 1024 of a fit with a million users is 16 GB - ask for the users you need."""
+        features = self._check_predict(features)
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        N = validate.deep_topn(N)
+        u = validate.user_ids(users, self.U.shape[0])
+        n_total = self.V.shape[0] + (new_items.n_items if new_items is not None else 0)
+        filters = validate.item_filters(items, filter_items, n_total)
+        after = validate.deep_cursor(after, u.size, n_total)
+        if u.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_deep(self._dev_i32(u), N, features, exclude_seen, new_items, filters, after)
+
+    def recommend_new_deep(self, R_new, N: int = 500, *, features: Optional[Dict[str, np.ndarray]] = None,
+                           n_sweeps: Optional[int] = None, exclude_seen: bool = True, items=None, filter_items=None,
+                           after=None):
+        """`recommend_deep` for users outside the fit: `fold_in(R_new, ...)` as in `recommend_new`, then the contract
+        of `recommend_deep` on the folded factors; `after` holds one cursor per row of R_new."""
+        features = self._check_predict(features)
+        N = validate.deep_topn(N)
+        T = validate.sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        filters = validate.item_filters(items, filter_items, self.V.shape[0])
+        after = validate.deep_cursor(after, indptr.size - 1, self.V.shape[0])
+        if indptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_new_deep(indptr, indices, vals, N, features, T, exclude_seen, filters, after)
 
     # ------------------------------------------------------------ diversity
     def recommend_diverse(self, users=None, N: int = 10, *, diversity: float = 0.3, pool: Optional[int] = None,

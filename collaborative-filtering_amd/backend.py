@@ -50,6 +50,7 @@ class HipBackend:
         self._stats_partials: Optional[torch.Tensor] = None
         self._spd_ws: Optional[torch.Tensor] = None
         self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
+        self._deep_ws: Optional[torch.Tensor] = None       # slice lists, running lists, ceilings of als_recommend_deep
         self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
         self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
         self._aud_ws: Optional[torch.Tensor] = None        # slice lists of als_audience_topk
@@ -339,6 +340,33 @@ class HipBackend:
         self._check(fn(k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr),
                        _p(seen_idx), *allow, topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
                        _p(self._rec_ws) if need > 0 else None, need, self._stream()), what)
+
+    def recommend_deep(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, after_key, topn,
+                       top_val, top_idx, top_cnt, rounds=None):
+        """`recommend_topk_masked` (allow None: every item) for topn up to ALS_TOPK_DEEP_MAX = 1024, optionally below
+        a cursor: als_recommend_deep.  after_key: None, or int64 [B] holding the bits of the 64-bit cursor keys
+        (serving.cursor_keys); rounds: None or an int32 [1] device tensor that receives the scoring rounds that did work.
+        The workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
+        if allow is not None:
+            self._check_bitmap(allow, n)
+        if after_key is not None and (after_key.dtype != torch.int64 or not after_key.is_cuda
+                                      or not after_key.is_contiguous() or after_key.numel() != users.numel()):
+            raise ValueError("after_key must be a contiguous int64 device tensor with one key per batch row")
+        if seen_idx is not None and seen_idx.numel() == 0:
+            seen_ptr = seen_idx = None
+        nsl = self.recommend_slices()
+        need = self.recommend_deep_workspace_bytes(users.numel(), n, topn)
+        if need > 0 and (self._deep_ws is None or self._deep_ws.numel() < need):
+            self._deep_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.als_recommend_deep(
+            k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr), _p(seen_idx),
+            _p(allow), _p(after_key), topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt), _p(rounds),
+            _p(self._deep_ws) if need > 0 else None, need, self._stream()), "als_recommend_deep")
+
+    def recommend_deep_workspace_bytes(self, nusers: int, n: int, topn: int) -> int:
+        """Bytes of workspace a `recommend_deep` call over `nusers` rows takes (als_recommend_deep_workspace_bytes
+        under the slice count in force)."""
+        return int(self.lib.als_recommend_deep_workspace_bytes(nusers, n, topn, self.recommend_slices()))
 
     def rank_count(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score,
                    above, n_cand):

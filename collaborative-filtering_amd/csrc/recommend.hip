@@ -28,6 +28,15 @@
 // catch up on their own: the exclusion walk consumes every entry below the block it is asked about.  The unmasked
 // instantiations contain none of this: they are the code they were before the bitmap existed.
 //
+// Ceilings (als_recommend_deep, recommend_deep.hip; the DEEP instantiations): every (slice, user) has a ceiling key in
+// ceil[slice * nusers + b], and a candidate passes only when its key is BELOW it as well as above the threshold - ~0
+// is no ceiling, 0 closes the slice for the user.  A workgroup none of whose 64 users is open for its slice returns
+// before the first barrier (every wave reads the same 64 ceilings, one per lane, so the decision is the workgroup's),
+// as does every workgroup of a round whose predecessor raised no flag (*go == 0).  The lists always go to the workspace
+// as raw keys, 128 per (slice, user).  The walk itself is untouched, and so is rank_eval.hip's copy: the ceiling is one
+// more term of the candidate test, which k_rank_count does not have.  The instantiations without DEEP contain none of
+// this: their instruction streams are those of the kernel without the parameter.
+//
 // The walk is written a second time in rank_eval.hip (k_rank_count), character for character apart from the RC_ / RK_
 // prefix: fetch / stage, next_chunk / window / after, the cursor set-up, the exclusion walk, the score tiles, the
 // candidate test, the chunk loop.  Only the chunk and slice arithmetic and the score epilogue are one copy
@@ -35,6 +44,7 @@
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
+#include "recommend_deep.hpp"
 #include "topk_common.hpp"
 
 namespace {
@@ -50,14 +60,15 @@ constexpr int RC_NARROW = 128;      // users per workgroup, topn <= 32: 8 waves,
 __device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 
 // CAP keys per user: list [0, L) + survivor buffer [L, CAP)
-template <int KB, int NW, int CAP, bool MASKED>
+template <int KB, int NW, int CAP, bool MASKED, bool DEEP = false>
 __global__ __launch_bounds__(NW * 64)
 void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t n, int64_t slice,
                  const float* __restrict__ U, const float* __restrict__ Z, const float* __restrict__ b_u,
                  const float* __restrict__ b_i, const double* __restrict__ mu_p,
                  const int64_t* __restrict__ seen_ptr, const int32_t* __restrict__ seen_idx, int topn,
                  float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt,
-                 unsigned long long* __restrict__ part, const uint32_t* __restrict__ allow) {
+                 unsigned long long* __restrict__ part, const uint32_t* __restrict__ allow,
+                 const unsigned long long* __restrict__ ceil, const int32_t* __restrict__ go) {
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
     constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
@@ -71,6 +82,13 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     const int64_t b0 = ((int64_t)blockIdx.x * NW + wave) * 16;            // first batch row of this wave
     const int64_t lo = (int64_t)blockIdx.y * slice, hi = min(n, lo + slice);
     unsigned long long (*kw)[CAP] = keys + wave * 16;
+    if constexpr (DEEP) {
+        static_assert(NW * 16 == 64, "one ceiling per lane covers the workgroup's users");
+        if (go && *go == 0) return;                                      // the round before left no slice open
+        const int64_t ub = (int64_t)blockIdx.x * 64 + lane;
+        const bool open = ub < nusers && ceil[(int64_t)blockIdx.y * nusers + ub] != 0ull;
+        if (!__ballot(open)) return;                                     // the same in every wave of the workgroup
+    }
 
     float ua[E];
     load_frow<E>(U + (size_t)users[min(b0 + c, nusers - 1)] * ld + E * q, ua);
@@ -78,12 +96,14 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     bool valid[4];
     int64_t cur[4], end[4];
     int nxt[4];                                                          // next seen item of rows 4q + r
+    unsigned long long cl[4] = {0ull, 0ull, 0ull, 0ull};                 // DEEP: ceiling keys of rows 4q + r
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t rb = b0 + 4 * q + r;
         valid[r] = rb < nusers;
         const int u = users[min(rb, nusers - 1)];
         bu[r] = b_u[u];
+        if constexpr (DEEP) cl[r] = valid[r] ? ceil[(int64_t)blockIdx.y * nusers + rb] : 0ull;
         cur[r] = end[r] = 0;
         if (seen_ptr && valid[r]) {
             int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
@@ -169,7 +189,8 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         for (int r = 0; r < 4; ++r) {
             const float score = walk::score(acc[r], mu, bu[r], bi);
             const unsigned long long key = make_key(score, (unsigned)col);
-            const bool pass = col < hi && valid[r] && !((msk[r] >> c) & 1u) && score == score && key > thr[r];
+            bool pass = col < hi && valid[r] && !((msk[r] >> c) & 1u) && score == score && key > thr[r];
+            if constexpr (DEEP) pass = pass && key < cl[r];
             const unsigned long long m = __ballot(pass);
             const unsigned sub = (unsigned)(m >> (16 * q)) & 0xFFFFu;
             if (pass) kw[4 * q + r][L + cnt[r] + __popc(sub & ((1u << c) - 1u))] = key;
@@ -340,17 +361,44 @@ int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, in
         const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
         auto kern = allow ? k_recommend<KB, RC_NARROW / 16, 128, true> : k_recommend<KB, RC_NARROW / 16, 128, false>;
         hipLaunchKernelGGL(kern, grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow);
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr);
     } else {
         const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
         auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true> : k_recommend<KB, RC_WIDE / 16, 256, false>;
         hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow);
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr);
     }
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
+template <int KB>
+int launch_recommend_ceil(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U,
+                          const float* Z, const float* b_u, const float* b_i, const double* mu,
+                          const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                          unsigned long long* part, const unsigned long long* ceil, const int32_t* go, hipStream_t st) {
+    const int64_t slice = walk::slice_items(n, nsl);
+    const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
+    auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true, true> : k_recommend<KB, RC_WIDE / 16, 256, false, true>;
+    hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr,
+                       seen_idx, ALS_TOPK_MAX, nullptr, nullptr, nullptr, part, allow, ceil, go);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
 }  // namespace
+
+// one scoring round of als_recommend_deep (recommend_deep.hpp)
+int deep::score_round(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
+                      const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
+                      const int32_t* seen_idx, const uint32_t* allow, unsigned long long* part,
+                      const unsigned long long* ceil, const int32_t* go, hipStream_t st) {
+    int rc = ALS_E_BADK;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend_ceil<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
+                                                            seen_idx, allow, part, ceil, go, st));
+    return rc;
+}
+int deep::plan_slices(int64_t nusers, int64_t n, int nslices) {
+    return walk::plan_slices(nusers, RC_WIDE, n, nslices, ALS_RECOMMEND_MAX_SLICES);
+}
 
 extern "C" size_t als_recommend_workspace_bytes(int64_t nusers, int64_t n, int topn, int nslices) {
     if (nusers <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;

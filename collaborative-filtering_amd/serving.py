@@ -1,6 +1,7 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
-`recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile` and `list_miscalibration`.
+`recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile`, `list_miscalibration` and
+`recommend*_deep`.
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -21,6 +22,7 @@ import torch
 from . import layout
 
 RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
+RECOMMEND_DEEP_MAX_N = 1024     # ALS_TOPK_DEEP_MAX: longest list of ALS.recommend_deep
 
 logger = logging.getLogger(__name__)
 
@@ -83,6 +85,17 @@ def pack_bitmap(mask: torch.Tensor) -> torch.Tensor:
     return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
 
 
+def cursor_keys(after_items: np.ndarray, after_scores: np.ndarray) -> np.ndarray:
+    """The cursor keys of als_recommend_deep (include/als_hip.h) for the entries (after_items [B], after_scores [B]):
+    (enc(float32(score)) << 32) | (0xFFFFFFFF - item) as int64 bit patterns; item -1 - the padding of an exhausted
+    list - gives key 0, below which no candidate lies."""
+    bits = (after_scores.astype(np.float32) + np.float32(0.0)).view(np.uint32).astype(np.uint64)      # -0.0 -> +0.0
+    enc = np.where(bits & np.uint64(0x80000000), bits ^ np.uint64(0xFFFFFFFF), bits | np.uint64(0x80000000))
+    low = np.uint64(0xFFFFFFFF) - np.maximum(after_items, 0).astype(np.uint64)
+    key = np.where(after_items < 0, np.uint64(0), (enc << np.uint64(32)) | low)
+    return key.astype(np.uint64).view(np.int64)
+
+
 def _raise_unless_solved(status: torch.Tensor, what: str, row_name=lambda r: f"row {r}") -> None:
     """`status` is the one-word result of a solve kernel: 0, or 1 + the first row whose system failed."""
     bad = int(status.item())
@@ -101,6 +114,11 @@ class _Serving:
     # EXPLORE_W_BYTES hold (4096 rows at k = 64, 655 at k = 160), at most REC_BATCH; EXPLORE_BATCH overrides (tests)
     EXPLORE_W_BYTES = 64 << 20
     EXPLORE_BATCH: Optional[int] = None
+    # rows per als_recommend_deep call: at most DEEP_BATCH (and REC_BATCH), halved until the call's workspace - 8 nb
+    # (128 S + NL + S) + 64 bytes, S <= 64 slices, a running list of NL <= 1024 keys, so at most 74 240 B per row - is
+    # within DEEP_WS_BYTES.  Few slices (many users, short lists) allow large calls, which the walk rewards
+    DEEP_BATCH = 1 << 16
+    DEEP_WS_BYTES = 512 << 20
 
     # ------------------------------------------------------------- helpers
     def _concat_w(self, names, dims, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -519,6 +537,50 @@ class _Serving:
         side = self._joint_side(features, folded)
         return self._topk_chunks(users_t.numel(), N, self._joint_rows(users_t, exclude_seen, folded), side,
                                  allow=self.allow_bitmap(filters, side["n"]))
+
+    # ------------------------------------------------------------ deep lists
+    def _deep_chunks(self, B: int, N: int, rows, items: dict, allow: Optional[torch.Tensor], after):
+        """als_recommend_deep over B batch rows in chunks (DEEP_BATCH, DEEP_WS_BYTES); `rows`, `items`, `allow` as in
+        `_topk_chunks`, `after` the validated (after_items int64 [B], after_scores float64 [B]) cursor or None.  Returns host (items
+        int64 [B, N], scores float64 [B, N]), copied chunk by chunk."""
+        keys = None if after is None else torch.from_numpy(cursor_keys(*after)).to(self.dev)
+        out_items = np.empty((B, N), dtype=np.int64)
+        out_scores = np.empty((B, N), dtype=np.float64)
+        step = min(B, self.DEEP_BATCH, self.REC_BATCH)     # the chunk sources are sized for REC_BATCH rows at most
+        while step > 1 and self.be.recommend_deep_workspace_bytes(step, items["n"], N) > self.DEEP_WS_BYTES:
+            step = (step + 1) // 2
+        for b0 in range(0, B, step):
+            nb = min(step, B - b0)
+            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
+            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
+            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+            self.be.recommend_deep(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, allow=allow,
+                                   after_key=None if keys is None else keys[b0: b0 + nb], topn=N, top_val=tv,
+                                   top_idx=ti, top_cnt=tc, **items)
+            out_items[b0: b0 + nb] = ti.cpu().numpy()
+            out_scores[b0: b0 + nb] = tv.cpu().numpy()
+        return out_items, out_scores
+
+    def recommend_deep(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
+                       folded: Optional["FoldedItems"] = None, filters=None, after=None):
+        """`recommend` (or `recommend_with_items` with `folded`) for N up to RECOMMEND_DEEP_MAX_N, below the cursor
+        `after` when given: als_recommend_deep in the chunks of `_deep_chunks`."""
+        if folded is None:
+            side = self._item_side(self._compose_for(features))
+            rows = self._fitted_rows(users_t, exclude_seen)
+        else:
+            side = self._joint_side(features, folded)
+            rows = self._joint_rows(users_t, exclude_seen, folded)
+        return self._deep_chunks(users_t.numel(), N, rows, side, self.allow_bitmap(filters, side["n"]), after)
+
+    def recommend_new_deep(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
+                           filters=None, after=None):
+        """Fold in, then als_recommend_deep on the folded table, as `recommend_new`."""
+        Z = self._compose_for(features)
+        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        return self._deep_chunks(indptr.size - 1, N, rows, self._item_side(Z), self.allow_bitmap(filters, self.n),
+                                 after)
 
     # ------------------------------------------------------------ diversity
     def _pool_chunks(self, B: int, N: int, pool: int, rows, items: dict, allow, with_stat: bool, rerank):

@@ -12,7 +12,7 @@ import torch
 
 from . import layout
 from .containers import _SideDev
-from .serving import RECOMMEND_MAX_N, FoldedItems
+from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, FoldedItems
 
 
 def host_features(features):
@@ -46,6 +46,36 @@ def top_count(x, name: str) -> int:
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= RECOMMEND_MAX_N:
         raise ValueError(f"{name} must be an integer in [1, {RECOMMEND_MAX_N}], got {x!r}")
     return int(x)
+
+
+def deep_topn(x) -> int:
+    """The length N of `recommend_deep`: an integer in [1, RECOMMEND_DEEP_MAX_N]."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= RECOMMEND_DEEP_MAX_N:
+        raise ValueError(f"N must be an integer in [1, {RECOMMEND_DEEP_MAX_N}], got {x!r}")
+    return int(x)
+
+
+def deep_cursor(after, B: int, n_total: int):
+    """`after=` of `recommend_deep`: None, or (after_items [B], after_scores [B]) - the last entry of the page each
+    row already has -> (int64 [B], float64 [B]).  Items are integer ids in [-1, n_total) (-1: the padding of an
+    exhausted list), scores real and not NaN (+-inf are values a list can hold)."""
+    if after is None:
+        return None
+    if not isinstance(after, (tuple, list)) or len(after) != 2:
+        raise ValueError("after must be (after_items, after_scores)")
+    it, sc = (np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a) for a in after)
+    if it.shape != (B,) or sc.shape != (B,):
+        raise ValueError(f"after_items and after_scores must have shape ({B},), one entry per row of the batch")
+    if it.dtype == np.bool_ or not (np.issubdtype(it.dtype, np.integer) or it.size == 0):
+        raise ValueError(f"after_items must hold integer item ids, got dtype {it.dtype}")
+    if sc.dtype == np.bool_ or not (np.issubdtype(sc.dtype, np.integer) or np.issubdtype(sc.dtype, np.floating)):
+        raise ValueError(f"after_scores must hold real numbers, got dtype {sc.dtype}")
+    if it.size and (it.min() < -1 or it.max() >= n_total):
+        raise ValueError(f"after_items: item ids must lie in [-1, {n_total})")
+    sc = sc.astype(np.float64)
+    if np.isnan(sc).any():
+        raise ValueError("after_scores must not contain NaN")
+    return it.astype(np.int64), sc
 
 
 def diversity_args(diversity, N: int, pool):

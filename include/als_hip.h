@@ -458,6 +458,35 @@ int als_recommend_topk_masked(int k, int ld, int64_t nusers, const int32_t* user
                               size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Deep top-N with a paging cursor: als_recommend_topk_masked for 1 <= topn <= ALS_TOPK_DEEP_MAX, exactly.
+ *   Model arguments, seen rows, allow (NULL = every item), scores, order, ties, unused slots (top_idx -1, top_val
+ *   -inf) and top_cnt are als_recommend_topk_masked's; for topn <= ALS_TOPK_MAX and after_key == NULL the outputs
+ *   equal that call's, element for element.  n < 2^31; nusers == 0 is a no-op.
+ * after_key: NULL, or [nusers] cursor keys.  A candidate is the 64-bit key (enc(score) << 32) | (0xFFFFFFFF - item),
+ *   enc(s) = the bits of s + 0.0f with the sign bit set when s >= 0 and all bits inverted otherwise, so that the
+ *   integer order of the keys is (score descending, item ascending).  Row b then lists the topn best candidates whose
+ *   key is STRICTLY BELOW after_key[b]: with the key of the last entry of a page, the next page.  after_key[b] == 0
+ *   (no candidate is below it) gives an empty row, ~0 is no cursor.
+ * rounds: NULL, or one device int that receives the number of scoring rounds that did work, 1 ... ceil(topn / 128).
+ *   The call enqueues ceil(topn / 128) rounds of (scoring below a per-slice ceiling, merge) without synchronising with
+ *   the host; the kernels of a round return at once when the round before left no slice open, which is the rule when
+ *   the best topn items are spread over the slices.  The result is exact and does not depend on the slice count.
+ * nslices: as als_recommend_topk; 0 = automatic: that call's count, but at least ALS_DEEP_SLICE_FACTOR ceil(topn / 128)
+ *   (capped by ALS_RECOMMEND_MAX_SLICES and one slice per 32 items).
+ * workspace: als_recommend_deep_workspace_bytes(nusers, n, topn, nslices) bytes of device memory, always > 0:
+ *   8 nusers (128 S + NL + S) + 64 with S the slice count and NL = 128, 256, 512 or 1024, the least that holds topn
+ *   (the slice lists, the running list, the ceilings, the round flags).  The call allocates nothing.
+ * ------------------------------------------------------------------------- */
+#define ALS_TOPK_DEEP_MAX 1024
+#define ALS_DEEP_SLICE_FACTOR 4
+size_t als_recommend_deep_workspace_bytes(int64_t nusers, int64_t n, int topn, int nslices);
+int als_recommend_deep(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                       const float* Z, const float* b_u, const float* b_i, const double* mu,
+                       const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                       const unsigned long long* after_key, int topn, int nslices, float* top_val, int32_t* top_idx,
+                       int32_t* top_cnt, int32_t* rounds, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Exact full-catalogue ranks (evaluation).  Model arguments as als_recommend_topk: score(u, j) is bitwise the fp32
  * value als_predict_dense writes; seen_ptr / seen_idx a CSR by USER ID, ascending (both NULL = exclude nothing).
  * For user u the candidates are C(u) = { j < n : j not in u's seen row, score(u, j) is not NaN }.
