@@ -28,7 +28,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_audience_workspace_bytes", "als_audience_topk", "als_group_workspace_bytes", "als_group_topk",
            "als_row_whitener", "als_explore_workspace_bytes", "als_explore_topk",
            "als_category_profile", "als_calibrated_rerank", "als_list_miscalibration",
-           "als_recommend_deep_workspace_bytes", "als_recommend_deep")
+           "als_recommend_deep_workspace_bytes", "als_recommend_deep",
+           "als_recommend_topk_segmented", "als_rank_count_segmented", "als_eligibility_bitmaps")
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -174,6 +175,12 @@ def load():
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_recommend_topk_masked.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_recommend_topk_segmented.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _i64, _i64, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_rank_count_segmented.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                             _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t,
+                                             _vp]
+    lib.als_eligibility_bitmaps.argtypes = [_i64, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_recommend_deep_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
     lib.als_recommend_deep.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]

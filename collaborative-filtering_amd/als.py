@@ -15,7 +15,8 @@ signature is unchanged):
   predict_at(flat_idx, ...) predictions at flat indices u*n+i without the
                             dense m x n matrix
   recommend / fold_in / recommend_new / rank_of / rank_of_new / explain / explain_new / fold_in_items /
-  predict_new_items / similar_items / similar_users / recommend_users    serving calls on the fitted tables
+  predict_new_items / similar_items / similar_users / recommend_users / eligibility / recommend_eligible /
+  recommend_new_eligible / rank_of_eligible    serving calls on the fitted tables
 
 This module holds the `ALS` facade (each public method: validate, enter the device, call the engine, convert) and
 the memoised host build of the similarity graph.  The fit engine `_Engine` is engine.py; the device containers it
@@ -37,7 +38,9 @@ from . import layout, validate
 from .als_config import ALSConfig
 from .containers import FitCache, _SideDev, _TasksDev, _side_to_dev, _tasks_to_dev  # noqa: F401
 from .engine import EPS, SCALE_FACTOR, W_F64_BELOW, SweepNotResident, _Engine  # noqa: F401
+from . import serving
 from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, Explanation, FoldedItems, _Serving, concat_features  # noqa: F401
+from .serving import ItemEligibility
 from .validate import _as_side, _check_csr, _validate_graph  # noqa: F401
 from .validate import fold_in_csr, new_item_features, new_item_graph_csr  # noqa: F401
 from .validate import host_features as _host_features
@@ -347,6 +350,101 @@ class ALS:
             return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
         with _on(self._eng.dev):
             return self._eng.recommend_new(indptr, indices, vals, N, features, T, exclude_seen, filters)
+
+    # ---------------------------------------------------------- eligibility
+    def _n_total(self, new_items: Optional[FoldedItems]) -> int:
+        if new_items is not None:
+            validate.folded_items(self, new_items)
+        return self.V.shape[0] + (new_items.n_items if new_items is not None else 0)
+
+    def eligibility(self, segment_items=None, *, item_tags=None, rules=None, items=None, filter_items=None,
+                    new_items: Optional[FoldedItems] = None) -> ItemEligibility:
+        """A per-segment eligibility table for `recommend_eligible` / `recommend_new_eligible` / `rank_of_eligible`:
+        which items each of S segments of users (a country, a subscription tier, an age rating, a language, or a
+        combination) may be shown.  The table lives on the device (4 S ceil(n_total / 32) bytes, at most
+        serving.ELIGIBILITY_MAX_BYTES) and is reused across calls.  Exactly one of two inputs:
+
+        `segment_items`: a bool array [S, n_total] (True = eligible), or a sequence of S arrays of item ids.
+
+        `item_tags` with `rules`: `item_tags` is bool [n_total, A] (A <= 256 attributes) or the packed uint32
+        [n_total, tw] (attribute a = bit a & 31 of word a >> 5); `rules` is a dict with some of "need_all",
+        "need_any", "forbid", each bool [S, A] / uint32 [S, tw].  Item i is eligible in segment s when it has no
+        attribute of forbid[s], every attribute of need_all[s], and - unless need_any[s] is empty - at least one of
+        need_any[s].  The table is built on the device (als_eligibility_bitmaps), so a million items by a thousand
+        segments never exist as a dense array.
+
+        `items` / `filter_items` (as in `recommend`) are ANDed into every segment.  n_total is n, or n + B with
+        `new_items` (a `fold_in_items` result): the table then spans the joint catalogue, and only calls with the same
+        `new_items` take it."""
+        validate.fitted(self)
+        n_total = self._n_total(new_items)
+        kind, payload = validate.eligibility_inputs(segment_items, item_tags, rules, n_total,
+                                                    serving.ELIGIBILITY_MAX_BYTES)
+        filters = validate.item_filters(items, filter_items, n_total)
+        if kind == "masks" and filters is not None:
+            payload = payload & validate.allowed_mask(filters, n_total)[None, :]
+        with _on(self._eng.dev):
+            return self._eng.eligibility_table(kind, payload, filters, n_total)
+
+    def recommend_eligible(self, users=None, N: int = 10, *, eligibility: ItemEligibility, segments,
+                           features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                           new_items: Optional[FoldedItems] = None):
+        """`recommend` with a per-user catalogue: batch row b is ranked among the items eligible in segment
+        segments[b] of `eligibility` (an `ALS.eligibility` table).  `segments`: one id in [0, S) per batch row -
+        aligned with `users` (length m when `users` is None), so the same user may appear under several segments.
+
+        Returns and padding are `recommend`'s, and row b equals, element for element, row 0 of
+        `recommend([users[b]], N, items=<the eligible items of segments[b]>, ...)`.  One fused kernel serves the
+        whole batch, whatever the number of segments in it (als_recommend_topk_segmented): every row's bitmap
+        word joins the candidate test of its own scores."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        elig = validate.eligibility_table(eligibility, self._n_total(new_items))
+        u = validate.user_ids(users, self.U.shape[0])
+        seg = validate.segment_ids(segments, u.size, elig.n_segments)
+        if u.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_eligible(self._dev_i32(u), N, features, exclude_seen, elig, self._dev_i32(seg),
+                                                new_items)
+
+    def recommend_new_eligible(self, R_new, N: int = 10, *, eligibility: ItemEligibility, segments,
+                               features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                               exclude_seen: bool = True):
+        """`recommend_new` with a per-row catalogue: new row b is ranked among the items eligible in segment
+        segments[b] of `eligibility` (one id per row of R_new), as `recommend_eligible`."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        T = validate.sweeps(n_sweeps)
+        indptr, indices, vals = fold_in_csr(R_new, self.V.shape[0])
+        elig = validate.eligibility_table(eligibility, self.V.shape[0])
+        seg = validate.segment_ids(segments, indptr.size - 1, elig.n_segments, "row of R_new")
+        if indptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_new_eligible(indptr, indices, vals, N, features, T, exclude_seen, elig,
+                                                    self._dev_i32(seg))
+
+    def rank_of_eligible(self, users, items, *, eligibility: ItemEligibility, segments,
+                         features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                         new_items: Optional[FoldedItems] = None):
+        """`rank_of` within each user's eligible catalogue: (rank, n_candidates, scores) as `rank_of`, the candidates
+        of pair p being the items eligible in segment segments[p] (one id per pair).  All pairs of one user must name
+        the same segment (ValueError otherwise): a user's row is scored once.  An item `recommend_eligible` returns
+        at position j has rank j; the rank of a target that is itself not eligible is the position it would take
+        (als_rank_count_segmented).  With `new_items` the targets and the table span the joint catalogue."""
+        features = self._check_predict(features)
+        n_total = self._n_total(new_items)
+        u, i = validate.id_pairs(users, items, self.U.shape[0], n_total)
+        elig = validate.eligibility_table(eligibility, n_total)
+        seg = validate.segment_ids(segments, u.size, elig.n_segments, "(user, item) pair")
+        if np.unique(np.stack([u, seg.astype(np.int64)]), axis=1).shape[1] != np.unique(u).size:
+            raise ValueError("segments: the pairs of one user must all name the same segment")
+        if u.size == 0:
+            return np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float32)
+        with _on(self._eng.dev):
+            return self._eng.rank_of_eligible(self._dev_i32(u), self._dev_i32(i), features, exclude_seen, elig,
+                                              self._dev_i32(seg), new_items)
 
     # ----------------------------------------------------------- deep lists
     def recommend_deep(self, users=None, N: int = 500, *, features: Optional[Dict[str, np.ndarray]] = None,

@@ -384,6 +384,49 @@ class HipBackend:
         self._rank(self.lib.als_rank_count_masked, "als_rank_count_masked", (_p(allow),), k, ld, n, U, Z, b_u, b_i, mu,
                    seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above, n_cand)
 
+    def _segment_args(self, seg_allow: torch.Tensor, row_seg: torch.Tensor, n: int, rows: int):
+        # the kernels index the table by (segment, item word) and row_seg by batch row: anything short is an
+        # out-of-bounds read.  Ids outside [0, S) are the kernel's to refuse (such a row gets no candidates)
+        W = (n + 31) // 32
+        if (seg_allow.dtype != torch.int32 or not seg_allow.is_cuda or not seg_allow.is_contiguous()
+                or seg_allow.dim() != 2 or seg_allow.shape[0] < 1 or seg_allow.shape[1] < W):
+            raise ValueError(f"eligibility table must be a contiguous int32 device tensor [S >= 1, >= {W} words]")
+        if (row_seg.dtype != torch.int32 or not row_seg.is_cuda or not row_seg.is_contiguous()
+                or row_seg.numel() != rows):
+            raise ValueError("row_seg must be a contiguous int32 device tensor with one segment id per batch row")
+        return _p(seg_allow), seg_allow.shape[0], seg_allow.shape[1], _p(row_seg)
+
+    def recommend_topk_segmented(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, seg_allow, row_seg,
+                                 topn, top_val, top_idx, top_cnt):
+        """`recommend_topk_masked` with the bitmap of batch row b being row row_seg[b] (int32 [B]) of the table
+        `seg_allow` (int32 [S, >= ceil(n / 32)]): als_recommend_topk_segmented."""
+        seg = self._segment_args(seg_allow, row_seg, n, users.numel())
+        self._recommend(self.lib.als_recommend_topk_segmented, "als_recommend_topk_segmented", seg, k, ld, users, n, U,
+                        Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
+
+    def rank_count_segmented(self, *, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, seg_allow, row_seg, q_users,
+                             q_ptr, q_items, t_score, above, n_cand):
+        """`rank_count_masked` with one table row per batch row, as `recommend_topk_segmented`:
+        als_rank_count_segmented."""
+        seg = self._segment_args(seg_allow, row_seg, n, q_users.numel())
+        self._rank(self.lib.als_rank_count_segmented, "als_rank_count_segmented", seg, k, ld, n, U, Z, b_u, b_i, mu,
+                   seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above, n_cand)
+
+    def eligibility_bitmaps(self, *, n, item_tags, need_all, need_any, forbid, base_allow, out):
+        """out int32 [S, ceil(n / 32)] = the eligibility table of the rules need_all / need_any / forbid (int32 [S, tw]
+        each, None = all zero) over item_tags (int32 [n, tw]), ANDed with the bitmap base_allow (or None):
+        als_eligibility_bitmaps."""
+        tw, S = item_tags.shape[1], out.shape[0]
+        assert item_tags.dtype == torch.int32 and item_tags.is_contiguous() and item_tags.shape[0] == n
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape[1] == (n + 31) // 32
+        for r in (need_all, need_any, forbid):
+            assert r is None or (r.dtype == torch.int32 and r.is_contiguous() and tuple(r.shape) == (S, tw))
+        if base_allow is not None:
+            self._check_bitmap(base_allow, n)
+        self._check(self.lib.als_eligibility_bitmaps(n, tw, _p(item_tags), S, _p(need_all), _p(need_any), _p(forbid),
+                                                     _p(base_allow), _p(out), self._stream()),
+                    "als_eligibility_bitmaps")
+
     def _rank(self, fn, what, allow, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items,
               t_score, above, n_cand):
         if seen_idx is not None and seen_idx.numel() == 0:

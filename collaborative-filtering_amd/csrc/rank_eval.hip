@@ -25,6 +25,10 @@
 // workgroup, the prefetch aimed at the next chunk with a set bit.  Target scores are formed whether or not the
 // target is allowed.  The unmasked instantiations contain none of this.
 //
+// Eligibility table (als_rank_count_segmented; the SEG instantiations) as k_recommend's: one word per row 4q + r and
+// chunk, prefetched behind the Z loads, ANDed into the candidate test; a wave none of whose rows has a set bit in the
+// chunk counts nothing but still stages and passes both barriers.  Not combined with MASKED.
+//
 // "k_recommend's" above means a second copy of that code in this file, not a shared implementation: only the chunk and
 // slice arithmetic and the score epilogue are shared (catalogue_walk.hpp, which says why the rest is not).  An edit
 // to the walk in recommend.hip belongs here too.
@@ -42,14 +46,16 @@ constexpr int RK_TP = 16;           // targets per row and pass (4 * RK_TP count
 constexpr int RK_TG = 8;            // targets per skip group
 constexpr unsigned long long RK_NONE = ~0ull;   // target key of a NaN score / an unused slot: nothing is above it
 
-template <int KB, int NW, bool MASKED>
+template <int KB, int NW, bool MASKED, bool SEG = false>
 __global__ __launch_bounds__(NW * 64)
 void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const int64_t* __restrict__ q_ptr,
                   const int32_t* __restrict__ q_items, int64_t n, int64_t slice, const float* __restrict__ U,
                   const float* __restrict__ Z, const float* __restrict__ b_u, const float* __restrict__ b_i,
                   const double* __restrict__ mu_p, const int64_t* __restrict__ seen_ptr,
                   const int32_t* __restrict__ seen_idx, float* __restrict__ t_score, int32_t* __restrict__ above,
-                  int32_t* __restrict__ n_cand, int64_t slice_stride, const uint32_t* __restrict__ allow) {
+                  int32_t* __restrict__ n_cand, int64_t slice_stride, const uint32_t* __restrict__ allow, int64_t nseg,
+                  int64_t seg_stride, const int32_t* __restrict__ row_seg) {
+    static_assert(!SEG || !MASKED, "the eligibility table replaces the bitmap");
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int NT = NW * 64, NV = RK_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     __shared__ unsigned long long tks[NW * 16][RK_TP];
@@ -68,12 +74,19 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
     float bu[4];
     bool valid[4];
     int su[4];                                                           // user ids of rows 4q + r
+    int64_t so[4] = {0, 0, 0, 0};                                        // SEG: word of chunk 0 in the segment row of rows 4q + r
+    bool sv[4] = {false, false, false, false};                           // SEG: the row is valid and its segment id in range
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t rb = b0 + 4 * q + r;
         valid[r] = rb < nq;
         su[r] = users[min(rb, nq - 1)];
         bu[r] = b_u[su[r]];
+        if constexpr (SEG) {
+            const int64_t sg = row_seg[min(rb, nq - 1)];
+            sv[r] = valid[r] && sg >= 0 && sg < nseg;
+            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / RK_CHUNK;       // lo is a multiple of 32
+        }
     }
     // target range of row c (the row whose targets this lane gathers) and the largest count of the wave's rows
     const int64_t ctp = q_ptr[min(b0 + c, nq - 1)];
@@ -133,6 +146,13 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         const unsigned long long m = __ballot(pw != 0u);
         return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
     };
+    // SEG: the words of chunk `ch` in the segment rows of this lane's rows 4q + r, 0 for a row that takes no part;
+    // ch < nch keeps the word inside the table row (lo / 32 + ch < ceil(n / 32) <= seg_stride)
+    unsigned sp[4] = {0u, 0u, 0u, 0u};
+    auto seg_fetch = [&](int64_t ch) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sp[r] = sv[r] ? allow[so[r] + ch] : 0u;
+    };
     for (int pass = 0; pass < npass; ++pass) {
         const int64_t t0 = (int64_t)pass * RK_TP;                        // first target of this pass
         const int wt = (int)max(min(wtn - t0, (int64_t)RK_TP), (int64_t)0);      // targets of the wave's fullest row
@@ -188,6 +208,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         }
 
         unsigned deny = 0u; // MASKED: bit c set = item cb + c of the block `keys_of` is called for is not allowed
+        unsigned dn[4] = {0u, 0u, 0u, 0u};                               // SEG: the same, one word per row 4q + r
         // one 16-item block [cb, cb + 16): keys of the lane's four scores, 0 where the score is no candidate
         auto keys_of = [&](const f32x4& acc, int64_t cb, unsigned long long (&key)[4]) {
             unsigned msk[4] = {0u, 0u, 0u, 0u};
@@ -223,6 +244,10 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
 #pragma unroll
                 for (int r = 0; r < 4; ++r) msk[r] |= deny;
             }
+            if constexpr (SEG) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) msk[r] |= dn[r];
+            }
             const int64_t col = cb + c;
             const float bi = b_i[min(col, n - 1)];
 #pragma unroll
@@ -238,19 +263,35 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         if constexpr (MASKED) {
             nx = next_chunk(0);
             if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }
-        } else if (nch > 0) fetch(lo);
+        } else if (nch > 0) {
+            fetch(lo);
+            if constexpr (SEG) seg_fetch(0);
+        }
         for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
             const int64_t it0 = lo + ch * RK_CHUNK;
             unsigned word = 0u;
             if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
+            unsigned sw[4] = {0u, 0u, 0u, 0u};           // SEG: this chunk's words, before the prefetch reuses sp
+            if constexpr (SEG) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sw[r] = sp[r];
+            }
             __syncthreads();                             // every wave is done with the previous chunk
             stage();
             __syncthreads();
             if constexpr (MASKED) {
                 nx = after(ch);
                 if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }      // however far ahead
-            } else if (ch + 1 < nch) fetch(it0 + RK_CHUNK);
+            } else if (ch + 1 < nch) {
+                fetch(it0 + RK_CHUNK);
+                if constexpr (SEG) seg_fetch(ch + 1);
+            }
             if (!active) continue;                       // wave-uniform: this wave's rows have no targets left
+            if constexpr (SEG) {
+                // none of the wave's 16 rows may take an item of this chunk: no scores, nothing to count.  The wave
+                // has staged its share and passed both barriers; its counters are as the last chunk left them
+                if (!__ballot((sw[0] | sw[1] | sw[2] | sw[3]) != 0u)) continue;
+            }
             float z0[E], z1[E];
             load_frow<E>(&zs[c][E * q], z0);
             load_frow<E>(&zs[16 + c][E * q], z1);
@@ -262,8 +303,16 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             }
             unsigned long long k0[4], k1[4];
             if constexpr (MASKED) deny = ~word & 0xFFFFu;
+            if constexpr (SEG) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dn[r] = ~sw[r] & 0xFFFFu;
+            }
             keys_of(acc0, it0, k0);
             if constexpr (MASKED) deny = ~word >> 16;
+            if constexpr (SEG) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dn[r] = ~sw[r] >> 16;
+            }
             keys_of(acc1, it0 + 16, k1);
 #pragma unroll
             for (int g = 0; g < RK_TP / RK_TG; ++g) {
@@ -348,7 +397,22 @@ int launch_rank(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, 
     const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
     auto kern = allow ? k_rank_count<KB, NW, true> : k_rank_count<KB, NW, false>;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n, slice, U, Z, b_u, b_i, mu,
-                       seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, allow);
+                       seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, allow, (int64_t)0, (int64_t)0, nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+template <int KB>
+int launch_rank_seg(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, const int32_t* q_items, int64_t n,
+                    int nsl, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
+                    const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* seg_allow, int64_t nseg,
+                    int64_t seg_stride, const int32_t* row_seg, float* t_score, int32_t* above, int32_t* n_cand,
+                    int64_t slice_stride, hipStream_t st) {
+    constexpr int NW = rk_waves(KB);
+    const int64_t slice = walk::slice_items(n, nsl);
+    const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
+    hipLaunchKernelGGL((k_rank_count<KB, NW, false, true>), grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n,
+                       slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, seg_allow,
+                       nseg, seg_stride, row_seg);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
@@ -386,6 +450,38 @@ extern "C" int als_rank_count_masked(int k, int ld, int64_t n, const float* U, c
     ALS_DISPATCH_KB(ld / 16, rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
                                                   seen_idx, allow, t_score, part ? part : above,
                                                   part ? part + nt : n_cand, part ? nt + nq : 0, st));
+    if (rc != 0 || nsl == 1) return rc;
+    hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
+                       above, n_cand);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+extern "C" int als_rank_count_segmented(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
+                                        const float* b_i, const double* mu, const int64_t* seen_ptr,
+                                        const int32_t* seen_idx, const uint32_t* seg_allow, int64_t nseg,
+                                        int64_t seg_stride_words, const int32_t* row_seg, int64_t nq,
+                                        const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items,
+                                        int64_t nt, int nslices, float* t_score, int32_t* above, int32_t* n_cand,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    const int kp = als_padded_k(k);
+    if (kp < 0) return ALS_E_BADK;
+    if (ld != kp || nq < 0 || nt < 0 || n < 1 || n >= ((int64_t)1 << 31) || nslices < 0 ||
+        nslices > ALS_RECOMMEND_MAX_SLICES || nseg < 1 || seg_stride_words < (n + 31) / 32)
+        return ALS_E_BADARG;
+    if (nq == 0) return 0;
+    if (!q_users || !q_ptr || !U || !Z || !b_u || !b_i || !mu || !n_cand || (!seen_ptr != !seen_idx) ||
+        (nt > 0 && (!q_items || !t_score || !above)) || !seg_allow || !row_seg)
+        return ALS_E_BADARG;
+    const int nsl = rank_slices(ld, nq, n, nslices);
+    const size_t need = als_rank_count_workspace_bytes(k, nq, nt, n, nslices);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* part = nsl > 1 ? (int32_t*)workspace : nullptr;
+    int rc;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_rank_seg<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu,
+                                                      seen_ptr, seen_idx, seg_allow, nseg, seg_stride_words, row_seg,
+                                                      t_score, part ? part : above, part ? part + nt : n_cand,
+                                                      part ? nt + nq : 0, st));
     if (rc != 0 || nsl == 1) return rc;
     hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
                        above, n_cand);

@@ -37,6 +37,15 @@
 // more term of the candidate test, which k_rank_count does not have.  The instantiations without DEEP contain none of
 // this: their instruction streams are those of the kernel without the parameter.
 //
+// Eligibility table (als_recommend_topk_segmented; the SEG instantiations): `allow` is then nseg rows of the bitmap,
+// seg_stride words apart, and batch row b reads row row_seg[b] - the deny word is per row, not per wave.  A lane (c, q)
+// keeps the int64 offsets of its rows 4q + r and loads their four words of the next chunk behind the Z prefetch (word
+// lo / 32 + ch of each row; 0 for a row past the batch or with a segment id outside [0, nseg)).  The low halves join
+// msk[r] for block 0, the high halves for block 1.  No chunk is skipped by the workgroup - its rows disagree about
+// which are empty -, but a wave none of whose 16 rows has a set bit in the chunk forms no scores and selects nothing:
+// it stages its share and passes both barriers, so they stay matched.  The seen cursors catch up as under MASKED.
+// SEG is combined with neither MASKED nor DEEP, and the other instantiations contain none of it.
+//
 // The walk is written a second time in rank_eval.hip (k_rank_count), character for character apart from the RC_ / RK_
 // prefix: fetch / stage, next_chunk / window / after, the cursor set-up, the exclusion walk, the score tiles, the
 // candidate test, the chunk loop.  Only the chunk and slice arithmetic and the score epilogue are one copy
@@ -60,7 +69,7 @@ constexpr int RC_NARROW = 128;      // users per workgroup, topn <= 32: 8 waves,
 __device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 
 // CAP keys per user: list [0, L) + survivor buffer [L, CAP)
-template <int KB, int NW, int CAP, bool MASKED, bool DEEP = false>
+template <int KB, int NW, int CAP, bool MASKED, bool DEEP = false, bool SEG = false>
 __global__ __launch_bounds__(NW * 64)
 void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t n, int64_t slice,
                  const float* __restrict__ U, const float* __restrict__ Z, const float* __restrict__ b_u,
@@ -68,7 +77,9 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
                  const int64_t* __restrict__ seen_ptr, const int32_t* __restrict__ seen_idx, int topn,
                  float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt,
                  unsigned long long* __restrict__ part, const uint32_t* __restrict__ allow,
-                 const unsigned long long* __restrict__ ceil, const int32_t* __restrict__ go) {
+                 const unsigned long long* __restrict__ ceil, const int32_t* __restrict__ go, int64_t nseg,
+                 int64_t seg_stride, const int32_t* __restrict__ row_seg) {
+    static_assert(!SEG || (!MASKED && !DEEP), "the eligibility table replaces the bitmap; deep lists do not take one");
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
     constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
@@ -97,6 +108,8 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     int64_t cur[4], end[4];
     int nxt[4];                                                          // next seen item of rows 4q + r
     unsigned long long cl[4] = {0ull, 0ull, 0ull, 0ull};                 // DEEP: ceiling keys of rows 4q + r
+    int64_t so[4] = {0, 0, 0, 0};                                        // SEG: word of chunk 0 in the segment row of rows 4q + r
+    bool sv[4] = {false, false, false, false};                           // SEG: the row is valid and its segment id in range
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t rb = b0 + 4 * q + r;
@@ -104,6 +117,11 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         const int u = users[min(rb, nusers - 1)];
         bu[r] = b_u[u];
         if constexpr (DEEP) cl[r] = valid[r] ? ceil[(int64_t)blockIdx.y * nusers + rb] : 0ull;
+        if constexpr (SEG) {
+            const int64_t sg = row_seg[min(rb, nusers - 1)];
+            sv[r] = valid[r] && sg >= 0 && sg < nseg;
+            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / RC_CHUNK;       // lo is a multiple of 32
+        }
         cur[r] = end[r] = 0;
         if (seen_ptr && valid[r]) {
             int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
@@ -148,6 +166,7 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     };
 
     unsigned deny = 0u;     // MASKED: bit c set = item cb + c of the block `select` is called for is not allowed
+    unsigned dn[4] = {0u, 0u, 0u, 0u};                                   // SEG: the same, one word per row 4q + r
     // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold test, append
     auto select = [&](const f32x4& acc, int64_t cb) {
         unsigned msk[4] = {0u, 0u, 0u, 0u};
@@ -182,6 +201,10 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         if constexpr (MASKED) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) msk[r] |= deny;
+        }
+        if constexpr (SEG) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) msk[r] |= dn[r];
         }
         const int64_t col = cb + c;
         const float bi = b_i[min(col, n - 1)];
@@ -239,22 +262,45 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         const unsigned long long m = __ballot(pw != 0u);
         return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
     };
+    // SEG: the words of chunk `ch` in the segment rows of this lane's rows 4q + r, 0 for a row that takes no part;
+    // ch < nch keeps the word inside the table row (lo / 32 + ch < ceil(n / 32) <= seg_stride)
+    unsigned sp[4] = {0u, 0u, 0u, 0u};
+    auto seg_fetch = [&](int64_t ch) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sp[r] = sv[r] ? allow[so[r] + ch] : 0u;
+    };
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);
         if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }
-    } else if (nch > 0) fetch(lo);
+    } else if (nch > 0) {
+        fetch(lo);
+        if constexpr (SEG) seg_fetch(0);
+    }
     for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
         const int64_t it0 = lo + ch * RC_CHUNK;
         unsigned word = 0u;
         if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
+        unsigned sw[4] = {0u, 0u, 0u, 0u};               // SEG: this chunk's words, before the prefetch reuses sp
+        if constexpr (SEG) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sw[r] = sp[r];
+        }
         __syncthreads();                                 // every wave is done with the previous chunk
         stage();
         __syncthreads();
         if constexpr (MASKED) {
             nx = after(ch);
             if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }      // however far ahead
-        } else if (ch + 1 < nch) fetch(it0 + RC_CHUNK);
+        } else if (ch + 1 < nch) {
+            fetch(it0 + RC_CHUNK);
+            if constexpr (SEG) seg_fetch(ch + 1);
+        }
+        if constexpr (SEG) {
+            // none of the wave's 16 rows may take an item of this chunk: no scores, no selection.  The wave has
+            // staged its share and passed both barriers; its buffers are as the last chunk left them
+            if (!__ballot((sw[0] | sw[1] | sw[2] | sw[3]) != 0u)) continue;
+        }
         float z0[E], z1[E];
         load_frow<E>(&zs[c][E * q], z0);
         load_frow<E>(&zs[16 + c][E * q], z1);
@@ -265,8 +311,16 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
             acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
         }
         if constexpr (MASKED) deny = ~word & 0xFFFFu;
+        if constexpr (SEG) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dn[r] = ~sw[r] & 0xFFFFu;
+        }
         select(acc0, it0);
         if constexpr (MASKED) deny = ~word >> 16;
+        if constexpr (SEG) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dn[r] = ~sw[r] >> 16;
+        }
         select(acc1, it0 + 16);
         bool full = false;
 #pragma unroll
@@ -361,12 +415,35 @@ int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, in
         const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
         auto kern = allow ? k_recommend<KB, RC_NARROW / 16, 128, true> : k_recommend<KB, RC_NARROW / 16, 128, false>;
         hipLaunchKernelGGL(kern, grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr);
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr, (int64_t)0, (int64_t)0,
+                           nullptr);
     } else {
         const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
         auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true> : k_recommend<KB, RC_WIDE / 16, 256, false>;
         hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr);
+                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr, (int64_t)0, (int64_t)0,
+                           nullptr);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+template <int KB>
+int launch_recommend_seg(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
+                         const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
+                         const int32_t* seen_idx, const uint32_t* seg_allow, int64_t nseg, int64_t seg_stride,
+                         const int32_t* row_seg, int topn, float* tv, int32_t* ti, int32_t* tc,
+                         unsigned long long* part, hipStream_t st) {
+    const int64_t slice = walk::slice_items(n, nsl);
+    if (topn <= 32) {
+        const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
+        hipLaunchKernelGGL((k_recommend<KB, RC_NARROW / 16, 128, false, false, true>), grid, dim3(RC_NARROW * 4), 0, st,
+                           ld, nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part,
+                           seg_allow, nullptr, nullptr, nseg, seg_stride, row_seg);
+    } else {
+        const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
+        hipLaunchKernelGGL((k_recommend<KB, RC_WIDE / 16, 256, false, false, true>), grid, dim3(RC_WIDE * 4), 0, st, ld,
+                           nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part,
+                           seg_allow, nullptr, nullptr, nseg, seg_stride, row_seg);
     }
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
@@ -380,7 +457,7 @@ int launch_recommend_ceil(int ld, int64_t nusers, const int32_t* users, int64_t 
     const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
     auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true, true> : k_recommend<KB, RC_WIDE / 16, 256, false, true>;
     hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr,
-                       seen_idx, ALS_TOPK_MAX, nullptr, nullptr, nullptr, part, allow, ceil, go);
+                       seen_idx, ALS_TOPK_MAX, nullptr, nullptr, nullptr, part, allow, ceil, go, (int64_t)0, (int64_t)0, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
 
@@ -428,6 +505,37 @@ extern "C" int als_recommend_topk_masked(int k, int ld, int64_t nusers, const in
     int rc;
     ALS_DISPATCH_KB(ld / 16, rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx,
                                                        allow, topn, top_val, top_idx, top_cnt, part, st));
+    if (rc != 0 || nsl == 1) return rc;
+    hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
+                       top_val, top_idx, top_cnt);
+    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+}
+
+extern "C" int als_recommend_topk_segmented(int k, int ld, int64_t nusers, const int32_t* users, int64_t n,
+                                            const float* U, const float* Z, const float* b_u, const float* b_i,
+                                            const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
+                                            const uint32_t* seg_allow, int64_t nseg, int64_t seg_stride_words,
+                                            const int32_t* row_seg, int topn, int nslices, float* top_val,
+                                            int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    const int kp = als_padded_k(k);
+    if (kp < 0) return ALS_E_BADK;
+    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
+        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES || nseg < 1 || seg_stride_words < (n + 31) / 32)
+        return ALS_E_BADARG;
+    if (nusers == 0) return 0;
+    if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx) ||
+        !seg_allow || !row_seg)
+        return ALS_E_BADARG;
+    const int nsl = rec_slices(nusers, n, topn, nslices);
+    const size_t need = als_recommend_workspace_bytes(nusers, n, topn, nslices);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
+    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend_seg<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
+                                                           seen_idx, seg_allow, nseg, seg_stride_words, row_seg, topn,
+                                                           top_val, top_idx, top_cnt, part, st));
     if (rc != 0 || nsl == 1) return rc;
     hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
                        top_val, top_idx, top_cnt);

@@ -162,6 +162,34 @@ def ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: 
     return {**_ranking_metrics(top, ub, cols, model.V.shape[0], K), **extra}
 
 
+def eligible_ranking_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, eligibility, segments_of_user,
+                          min_rating: Optional[float] = None,
+                          features: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Any]:
+    """`ranking_at_k` over `model.recommend_eligible`: recall@K and NDCG@K when every user is served from the
+    catalogue of their segment.  `eligibility` is an `ALS.eligibility` table over the n fitted items and
+    `segments_of_user` an integer array [m], the segment of every user id.
+
+    top(u) = model.recommend_eligible([u], K, eligibility=eligibility, segments=[segments_of_user[u]]).  A held-out
+    pair whose item is not eligible for its user cannot be ranked within that user's catalogue: it is left out of
+    rel(u), and "ineligible" in the result is the number of such pairs (after `min_rating`).  Otherwise the result is
+    `ranking_at_k`'s: {"users", "recall@K", "ndcg@K", "ineligible"}."""
+    validate.fitted(model)
+    m, n = model.U.shape[0], model.V.shape[0]
+    elig = validate.eligibility_table(eligibility, n)
+    seg_of = validate.segment_ids(segments_of_user, m, elig.n_segments, "user")
+    rows, cols = _held_out_pairs(rows, cols, vals, min_rating)
+    validate._in_range(rows, m, "user")
+    validate._in_range(cols, n, "item")
+    ok = elig.allowed(seg_of[rows], cols)
+    extra = {"ineligible": int((~ok).sum())}
+    rows, cols = rows[ok], cols[ok]
+    users, ub = np.unique(rows, return_inverse=True)
+    if users.size == 0:
+        return {"users": 0, "recall@K": float("nan"), "ndcg@K": float("nan"), **extra}
+    top, _ = model.recommend_eligible(users, K, eligibility=elig, segments=seg_of[users], features=features)
+    return {**_ranking_metrics(top, ub, cols, n, K), **extra}
+
+
 def diversity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, diversity: float = 0.0,
                    pool: Optional[int] = None, min_rating: Optional[float] = None,
                    features: Optional[Dict[str, np.ndarray]] = None, items=None, filter_items=None) -> Dict[str, Any]:

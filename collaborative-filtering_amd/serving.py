@@ -1,7 +1,7 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
 `recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile`, `list_miscalibration` and
-`recommend*_deep`.
+`recommend*_deep`, and the per-user eligibility calls (`eligibility`, `recommend*_eligible`, `rank_of_eligible`).
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -23,6 +23,7 @@ from . import layout
 
 RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
 RECOMMEND_DEEP_MAX_N = 1024     # ALS_TOPK_DEEP_MAX: longest list of ALS.recommend_deep
+ELIGIBILITY_MAX_BYTES = 1 << 30     # largest eligibility table ALS.eligibility builds (4 S ceil(n / 32) bytes)
 
 logger = logging.getLogger(__name__)
 
@@ -43,6 +44,22 @@ class FoldedItems:
     @property
     def n_items(self) -> int:
         return int(self.b_i.shape[0])
+
+
+@dataclass
+class ItemEligibility:
+    """Per-segment item eligibility, made by `ALS.eligibility` and resident on the device: `table` int32
+    [n_segments, ceil(n_items / 32)], row s the allow bitmap of segment s (`pack_bitmap`'s layout).  The
+    `*_eligible` calls take it with one segment id per batch row."""
+    table: torch.Tensor
+    n_segments: int
+    n_items: int
+
+    def allowed(self, segments: np.ndarray, items: np.ndarray) -> np.ndarray:
+        """bool [P]: item items[p] is eligible in segment segments[p] (read from the device table)."""
+        s = torch.from_numpy(np.asarray(segments, dtype=np.int64)).to(self.table.device)
+        i = torch.from_numpy(np.asarray(items, dtype=np.int64)).to(self.table.device)
+        return (((self.table[s, i >> 5].to(torch.int64) >> (i & 31)) & 1) != 0).cpu().numpy()
 
 
 @dataclass
@@ -83,6 +100,16 @@ def pack_bitmap(mask: torch.Tensor) -> torch.Tensor:
     bits[:n] = mask
     words = (bits.view(nw, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(dim=1)
     return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def pack_words(bits: np.ndarray) -> np.ndarray:
+    """bool [R, A] (host) -> int32 [R, ceil(A / 32)] holding uint32 words: bit a of a row is bit a & 31 of word a >> 5,
+    the bits beyond A zero - the rows of an eligibility table (A = n items: `pack_bitmap`'s layout) and the attribute
+    words of als_eligibility_bitmaps."""
+    R, A = bits.shape
+    by = np.zeros((R, (A + 31) // 32 * 4), dtype=np.uint8)
+    by[:, : (A + 7) // 8] = np.packbits(bits, axis=1, bitorder="little")
+    return by.view("<u4").astype(np.uint32).view(np.int32)
 
 
 def cursor_keys(after_items: np.ndarray, after_scores: np.ndarray) -> np.ndarray:
@@ -197,10 +224,11 @@ class _Serving:
         return rows
 
     def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False,
-                     allow: Optional[torch.Tensor] = None):
+                     allow: Optional[torch.Tensor] = None, seg=None):
         """als_recommend_topk over B batch rows in REC_BATCH chunks.  rows(b0, nb) -> (users int32 [nb], U, b_u,
         seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu); `allow`: the
-        bitmap of the call (`allow_bitmap`) - every chunk then goes through als_recommend_topk_masked.  Returns host
+        bitmap of the call (`allow_bitmap`) - every chunk then goes through als_recommend_topk_masked; `seg` =
+        (eligibility table, row_seg int32 [B] on the device) instead: als_recommend_topk_segmented.  Returns host
         (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk, or with `on_device` the kernel's own
         (top_val fp32 [B, N], top_idx int32 [B, N])."""
         if on_device:
@@ -219,7 +247,11 @@ class _Serving:
                 tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
                 ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
                 tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            if allow is None:
+            if seg is not None:
+                self.be.recommend_topk_segmented(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                                                 seg_allow=seg[0], row_seg=seg[1][b0: b0 + nb], topn=N, top_val=tv,
+                                                 top_idx=ti, top_cnt=tc, **items)
+            elif allow is None:
                 self.be.recommend_topk(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
                                        top_val=tv, top_idx=ti, top_cnt=tc, **items)
             else:
@@ -231,10 +263,11 @@ class _Serving:
         return (top_val, top_idx) if on_device else (out_items, out_scores)
 
     def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, Z,
-                     allow: Optional[torch.Tensor] = None):
+                     allow: Optional[torch.Tensor] = None, seg=None, side: Optional[dict] = None):
         """als_rank_count over the batch rows of the prefix sum `t_ptr` (device; `t_ptr_h` its host copy) in
-        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows` and `allow` as in
-        `_topk_chunks` (als_rank_count_masked).
+        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows`, `allow` and `seg` as in
+        `_topk_chunks` (als_rank_count_masked, als_rank_count_segmented); `side`: the item tables when they are not
+        the fitted ones of Z (`_joint_side`).
         Returns device (above int32 [P], n_cand int32 [rows], score fp32 [P])."""
         B, P = t_ptr_h.size - 1, q_items.numel()
         above = torch.empty(P, dtype=torch.int32, device=self.dev)
@@ -246,8 +279,11 @@ class _Serving:
             t0, t1 = int(t_ptr_h[b0]), int(t_ptr_h[b0 + nb])
             kw = dict(U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users,
                       q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
-                      t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb], **self._item_side(Z))
-            if allow is None:
+                      t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb],
+                      **(self._item_side(Z) if side is None else side))
+            if seg is not None:
+                self.be.rank_count_segmented(seg_allow=seg[0], row_seg=seg[1][b0: b0 + nb], **kw)
+            elif allow is None:
                 self.be.rank_count(**kw)
             else:
                 self.be.rank_count_masked(allow=allow, **kw)
@@ -537,6 +573,59 @@ class _Serving:
         side = self._joint_side(features, folded)
         return self._topk_chunks(users_t.numel(), N, self._joint_rows(users_t, exclude_seen, folded), side,
                                  allow=self.allow_bitmap(filters, side["n"]))
+
+    # ----------------------------------------------------------- eligibility
+    def eligibility_table(self, kind: str, payload, filters, n_total: int) -> "ItemEligibility":
+        """The resident table of `ALS.eligibility` from validate.eligibility_inputs' (kind, payload).  "masks": bool
+        [S, n_total] with the call's filters already ANDed in, packed on the host (`pack_words`), one upload.  "tags":
+        the packed tags and rules go up and als_eligibility_bitmaps writes the table with the bitmap of `filters` (the
+        validated (items, filter_items) pair or None) as its base, so nothing S x n exists on the host."""
+        W = (n_total + 31) // 32
+        if kind == "masks":
+            return ItemEligibility(torch.from_numpy(pack_words(payload)).to(self.dev), payload.shape[0], n_total)
+        tags, *rules = payload
+        S = next(r for r in rules if r is not None).shape[0]
+        up = lambda a: None if a is None else torch.from_numpy(a).to(self.dev)      # noqa: E731
+        table = torch.empty(S, W, dtype=torch.int32, device=self.dev)
+        self.be.eligibility_bitmaps(n=n_total, item_tags=up(tags), need_all=up(rules[0]), need_any=up(rules[1]),
+                                    forbid=up(rules[2]), base_allow=self.allow_bitmap(filters, n_total), out=table)
+        return ItemEligibility(table, S, n_total)
+
+    def recommend_eligible(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool, elig, row_seg,
+                           folded: Optional["FoldedItems"] = None):
+        """`recommend` (or `recommend_with_items` with `folded`) with the catalogue of batch row b restricted to row
+        row_seg[b] (int32 [B], device) of the table `elig`: als_recommend_topk_segmented in REC_BATCH chunks."""
+        if folded is None:
+            side = self._item_side(self._compose_for(features))
+            rows = self._fitted_rows(users_t, exclude_seen)
+        else:
+            side = self._joint_side(features, folded)
+            rows = self._joint_rows(users_t, exclude_seen, folded)
+        return self._topk_chunks(users_t.numel(), N, rows, side, seg=(elig.table, row_seg))
+
+    def recommend_new_eligible(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
+                               elig, row_seg):
+        """Fold in, then als_recommend_topk_segmented on the folded table, as `recommend_new`."""
+        Z = self._compose_for(features)
+        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z), seg=(elig.table, row_seg))
+
+    def rank_of_eligible(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool, elig, pair_seg,
+                         folded: Optional["FoldedItems"] = None):
+        """`rank_of` among the items eligible for each pair's segment (pair_seg int32 [P], device; the pairs of a
+        user agree on it - the facade checked): grouped by user as `rank_of`, the segment of a user's row that of
+        its first pair, als_rank_count_segmented in REC_BATCH chunks."""
+        order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
+        row_seg = pair_seg[order][ptr[:-1]].contiguous()
+        if folded is None:
+            Z, side = self._compose_for(features), None
+            rows = self._fitted_rows(uniq, exclude_seen)
+        else:
+            side = self._joint_side(features, folded)
+            Z, rows = side["Z"], self._joint_rows(uniq, exclude_seen, folded)
+        above, ncand, score = self._rank_chunks(rows, ptr, ptr_h, is_[order].contiguous(), Z,
+                                                seg=(elig.table, row_seg), side=side)
+        return self._rank_outputs(above, ncand, counts, score, inv)
 
     # ------------------------------------------------------------ deep lists
     def _deep_chunks(self, B: int, N: int, rows, items: dict, allow: Optional[torch.Tensor], after):

@@ -12,7 +12,7 @@ import torch
 
 from . import layout
 from .containers import _SideDev
-from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, FoldedItems
+from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, FoldedItems, ItemEligibility, pack_words
 
 
 def host_features(features):
@@ -356,6 +356,107 @@ def allowed_mask(filters, n_total: int) -> np.ndarray:
         else:
             mask[block] = False
     return mask
+
+
+ELIGIBILITY_MAX_ATTRS = 256     # 32 ALS_ELIGIBILITY_MAX_TAG_WORDS
+ELIGIBILITY_RULES = ("need_all", "need_any", "forbid")
+
+
+def _host(x):
+    return np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x)
+
+
+def _tag_words(x, rows: int, tw: Optional[int], name: str, row_kind: str, attrs: Optional[int] = None) -> np.ndarray:
+    """One of item_tags / a rule of `ALS.eligibility` -> int32 words [rows, tw]: bool [rows, A <= 256] is packed
+    (`pack_words`), uint32 / int32 [rows, tw <= 8] taken as the words.  `tw`: the width the tags fixed, None for the
+    tags themselves; `attrs`: the attribute count of boolean tags, which a boolean rule has to match."""
+    a = _host(x)
+    if a.ndim != 2 or a.shape[0] != rows:
+        raise ValueError(f"{name} must be a 2-D array with one row per {row_kind} ({rows}), got shape {a.shape}")
+    if a.dtype == np.bool_:
+        if not 1 <= a.shape[1] <= ELIGIBILITY_MAX_ATTRS:
+            raise ValueError(f"{name}: between 1 and {ELIGIBILITY_MAX_ATTRS} attributes, got {a.shape[1]}")
+        if attrs is not None and a.shape[1] != attrs:
+            raise ValueError(f"{name} has {a.shape[1]} attributes; item_tags has {attrs}")
+        w = pack_words(a)
+    elif a.dtype in (np.uint32, np.int32):
+        if not 1 <= a.shape[1] <= ELIGIBILITY_MAX_ATTRS // 32:
+            raise ValueError(f"{name}: between 1 and {ELIGIBILITY_MAX_ATTRS // 32} words per row, got {a.shape[1]}")
+        w = np.ascontiguousarray(a).view(np.int32)
+    else:
+        raise ValueError(f"{name} must be boolean [rows, attributes] or uint32 [rows, words], got dtype {a.dtype}")
+    if tw is not None and w.shape[1] != tw:
+        raise ValueError(f"{name} has {w.shape[1]} words of attribute bits per row; item_tags has {tw}")
+    return w
+
+
+def eligibility_inputs(segment_items, item_tags, rules, n_total: int, max_bytes: int):
+    """The table input of `ALS.eligibility` over a catalogue of n_total items: ("masks", bool [S, n_total]) from
+    `segment_items` (a bool array or S id lists), or ("tags", (tags, need_all, need_any, forbid)) - int32 words
+    [n_total, tw] and [S, tw], an absent rule None - from `item_tags` and `rules`.  Exactly one of the two; a table of
+    more than `max_bytes` (serving.ELIGIBILITY_MAX_BYTES) is refused before anything is built."""
+    if (segment_items is None) == (item_tags is None):
+        raise ValueError("give exactly one of segment_items and item_tags")
+
+    def check_size(S: int):
+        if S < 1:
+            raise ValueError("an eligibility table needs at least one segment")
+        need = S * ((n_total + 31) // 32) * 4
+        if need > max_bytes:
+            raise ValueError(f"the eligibility table of {S} segments over {n_total} items takes {need} bytes; "
+                             f"ELIGIBILITY_MAX_BYTES is {max_bytes}")
+
+    if segment_items is not None:
+        if rules is not None:
+            raise ValueError("rules go with item_tags, not with segment_items")
+        a = segment_items if isinstance(segment_items, (list, tuple)) else _host(segment_items)
+        if isinstance(a, np.ndarray) and a.dtype == np.bool_:
+            if a.ndim != 2 or a.shape[1] != n_total:
+                raise ValueError(f"segment_items as a boolean array must be [segments, {n_total}], got {a.shape}")
+            check_size(a.shape[0])
+            return "masks", a
+        check_size(len(a))
+        masks = np.zeros((len(a), n_total), dtype=bool)
+        for s, ids in enumerate(a):
+            ids = item_filter(ids, n_total, f"segment_items[{s}]")
+            masks[s] = ids if ids.dtype == np.bool_ else np.isin(np.arange(n_total), ids)
+        return "masks", masks
+    if not isinstance(rules, dict) or not rules or set(rules) - set(ELIGIBILITY_RULES):
+        raise ValueError(f"rules must be a dict with some of the keys {ELIGIBILITY_RULES}")
+    given = [r for r in ELIGIBILITY_RULES if rules.get(r) is not None]
+    if not given:
+        raise ValueError("rules holds no rule")
+    first, raw_tags = _host(rules[given[0]]), _host(item_tags)
+    S = first.shape[0] if first.ndim == 2 else 0
+    check_size(S)
+    tags = _tag_words(raw_tags, n_total, None, "item_tags", "item")
+    attrs = raw_tags.shape[1] if raw_tags.dtype == np.bool_ else None
+    words = [None if rules.get(r) is None else
+             _tag_words(rules[r], S, tags.shape[1], f"rules[{r!r}]", "segment", attrs) for r in ELIGIBILITY_RULES]
+    return "tags", (tags, *words)
+
+
+def eligibility_table(elig, n_total: int):
+    """The `eligibility=` argument of the *_eligible calls: an ItemEligibility over exactly the catalogue scored."""
+    if not isinstance(elig, ItemEligibility):
+        raise ValueError("eligibility must be an ItemEligibility (ALS.eligibility)")
+    if elig.n_items != n_total:
+        raise ValueError(f"the eligibility table spans {elig.n_items} items. Expected number of items: {n_total}.")
+    return elig
+
+
+def segment_ids(segments, rows: int, n_segments: int, what: str = "batch row") -> np.ndarray:
+    """`segments=` -> int32 [rows]: one id in [0, n_segments) per `what`."""
+    if segments is None:
+        raise ValueError("segments is required: one segment id per " + what)
+    s = _host(segments)
+    if s.ndim != 1 or (s.size and not np.issubdtype(s.dtype, np.integer)):
+        raise ValueError("segments must be a 1-D array of integer segment ids")
+    if s.size != rows:
+        raise ValueError(f"segments has {s.size} entries. Expected one per {what}: {rows}.")
+    if s.size and (s.min() < 0 or s.max() >= n_segments):
+        raise ValueError(f"segment ids must lie in [0, {n_segments})")
+    return s.astype(np.int32)
 
 
 def folded_items(model, folded) -> None:

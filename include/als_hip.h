@@ -529,6 +529,49 @@ int als_rank_count_masked(int k, int ld, int64_t n, const float* U, const float*
                           int32_t* n_cand, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Per-row eligibility: als_recommend_topk_masked / als_rank_count_masked with one allow bitmap PER BATCH ROW, picked
+ * from a table of segments ("this user's country / tier / age rating / language").
+ *   seg_allow: device table of nseg >= 1 bitmap rows, seg_stride_words (>= ceil(n / 32)) words apart; row s is an
+ *   allow bitmap as als_recommend_topk_masked reads it (item i = bit (i & 31) of word (i >> 5), bits >= n ignored).
+ *   row_seg [nusers] (als_rank_count_segmented: [nq]): the segment of every batch row - per row, not per user id, so a
+ *   user may appear under several segments in one call.  A row whose id is outside [0, nseg) has no candidates
+ *   (top_cnt 0 / n_cand 0); nothing is read for it.
+ *   Row b of the outputs equals, element for element, row b of als_recommend_topk_masked (als_rank_count_masked)
+ *   called with allow = seg_allow + row_seg[b] * seg_stride_words; every other argument, the slices and the
+ *   workspace (als_recommend_workspace_bytes / als_rank_count_workspace_bytes) are that call's.
+ * The whole catalogue is walked for every workgroup (its rows disagree about which chunks are empty); a wave none of
+ * whose 16 rows is allowed an item of a chunk of 32 skips the chunk's scores and selection.
+ * ------------------------------------------------------------------------- */
+int als_recommend_topk_segmented(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                                 const float* Z, const float* b_u, const float* b_i, const double* mu,
+                                 const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* seg_allow,
+                                 int64_t nseg, int64_t seg_stride_words, const int32_t* row_seg, int topn, int nslices,
+                                 float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int als_rank_count_segmented(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
+                             const float* b_i, const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx,
+                             const uint32_t* seg_allow, int64_t nseg, int64_t seg_stride_words, const int32_t* row_seg,
+                             int64_t nq, const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items,
+                             int64_t nt, int nslices, float* t_score, int32_t* above, int32_t* n_cand,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The eligibility table from item attributes: out [nseg][W], W = ceil(n / 32), dense rows (seg_stride_words = W).
+ *   item_tags [n][tw]: 1 <= tw <= ALS_ELIGIBILITY_MAX_TAG_WORDS words of attribute bits per item; need_all, need_any,
+ *   forbid [nseg][tw]: the rule of every segment (NULL = all zero); base_allow: an allow bitmap over the n items ANDed
+ *   into every segment, or NULL.  With t = item_tags[i] and the rule words of segment s:
+ *     eligible(s, i) = (t & forbid) == 0 in every word  &&  (t & need_all) == need_all in every word
+ *                      &&  (need_any is all zero  ||  (t & need_any) != 0 in some word)  &&  bit i of base_allow.
+ *   Bit (i & 31) of out[s][i >> 5] = eligible(s, i); the bits >= n of the last word are written 0.
+ * item_tags is read once (one lane per item keeps its words and loops over the segments).  n < 2^31; nseg == 0 is a
+ * no-op; tw outside its range: ALS_E_BADARG.
+ * ------------------------------------------------------------------------- */
+#define ALS_ELIGIBILITY_MAX_TAG_WORDS 8
+int als_eligibility_bitmaps(int64_t n, int tw, const uint32_t* item_tags, int64_t nseg, const uint32_t* need_all,
+                            const uint32_t* need_any, const uint32_t* forbid, const uint32_t* base_allow,
+                            uint32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user
  * half-step (scripts/als.py:411-433) for new rows.  For every row r < nrows of the CSR (indptr [nrows+1] /
  * indices / vals: device, column indices in [0, n), unique and ascending within a row), with S its items, n_r = |S|:

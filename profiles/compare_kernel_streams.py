@@ -1,12 +1,16 @@
-"""Compare the gfx950 instruction streams of the k_recommend instantiations of two builds of recommend.hip.
+"""Compare the gfx950 instruction streams of the k_recommend / k_rank_count instantiations of two builds of
+recommend.hip or rank_eval.hip.
 
     python profiles/compare_kernel_streams.py OLD/recommend.o NEW/recommend.o
+    python profiles/compare_kernel_streams.py OLD/rank_eval.o NEW/rank_eval.o
 
 Both objects are taken apart with llvm-objdump (--offloading, then -d on the gfx950 code object).  A kernel is keyed
-by its template arguments (KB, NW, CAP, MASKED) - the mangled names differ between the builds when a template or a
-function parameter was added -, and two kernels are equal when their instructions AND their encodings are, line by
-line (addresses dropped).  Instantiations with a fifth argument set (DEEP) are new and only counted.  Exit status 1
-when a kernel that both builds have differs.  (DESIGN.md section 26 records the outcome for als_recommend_deep.)"""
+by its name and template arguments (k_recommend: KB, NW, CAP, MASKED, DEEP, SEG; k_rank_count: KB, NW, MASKED, SEG)
+with trailing zeros dropped - the mangled names differ between the builds when a template or a function parameter
+was added, and a flag that did not exist is a flag that is off -, and two kernels are equal when their instructions
+AND their encodings are, line by line (addresses dropped).  Keys only the new build has are new and only counted.
+Exit status 1 when a kernel that both builds have differs.  (DESIGN.md sections 26 and 27 record the outcomes for
+als_recommend_deep and als_recommend_topk_segmented.)"""
 import os
 import re
 import shutil
@@ -15,11 +19,11 @@ import sys
 import tempfile
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-NAME = re.compile(r"k_recommendILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E(?:Lb([01])E)?E")
+NAME = re.compile(r"(k_recommend|k_rank_count)I((?:L[ib]\d+E)+)E")
 
 
 def kernels(obj):
-    """{(KB, NW, CAP, MASKED, DEEP): [(instruction, encoding), ...]} of the k_recommend kernels in `obj`."""
+    """{(name, template arguments without trailing zeros): [(instruction, encoding), ...]} of the kernels in `obj`."""
     out, cur = {}, None
     with tempfile.TemporaryDirectory() as work:
         shutil.copy(obj, os.path.join(work, "in.o"))
@@ -33,7 +37,10 @@ def kernels(obj):
                     m = NAME.search(line)
                     cur = None
                     if m and line.rstrip().endswith(">:"):
-                        cur = tuple(int(g or 0) for g in m.groups())
+                        args = [int(g) for g in re.findall(r"L[ib](\d+)E", m.group(2))]
+                        while args and args[-1] == 0:
+                            args.pop()
+                        cur = (m.group(1), *args)
                         out[cur] = []
                     continue
                 if cur is not None and "//" in line:
@@ -46,7 +53,7 @@ def kernels(obj):
 
 def main(old, new):
     a, b = kernels(old), kernels(new)
-    fresh = [k for k in b if k[4]]
+    fresh = [k for k in b if k not in a]
     same = differ = 0
     for key in sorted(a):
         if key not in b:
@@ -57,7 +64,7 @@ def main(old, new):
             differ += 1
         else:
             same += 1
-    print(f"{len(a)} kernels in the old build, {len(b)} in the new ({len(fresh)} DEEP); {same} identical, "
+    print(f"{len(a)} kernels in the old build, {len(b)} in the new ({len(fresh)} new); {same} identical, "
           f"{differ} not; {sum(len(v) for v in a.values())} instructions compared")
     return 1 if differ or not a else 0
 
