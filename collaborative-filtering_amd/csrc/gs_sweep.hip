@@ -298,6 +298,78 @@ __device__ unsigned long long g_gs_stamps[8];
 #define GS_STAMP(slot) do { } while (0)
 #endif
 
+// s_memtime ticks at the shader clock (~2.2 GHz measured, profiles/r03_placed_sweep.txt), not at 100 MHz as
+// rounds 1-2 assumed: 2^22 ticks were 1.9 ms - enough for a resident launch, but a spurious "not resident" as soon
+// as anything else holds compute units for a moment.  2^27 ticks = ~60 ms.
+constexpr unsigned long long GS_SPIN_LIMIT = 1ull << 27;
+
+// One batch of dependency rows of the dataflow sweep: the (up to GB) neighbours flagged in `m` (lanes of the chunk
+// whose index / weight are sj_l / sv_l), summed in ascending position order into gp.  The rows come from the
+// publication buffer, whose every word is the sentinel until its producer has stored it: data and "ready" travel in
+// the same 4-byte word, one round trip, no flag, no ordering between words needed.
+// WAIT = false: a batch whose words are not all there yet is left alone (-> false: the caller comes back to it
+// after the ready ones); WAIT = true: polls until they are, bounded by GS_SPIN_LIMIT (a timeout anywhere is sticky).
+// (Two instantiations called one after the other, nothing carried between them but a bit per batch.  As one loop
+// over two rounds that cleared the mask of every finished batch, the k > 128 kernels were WRONG: there the compiler
+// did not unroll the round loop ("loop not unrolled") and kept the eight masks as one vector-register tuple, and an
+// item with 21 dependencies among the 24 neighbours of its third chunk got the first batch of that chunk added
+// twice - image and stream form alike, with and without the pre-pass, every run: tests/test_gpu_gs_sweep.py,
+// k = 144, 150, 160.)
+template <int KB, bool WAIT>
+__device__ __forceinline__ bool gs_dep_batch(unsigned long long m, int sj_l, float sv_l, int ld, const float* pub,
+                                             const int (&col)[KCfg<KB>::NR], int lane, int32_t* err, bool& bail,
+                                             float (&gp)[KCfg<KB>::NR]) {
+    constexpr int NR = KCfg<KB>::NR;
+    constexpr int GB = (NR == 1) ? 16 : 8;
+    float w[GB], v[GB][NR];
+    int64_t off[GB];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+        const int src = m ? (int)__builtin_ctzll(m) : 0;
+        w[u] = m ? __shfl(sv_l, src, 64) : 0.f;
+        off[u] = m ? (int64_t)__shfl(sj_l, src, 64) * ld : -1;
+        if (m) m &= m - 1;
+    }
+    bool rdy = true;
+#pragma unroll
+    for (int u = 0; u < GB; ++u)
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) {
+            v[u][rr] = (off[u] >= 0) ? ld_agent(pub + off[u] + col[rr]) : 0.f;
+            rdy = rdy && (__float_as_uint(v[u][rr]) != GS_SENTINEL);
+        }
+    if (!bail && !__all(rdy)) {
+        if constexpr (!WAIT) {
+            return false;
+        } else {
+            const unsigned long long tstart = __builtin_amdgcn_s_memtime();
+            bail = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            while (!bail && !__all(rdy)) {
+                __builtin_amdgcn_s_sleep(1);
+                rdy = true;
+#pragma unroll
+                for (int u = 0; u < GB; ++u)
+#pragma unroll
+                    for (int rr = 0; rr < NR; ++rr) {
+                        if (off[u] >= 0 && __float_as_uint(v[u][rr]) == GS_SENTINEL)
+                            v[u][rr] = ld_agent(pub + off[u] + col[rr]);
+                        rdy = rdy && (__float_as_uint(v[u][rr]) != GS_SENTINEL);
+                    }
+                if (__builtin_amdgcn_s_memtime() - tstart > GS_SPIN_LIMIT ||
+                    __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+                    if (lane == 0) atomicExch(err, 1);
+                    bail = true;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < GB; ++u)
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) gp[rr] = fmaf(w[u], v[u][rr], gp[rr]);
+    return true;
+}
+
 // k <= 64: factor column in registers, 4 waves per workgroup.  k > 64, two forms:
 //   image  (STREAM = false) one wave per workgroup, the item's factor staged as a [KP][KP+1] LDS image before
 //          the waits - shortest hop (chain-bound sweeps), but 67 KB per wave leave 2 waves per CU;
@@ -321,10 +393,6 @@ void k_gs_dataflow(const als_gs_sweep_params P, const int32_t* __restrict__ Sw, 
     using D = DfCfg<KB, STREAM>;
     constexpr int LD = D::LD;
     constexpr bool IMAGE = D::IMAGE;
-    // s_memtime ticks at the shader clock (~2.2 GHz measured, profiles/r03_placed_sweep.txt), not at 100 MHz as
-    // rounds 1-2 assumed: 2^22 ticks were 1.9 ms - enough for a resident launch, but a spurious "not resident" as soon
-    // as anything else holds compute units for a moment.  2^27 ticks = ~60 ms.
-    constexpr unsigned long long SPIN_LIMIT = 1ull << 27;
     __shared__ float lds_img[D::IMG];
     float* Al = lds_img;
     float* vec = lds_img + (IMAGE ? KP * LD : 0);
@@ -447,61 +515,15 @@ void k_gs_dataflow(const als_gs_sweep_params P, const int32_t* __restrict__ Sw, 
                     for (int rr = 0; rr < NR; ++rr) gp[bb][rr] = 0.f;
                 }
                 bool bail = false;
+                unsigned later = 0;                                   // batches not ready yet: after the ready ones
 #pragma unroll
-                for (int round = 0; round < 2; ++round) {
+                for (int bb = 0; bb < NB; ++bb)
+                    if (bm[bb] != 0 && !gs_dep_batch<KB, false>(bm[bb], sj_l, sv_l, P.ld, pub, col, lane, err, bail, gp[bb]))
+                        later |= 1u << bb;
 #pragma unroll
-                    for (int bb = 0; bb < NB; ++bb) {
-                        if (bm[bb] == 0) continue;
-                        // The rows of this batch come from the publication buffer, whose every word is the
-                        // sentinel until its producer has stored it: data and "ready" travel in the same
-                        // 4-byte word, one round trip, no flag, no ordering between words needed.
-                        unsigned long long m = bm[bb];
-                        float w[GB], v[GB][NR];
-                        int64_t off[GB];
-#pragma unroll
-                        for (int u = 0; u < GB; ++u) {
-                            const int src = m ? (int)__builtin_ctzll(m) : 0;
-                            w[u] = m ? __shfl(sv_l, src, 64) : 0.f;
-                            off[u] = m ? (int64_t)__shfl(sj_l, src, 64) * P.ld : -1;
-                            if (m) m &= m - 1;
-                        }
-                        bool rdy = true;
-#pragma unroll
-                        for (int u = 0; u < GB; ++u)
-#pragma unroll
-                            for (int rr = 0; rr < NR; ++rr) {
-                                v[u][rr] = (off[u] >= 0) ? ld_agent(pub + off[u] + col[rr]) : 0.f;
-                                rdy = rdy && (__float_as_uint(v[u][rr]) != GS_SENTINEL);
-                            }
-                        if (!bail && !__all(rdy)) {
-                            if (round == 0) continue;                 // not ready yet: after the ready ones
-                            const unsigned long long tstart = __builtin_amdgcn_s_memtime();
-                            bail = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-                            while (!bail && !__all(rdy)) {            // a timeout anywhere is sticky
-                                __builtin_amdgcn_s_sleep(1);
-                                rdy = true;
-#pragma unroll
-                                for (int u = 0; u < GB; ++u)
-#pragma unroll
-                                    for (int rr = 0; rr < NR; ++rr) {
-                                        if (off[u] >= 0 && __float_as_uint(v[u][rr]) == GS_SENTINEL)
-                                            v[u][rr] = ld_agent(pub + off[u] + col[rr]);
-                                        rdy = rdy && (__float_as_uint(v[u][rr]) != GS_SENTINEL);
-                                    }
-                                if (__builtin_amdgcn_s_memtime() - tstart > SPIN_LIMIT ||
-                                    __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                                    if (lane == 0) atomicExch(err, 1);
-                                    bail = true;
-                                }
-                            }
-                        }
-                        bm[bb] = 0;
-#pragma unroll
-                        for (int u = 0; u < GB; ++u)
-#pragma unroll
-                            for (int rr = 0; rr < NR; ++rr) gp[bb][rr] = fmaf(w[u], v[u][rr], gp[bb][rr]);
-                    }
-                }
+                for (int bb = 0; bb < NB; ++bb)
+                    if (later & (1u << bb))
+                        gs_dep_batch<KB, true>(bm[bb], sj_l, sv_l, P.ld, pub, col, lane, err, bail, gp[bb]);
 #pragma unroll
                 for (int bb = 0; bb < NB; ++bb)
 #pragma unroll

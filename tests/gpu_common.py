@@ -176,6 +176,68 @@ def csr_rows(lengths, ncols, seed, weights=False):
 
 
 # ------------------------------------------------------------------------------------------ launches
+class GsSweep:
+    """One case of tests/gs_sweep_ref.py on the device, ready to be swept: the by-products come from als_row_solve in
+    factor mode (f64: as doubles, from the fp64 kernel), V and the biases hold the case's values on entry, `kw` is what
+    be.gs_level / gs_levels / gs_dataflow take (`stat`: with the fused residual statistics)."""
+
+    def __init__(self, E, case, f64=False, stat=True):
+        torch, dev, be = E.torch, E.dev, E.be
+        k, ld, n = case.k, case.ld, case.n
+        ft = torch.float64 if f64 else torch.float32
+        side = E.layout.SparseSide(n, case.m, case.indptr, case.indices, case.vals)
+        t = E.layout.build_row_tasks(side.indptr)
+        sd = E.side_dev(side, dev)
+        self.factor = torch.zeros(n * ld * ld, dtype=ft, device=dev)
+        rhs, cs = torch.zeros(n, ld, dtype=ft, device=dev), torch.zeros(n, ld, dtype=ft, device=dev)
+        sumr, sumr2 = torch.zeros(n, dtype=ft, device=dev), torch.zeros(n, dtype=ft, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(t.nslots, 1) * be.slot_bytes(k, f64) // 4, dtype=torch.float32, device=dev)
+        be.row_solve(k=k, ld=ld, side=sd, F=upload(pad(case.U, ld, 1), dev), zero_row=case.m,
+                     bias_self=upload(case.b_i, dev), bias_other=upload(case.b_u, dev),
+                     mu=torch.tensor([case.mu], dtype=torch.float64, device=dev), lam=0.0,
+                     lam_row=upload(case.lam_row, dev), lam_b=case.lam_b, lam_b_row=None, rhs_extra=None,
+                     diag_extra=upload(case.diag_extra, dev), X_out=None, bias_out=None, gram_out=None,
+                     factor_out=self.factor, rhs_out=rhs, colsum_out=cs, sumr_out=sumr, sumr2_out=sumr2,
+                     status=status, tasks=E.tasks_dev(t, dev), workspace=ws, f64=f64)
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0
+        self.torch, self.be, self.case = torch, be, case
+        self.V, self.bias = upload(case.V_pad(), dev), upload(case.b_i.copy(), dev)
+        self.stat = torch.full((n, 2), 7.0, dtype=torch.float32, device=dev) if stat else None
+        self.items = upload(case.sched.items, dev)
+        self.offsets = np.ascontiguousarray(case.sched.offsets, dtype=np.int64)
+        self.wait = upload(case.wait, dev)
+        self.kw = dict(k=k, ld=ld, S_ptr=upload(case.S_ptr, dev), S_idx=upload(case.S_idx, dev),
+                       S_val=upload(case.S_val, dev), alpha=case.alpha, factor=self.factor, rhs=rhs, colsum=cs,
+                       sumr=sumr, indptr=sd.indptr, lam_b=case.lam_b, lam_b_row=None, V=self.V, bias=self.bias)
+        if stat:
+            self.kw.update(sumr2=sumr2, lambda_eff=upload(case.lambda_eff, dev), stat_out=self.stat)
+        if f64:
+            self.kw["f64"] = True
+
+    def levels(self):
+        self.be.gs_levels(offsets=self.offsets, items=self.items, **self.kw)
+        return self.fetch()
+
+    def level_by_level(self):
+        for lo, hi in zip(self.offsets[:-1], self.offsets[1:]):
+            self.be.gs_level(items=self.items[int(lo): int(hi)], **self.kw)
+        return self.fetch()
+
+    def dataflow(self, publish, nondep=None):
+        """The whole schedule in its own order; -> (V, bias, stat) after asserting that no wait timed out."""
+        err = self.torch.zeros(1, dtype=self.torch.int32, device=self.V.device)
+        self.be.gs_dataflow(items=self.items, S_idx_wait=self.wait, publish=publish, err=err, nondep=nondep, **self.kw)
+        out = self.fetch()
+        assert int(err.item()) == 0, "a dependency wait of the dataflow sweep timed out"
+        return out
+
+    def fetch(self):
+        self.torch.cuda.synchronize()
+        return (self.V.cpu().numpy(), self.bias.cpu().numpy(), None if self.stat is None else self.stat.cpu().numpy())
+
+
 def predict_dense(torch, be, f, m, n, dev):
     """als_predict_dense on the first m users and n items of `factors`."""
     out = torch.empty(m, n, dtype=torch.float32, device=dev)
