@@ -31,6 +31,11 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_recommend_deep_workspace_bytes", "als_recommend_deep",
            "als_recommend_topk_segmented", "als_rank_count_segmented", "als_eligibility_bitmaps")
 
+# the workspace queries: they return size_t, everything else but the two slot-size queries an int status / value
+SIZE_QUERIES = ("als_spd_solve_workspace_bytes", "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
+                "als_similar_workspace_bytes", "als_audience_workspace_bytes", "als_group_workspace_bytes",
+                "als_explore_workspace_bytes", "als_recommend_deep_workspace_bytes")
+
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
@@ -220,18 +225,9 @@ def load():
     lib.als_host_row_tasks.argtypes = [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
     lib.als_host_level_schedule.argtypes = [_i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
     for name in EXPORTS:
-        if name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64", "als_spd_solve_workspace_bytes",
-                        "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
-                        "als_similar_workspace_bytes", "als_audience_workspace_bytes", "als_group_workspace_bytes",
-                        "als_explore_workspace_bytes", "als_recommend_deep_workspace_bytes"):
+        if name in SIZE_QUERIES:
+            getattr(lib, name).restype = C.c_size_t
+        elif name not in ("als_partial_slot_bytes", "als_partial_slot_bytes_f64"):      # int64 (above)
             getattr(lib, name).restype = C.c_int
-    lib.als_spd_solve_workspace_bytes.restype = C.c_size_t
-    lib.als_recommend_workspace_bytes.restype = C.c_size_t
-    lib.als_rank_count_workspace_bytes.restype = C.c_size_t
-    lib.als_similar_workspace_bytes.restype = C.c_size_t
-    lib.als_audience_workspace_bytes.restype = C.c_size_t
-    lib.als_group_workspace_bytes.restype = C.c_size_t
-    lib.als_explore_workspace_bytes.restype = C.c_size_t
-    lib.als_recommend_deep_workspace_bytes.restype = C.c_size_t
     _lib = lib
     return lib

@@ -48,14 +48,9 @@ class HipBackend:
         self._sumsq_partials = torch.empty(self.lib.als_sumsq_partials(), dtype=torch.float64,
                                            device=device)
         self._stats_partials: Optional[torch.Tensor] = None
-        self._spd_ws: Optional[torch.Tensor] = None
-        self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk
-        self._deep_ws: Optional[torch.Tensor] = None       # slice lists, running lists, ceilings of als_recommend_deep
-        self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count
-        self._sim_ws: Optional[torch.Tensor] = None        # slice lists of als_similar_topk
-        self._aud_ws: Optional[torch.Tensor] = None        # slice lists of als_audience_topk
-        self._grp_ws: Optional[torch.Tensor] = None        # slice lists of als_group_topk
-        self._exp_ws: Optional[torch.Tensor] = None        # slice lists of als_explore_topk
+        self._ws: dict = {}                # workspaces of the library calls by name (`_workspace`): uint8, grow-only
+        self._rec_ws: Optional[torch.Tensor] = None        # item-slice lists of als_recommend_topk* (`_recommend`)
+        self._rank_ws: Optional[torch.Tensor] = None       # item-slice counts of als_rank_count* (`_rank`)
         # operand scale of the f16x2 Gram ({S, 1 / S^2} of the gathered factor matrix + two working words that stay
         # zero between calls: als_factor_scale); one per backend - calls on one stream run in order
         self._fscale = torch.zeros(4, dtype=torch.float32, device=device)
@@ -100,6 +95,32 @@ class HipBackend:
     def _check(rc: int, what: str):
         if rc != 0:
             raise RuntimeError(f"{what} failed with status {rc} (see ALS_E_* in include/als_hip.h)")
+
+    def _workspace(self, name: str, need: int):
+        """Pointer to the workspace `name` of at least `need` bytes - owned here, grown when a call needs more, never
+        shrunk; None for need == 0 (the library then takes NULL)."""
+        if need <= 0:
+            return None
+        buf = self._ws.get(name)
+        if buf is None or buf.numel() < need:
+            buf = self._ws[name] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return _p(buf)
+
+    @staticmethod
+    def _seen(seen_ptr, seen_idx):
+        """The seen CSR as the library takes it: (None, None) when no row has an entry (and there is no storage to
+        point at)."""
+        if seen_idx is not None and seen_idx.numel() == 0:
+            return None, None
+        return _p(seen_ptr), _p(seen_idx)
+
+    def _bitmap(self, allow: Optional[torch.Tensor], n: int):
+        """Pointer to the allow bitmap of a call over n rows, checked; None allows every row (NULL).  The kernels
+        index the words by row: a short bitmap would be an out-of-bounds read."""
+        if allow is not None and (allow.dtype != torch.int32 or not allow.is_cuda or not allow.is_contiguous()
+                                  or allow.numel() < (n + 31) // 32):
+            raise ValueError(f"allow bitmap must be a contiguous int32 device tensor of {(n + 31) // 32} words")
+        return _p(allow)
 
     def slot_bytes(self, k: int, f64: bool = False) -> int:
         """Bytes of one partial slot of a split row (fp64 calls keep an fp64 image per segment)."""
@@ -239,11 +260,10 @@ class HipBackend:
         nbytes = int(self.lib.als_spd_solve_workspace_bytes(N))
         if nbytes == 0:
             raise ValueError(f"W-step system of order {N} exceeds ALS_SPD_MAX_N")
-        if self._spd_ws is None or self._spd_ws.numel() < nbytes:
-            self._spd_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         x = torch.empty(N, dtype=torch.float64, device=self.device)
-        self._check(self.lib.als_spd_solve_f64(N, _p(A), N, _p(b), float(diag_add), _p(x), _p(self._spd_ws),
-                                               _p(status), self._stream()), "als_spd_solve_f64")
+        self._check(self.lib.als_spd_solve_f64(N, _p(A), N, _p(b), float(diag_add), _p(x),
+                                               self._workspace("spd", nbytes), _p(status), self._stream()),
+                    "als_spd_solve_f64")
         return x
 
     # -- K6 ------------------------------------------------------------------
@@ -319,18 +339,15 @@ class HipBackend:
                               top_idx, top_cnt):
         """`recommend_topk` over the items of the bitmap `allow` (int32 [ceil(n / 32)], item i = bit i & 31 of word
         i >> 5): als_recommend_topk_masked."""
-        self._check_bitmap(allow, n)
-        self._recommend(self.lib.als_recommend_topk_masked, "als_recommend_topk_masked", (_p(allow),), k, ld, users,
-                        n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
-
-    def _check_bitmap(self, allow: torch.Tensor, n: int):
-        # the kernels index the words by item: a short bitmap would be an out-of-bounds read
-        if (allow.dtype != torch.int32 or not allow.is_cuda or not allow.is_contiguous()
-                or allow.numel() < (n + 31) // 32):
-            raise ValueError(f"allow bitmap must be a contiguous int32 device tensor of {(n + 31) // 32} words")
+        if allow is None:
+            raise ValueError("recommend_topk_masked needs an allow bitmap; recommend_topk is the call without one")
+        self._recommend(self.lib.als_recommend_topk_masked, "als_recommend_topk_masked", (self._bitmap(allow, n),), k,
+                        ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
 
     def _recommend(self, fn, what, allow, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val,
                    top_idx, top_cnt):
+        # the empty-seen rule and the workspace are written out here and in `_rank`, not taken from `_seen` /
+        # `_workspace`: these two serve the small-batch calls, where two more Python calls per call showed (DESIGN §28)
         if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
             seen_ptr = seen_idx = None
         nsl = self.recommend_slices()
@@ -347,21 +364,15 @@ class HipBackend:
         a cursor: als_recommend_deep.  after_key: None, or int64 [B] holding the bits of the 64-bit cursor keys
         (serving.cursor_keys); rounds: None or an int32 [1] device tensor that receives the scoring rounds that did work.
         The workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
-        if allow is not None:
-            self._check_bitmap(allow, n)
+        allow = self._bitmap(allow, n)
         if after_key is not None and (after_key.dtype != torch.int64 or not after_key.is_cuda
                                       or not after_key.is_contiguous() or after_key.numel() != users.numel()):
             raise ValueError("after_key must be a contiguous int64 device tensor with one key per batch row")
-        if seen_idx is not None and seen_idx.numel() == 0:
-            seen_ptr = seen_idx = None
-        nsl = self.recommend_slices()
         need = self.recommend_deep_workspace_bytes(users.numel(), n, topn)
-        if need > 0 and (self._deep_ws is None or self._deep_ws.numel() < need):
-            self._deep_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._check(self.lib.als_recommend_deep(
-            k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(seen_ptr), _p(seen_idx),
-            _p(allow), _p(after_key), topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt), _p(rounds),
-            _p(self._deep_ws) if need > 0 else None, need, self._stream()), "als_recommend_deep")
+            k, ld, users.numel(), _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), *self._seen(seen_ptr, seen_idx),
+            allow, _p(after_key), topn, self.recommend_slices(), _p(top_val), _p(top_idx), _p(top_cnt), _p(rounds),
+            self._workspace("recommend_deep", need), need, self._stream()), "als_recommend_deep")
 
     def recommend_deep_workspace_bytes(self, nusers: int, n: int, topn: int) -> int:
         """Bytes of workspace a `recommend_deep` call over `nusers` rows takes (als_recommend_deep_workspace_bytes
@@ -380,9 +391,10 @@ class HipBackend:
                           t_score, above, n_cand):
         """`rank_count` with the candidates limited to the bitmap `allow` (as `recommend_topk_masked`):
         als_rank_count_masked."""
-        self._check_bitmap(allow, n)
-        self._rank(self.lib.als_rank_count_masked, "als_rank_count_masked", (_p(allow),), k, ld, n, U, Z, b_u, b_i, mu,
-                   seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above, n_cand)
+        if allow is None:
+            raise ValueError("rank_count_masked needs an allow bitmap; rank_count is the call without one")
+        self._rank(self.lib.als_rank_count_masked, "als_rank_count_masked", (self._bitmap(allow, n),), k, ld, n, U, Z,
+                   b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items, t_score, above, n_cand)
 
     def _segment_args(self, seg_allow: torch.Tensor, row_seg: torch.Tensor, n: int, rows: int):
         # the kernels index the table by (segment, item word) and row_seg by batch row: anything short is an
@@ -421,10 +433,8 @@ class HipBackend:
         assert out.dtype == torch.int32 and out.is_contiguous() and out.shape[1] == (n + 31) // 32
         for r in (need_all, need_any, forbid):
             assert r is None or (r.dtype == torch.int32 and r.is_contiguous() and tuple(r.shape) == (S, tw))
-        if base_allow is not None:
-            self._check_bitmap(base_allow, n)
         self._check(self.lib.als_eligibility_bitmaps(n, tw, _p(item_tags), S, _p(need_all), _p(need_any), _p(forbid),
-                                                     _p(base_allow), _p(out), self._stream()),
+                                                     self._bitmap(base_allow, n), _p(out), self._stream()),
                     "als_eligibility_bitmaps")
 
     def _rank(self, fn, what, allow, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items,
@@ -519,16 +529,13 @@ class HipBackend:
         out (None: no exclusion), restricted to the bitmap `allow` (None: every row); q_inv / t_inv are the
         `row_inv_norms` of Q / T: als_similar_topk.  The slice workspace is owned here and grows as needed;
         ALS_RECOMMEND_SLICES applies."""
-        if allow is not None:
-            self._check_bitmap(allow, n)
+        allow = self._bitmap(allow, n)
         nq = q_ids.numel()
         nsl = self.recommend_slices()
         need = int(self.lib.als_similar_workspace_bytes(nq, n, topn, nsl))
-        if need > 0 and (self._sim_ws is None or self._sim_ws.numel() < need):
-            self._sim_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._check(self.lib.als_similar_topk(k, ld, nq, _p(q_ids), _p(Q), _p(q_inv), _p(self_ids), n, _p(T),
-                                              _p(t_inv), _p(allow), topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
-                                              _p(self._sim_ws) if need > 0 else None, need, self._stream()),
+                                              _p(t_inv), allow, topn, nsl, _p(top_val), _p(top_idx), _p(top_cnt),
+                                              self._workspace("similar", need), need, self._stream()),
                     "als_similar_topk")
 
     # -- K14 -------------------------------------------------------------------
@@ -537,18 +544,13 @@ class HipBackend:
         """Top-`topn` users of every query item q_ids[b] (int32, a row of Q / q_bias), the item's raters (CSR by
         ITEM id over user ids; None = none) left out, restricted to the user bitmap `allow` (None: every user):
         als_audience_topk.  The slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
-        if allow is not None:
-            self._check_bitmap(allow, m)
-        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
-            seen_ptr = seen_idx = None
+        allow = self._bitmap(allow, m)
         nq = q_ids.numel()
         nsl = self.recommend_slices()
         need = int(self.lib.als_audience_workspace_bytes(nq, m, topn, nsl))
-        if need > 0 and (self._aud_ws is None or self._aud_ws.numel() < need):
-            self._aud_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._check(self.lib.als_audience_topk(k, ld, nq, _p(q_ids), _p(Q), _p(q_bias), m, _p(U), _p(b_u), _p(mu),
-                                               _p(seen_ptr), _p(seen_idx), _p(allow), topn, nsl, _p(top_val),
-                                               _p(top_idx), _p(top_cnt), _p(self._aud_ws) if need > 0 else None, need,
+                                               *self._seen(seen_ptr, seen_idx), allow, topn, nsl, _p(top_val),
+                                               _p(top_idx), _p(top_cnt), self._workspace("audience", need), need,
                                                self._stream()), "als_audience_topk")
 
     # -- K15 -------------------------------------------------------------------
@@ -561,20 +563,15 @@ class HipBackend:
         "min", "max") of the members' scores, the items of row b of the seen CSR (indexed by BATCH GROUP; None =
         none) are left out, restricted to the item bitmap `allow` (None: every item): als_group_topk.  The slice
         workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES applies."""
-        if allow is not None:
-            self._check_bitmap(allow, n)
-        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
-            seen_ptr = seen_idx = None
+        allow = self._bitmap(allow, n)
         ng = g_ptr.numel() - 1
         nsl = self.recommend_slices()
         need = int(self.lib.als_group_workspace_bytes(ng, n, topn, nsl))
-        if need > 0 and (self._grp_ws is None or self._grp_ws.numel() < need):
-            self._grp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._check(self.lib.als_group_topk(k, ld, ng, _p(g_ptr), _p(g_users), int(max_members), n, _p(U), _p(Z),
-                                            _p(b_u), _p(b_i), _p(mu), _p(seen_ptr), _p(seen_idx), _p(allow),
+                                            _p(b_u), _p(b_i), _p(mu), *self._seen(seen_ptr, seen_idx), allow,
                                             self.GROUP_AGGREGATES[aggregate], topn, nsl, _p(top_val), _p(top_idx),
-                                            _p(top_cnt), _p(self._grp_ws) if need > 0 else None, need,
-                                            self._stream()), "als_group_topk")
+                                            _p(top_cnt), self._workspace("group", need), need, self._stream()),
+                    "als_group_topk")
 
     # -- K16 -------------------------------------------------------------------
     def row_whitener(self, *, k, ld, indptr, indices, rows, n, Z, lam_u, W_out, status):
@@ -592,20 +589,15 @@ class HipBackend:
         [B, ld, ld] by batch row (`row_whitener`); top_lev fp32 [B, topn] receives the leverages of the returned
         items: als_explore_topk.  The slice workspace is owned here and grows as needed; ALS_RECOMMEND_SLICES
         applies."""
-        if allow is not None:
-            self._check_bitmap(allow, n)
-        if seen_idx is not None and seen_idx.numel() == 0:      # every row empty (and no storage to point at)
-            seen_ptr = seen_idx = None
+        allow = self._bitmap(allow, n)
         B = users.numel()
         assert W.is_contiguous() and W.shape[1:] == (ld, ld) and W.shape[0] >= B
         nsl = self.recommend_slices()
         need = int(self.lib.als_explore_workspace_bytes(k, B, n, topn, nsl))
-        if need > 0 and (self._exp_ws is None or self._exp_ws.numel() < need):
-            self._exp_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._check(self.lib.als_explore_topk(k, ld, B, _p(users), n, _p(U), _p(Z), _p(b_u), _p(b_i), _p(mu), _p(W),
-                                              float(beta), _p(seen_ptr), _p(seen_idx), _p(allow), topn, nsl,
+                                              float(beta), *self._seen(seen_ptr, seen_idx), allow, topn, nsl,
                                               _p(top_val), _p(top_idx), _p(top_cnt), _p(top_lev),
-                                              _p(self._exp_ws) if need > 0 else None, need, self._stream()),
+                                              self._workspace("explore", need), need, self._stream()),
                     "als_explore_topk")
 
     # -- K17 -------------------------------------------------------------------

@@ -18,7 +18,8 @@
 // tests/test_gpu_audience.py compares every score with als_predict_dense's output with ==.  This layout ships because
 // it keeps k_similar's epilogue (per-row state in the q group, per-column values in lane c) unchanged.
 //
-// Exclusion is k_recommend's (recommend.hip), written here a third time because that file stays as it is: each query
+// Exclusion is k_recommend's (recommend.hip), written here a third time - the body of the walk is not shared, only
+// its lower-bound search (walk::lower_bound; catalogue_walk.hpp and DESIGN sections 19 and 28 say why): each query
 // row keeps a cursor into the ascending rater list of ITS ITEM (seen_ptr is indexed by q_ids[b]) and the next rater;
 // only a block that reaches that rater builds a 16-bit mask (one coalesced load of the next 16 entries by the row's
 // 16 lanes and an OR-reduction).  A slice starts with a lower-bound search for lo.  One addition: when a whole
@@ -34,6 +35,7 @@
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 #include "topk_rows.hpp"
 
 namespace {
@@ -41,17 +43,6 @@ namespace {
 using topk::make_key;
 
 constexpr int AU_CHUNK = walk::CHUNK;
-constexpr int AU_WIDE = 64;         // queries per workgroup, topn > 32: 4 waves, 256 keys per query (list 128)
-constexpr int AU_NARROW = 128;      // queries per workgroup, topn <= 32: 8 waves, 128 keys per query (list 32)
-
-// first position in [a, e) of the ascending list whose entry is >= bound
-__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ idx, int64_t a, int64_t e, int64_t bound) {
-    while (a < e) {
-        const int64_t mid = a + ((e - a) >> 1);
-        if (idx[mid] < bound) a = mid + 1; else e = mid;
-    }
-    return a;
-}
 
 // CAP keys per query: list [0, L) + survivor buffer [L, CAP)
 template <int KB, int NW, int CAP, bool MASKED>
@@ -91,7 +82,7 @@ void k_audience(int ld, int64_t nq, const int32_t* __restrict__ q_ids, const flo
         cur[r] = end[r] = 0;
         if (seen_ptr && valid[r]) {
             end[r] = seen_ptr[i + 1];
-            cur[r] = lower_bound(seen_idx, seen_ptr[i], end[r], lo);     // first rater >= lo
+            cur[r] = walk::lower_bound(seen_idx, seen_ptr[i], end[r], lo);     // first rater >= lo
         }
         nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
     }
@@ -127,7 +118,7 @@ void k_audience(int ld, int64_t nq, const int32_t* __restrict__ q_ids, const flo
                     if constexpr (MASKED) {
                         // all 16 below the block: the cursor fell behind over unscored chunks - jump, do not walk
                         const int last = __shfl(s, (lane & 48) | 15, 64);
-                        if (more && last < cb) cur[r] = lower_bound(seen_idx, cur[r], end[r], cb);
+                        if (more && last < cb) cur[r] = walk::lower_bound(seen_idx, cur[r], end[r], cb);
                     }
                 }
                 if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
@@ -199,36 +190,22 @@ void k_audience(int ld, int64_t nq, const int32_t* __restrict__ q_ids, const flo
         topk::finish_row<CAP>(kw, st, R, topn, lane, b0 + R, nq, (int64_t)blockIdx.y, part, top_val, top_idx, top_cnt);
 }
 
-int aud_slices(int64_t nq, int64_t m, int topn, int nslices) {
-    return walk::plan_slices(nq, topn <= 32 ? AU_NARROW : AU_WIDE, m, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
-
 template <int KB>
 int launch_audience(int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_bias, int64_t m, int nsl,
                     const float* U, const float* b_u, const double* mu, const int64_t* seen_ptr,
                     const int32_t* seen_idx, const uint32_t* allow, int topn, float* tv, int32_t* ti, int32_t* tc,
                     unsigned long long* part, hipStream_t st) {
-    const int64_t slice = walk::slice_items(m, nsl);
-    if (topn <= 32) {
-        const dim3 grid((unsigned)((nq + AU_NARROW - 1) / AU_NARROW), (unsigned)nsl);
-        auto kern = allow ? k_audience<KB, AU_NARROW / 16, 128, true> : k_audience<KB, AU_NARROW / 16, 128, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(AU_NARROW * 4), 0, st, ld, nq, q_ids, Q, q_bias, m, slice, U, b_u, mu,
-                           seen_ptr, seen_idx, allow, topn, tv, ti, tc, part);
-    } else {
-        const dim3 grid((unsigned)((nq + AU_WIDE - 1) / AU_WIDE), (unsigned)nsl);
-        auto kern = allow ? k_audience<KB, AU_WIDE / 16, 256, true> : k_audience<KB, AU_WIDE / 16, 256, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(AU_WIDE * 4), 0, st, ld, nq, q_ids, Q, q_bias, m, slice, U, b_u, mu,
-                           seen_ptr, seen_idx, allow, topn, tv, ti, tc, part);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    constexpr int NN = topk::ROWS_NARROW / 16, NWD = topk::ROWS_WIDE / 16;
+    return topk::launch_by_width(allow ? k_audience<KB, NN, 128, true> : k_audience<KB, NN, 128, false>,
+                                 allow ? k_audience<KB, NWD, 256, true> : k_audience<KB, NWD, 256, false>, topn, nq, nsl,
+                                 st, ld, nq, q_ids, Q, q_bias, m, walk::slice_items(m, nsl), U, b_u, mu, seen_ptr,
+                                 seen_idx, allow, topn, tv, ti, tc, part);
 }
 
 }  // namespace
 
 extern "C" size_t als_audience_workspace_bytes(int64_t nq, int64_t m, int topn, int nslices) {
-    if (nq <= 0 || m <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
-    const int s = aud_slices(nq, m, topn, nslices);
-    return s > 1 ? (size_t)s * (size_t)nq * (size_t)topn * sizeof(unsigned long long) : 0;
+    return topk::workspace_bytes(nq, topk::rows_per_wg(topn), m, topn, nslices);
 }
 
 extern "C" int als_audience_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_bias,
@@ -236,24 +213,17 @@ extern "C" int als_audience_topk(int k, int ld, int64_t nq, const int32_t* q_ids
                                  const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, int topn,
                                  int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nq < 0 || m < 1 || m >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0 ||
-        nslices > ALS_RECOMMEND_MAX_SLICES)
-        return ALS_E_BADARG;
+    const int bad = topk::check_shape(k, ld, nq, m, topn, ALS_TOPK_MAX, nslices);
+    if (bad) return bad;
     if (nq == 0) return 0;
     if (!q_ids || !Q || !q_bias || !U || !b_u || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx))
         return ALS_E_BADARG;
-    const int nsl = aud_slices(nq, m, topn, nslices);
-    const size_t need = als_audience_workspace_bytes(nq, m, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    const topk::SlicePlan p = topk::plan(nq, topk::rows_per_wg(topn), m, nslices, nq * topn,
+                                         sizeof(unsigned long long), workspace, workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_audience<KB>(ld, nq, q_ids, Q, q_bias, m, nsl, U, b_u, mu, seen_ptr, seen_idx,
-                                                      allow, topn, top_val, top_idx, top_cnt, part, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(topk::k_merge_slices, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, nq, nsl, topn, part,
-                       top_val, top_idx, top_cnt);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_audience<KB>(ld, nq, q_ids, Q, q_bias, m, p.nsl, U, b_u, mu, seen_ptr, seen_idx,
+                                                      allow, topn, top_val, top_idx, top_cnt, p.keys(), st));
+    return rc != 0 ? rc : topk::merge_slices(p.nsl, p.keys(), nq, topn, top_val, top_idx, top_cnt, st);
 }

@@ -130,17 +130,6 @@ __device__ __forceinline__ float state_kl(const CalLds<MP>& lds, const float* __
     return kl[0];
 }
 
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 template <int MP>
 __global__ __launch_bounds__(64)
 void k_calibrated_rerank(int ncat, int ldc, int64_t nrows, int64_t n, const float* __restrict__ C,

@@ -1,6 +1,7 @@
-// What k_recommend (recommend.hip) and k_rank_count (rank_eval.hip) share of their walk over the catalogue - the chunk
-// size, the slice plan, the LDS row stride - and the epilogue of every kernel that forms a prediction (theirs,
-// k_predict_dense's and k_predict_at's in predict.hip).
+// What the kernels that walk the catalogue share of their walk - k_recommend (recommend.hip), k_rank_count
+// (rank_eval.hip), k_similar, k_audience, k_group, k_explore: the chunk size, the slice plan, the LDS row stride, the
+// lower-bound search of the seen cursors - and the epilogue of every kernel that forms a prediction (theirs,
+// k_predict_dense's and k_predict_at's in predict.hip).  The host side of their entry points is topk_launch.hpp.
 //
 // Only what compiles to the same instructions as before lives here.  The rest of the walk - Z prefetch / staging,
 // allow-bitmap scan, seen-cursor set-up, 16-entry exclusion walk, score tiles, candidate test, chunk loop - was moved
@@ -41,5 +42,16 @@ constexpr int lds_row_stride(int KB) { return 16 * KB + 4; }    // floats per st
 // ---- the epilogue of every kernel that forms a prediction from a dot product: this association, so that every score
 // is bitwise the value als_predict_dense writes
 __device__ __forceinline__ float score(float dot, float mu, float bu, float bi) { return dot + mu + bu + bi; }
+
+// ---- first position in [a, e) of the ascending list whose entry is >= bound: where a seen cursor starts in a slice,
+// and where it jumps to after chunks that were not scored (k_audience, k_group, k_explore; k_recommend and
+// k_rank_count keep the search written out in their cursor set-up)
+__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ idx, int64_t a, int64_t e, int64_t bound) {
+    while (a < e) {
+        const int64_t mid = a + ((e - a) >> 1);
+        if (idx[mid] < bound) a = mid + 1; else e = mid;
+    }
+    return a;
+}
 
 }  // namespace walk

@@ -118,17 +118,6 @@ __device__ __forceinline__ float list_ild(const PoolLds<MP>& lds, int len, int l
     return len < 2 ? __int_as_float(0x7FC00000) : (float)(tot / (0.5 * (double)len * (double)(len - 1)));
 }
 
-__device__ __forceinline__ float wave_min_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // one row of als_mmr_rerank
 template <int KB, int MP>
 __device__ __forceinline__ void mmr_row(PoolLds<MP>& lds, int64_t row, int lane, int ld, int64_t n,

@@ -37,6 +37,7 @@
 #include "catalogue_walk.hpp"
 #include "row_f64_common.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 #include "topk_rows.hpp"
 
 namespace {
@@ -197,15 +198,6 @@ __device__ __forceinline__ float explore_key(float base, float beta, float lev) 
     return base + t;
 }
 
-// first position in [a, e) of the ascending list whose entry is >= bound
-__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ idx, int64_t a, int64_t e, int64_t bound) {
-    while (a < e) {
-        const int64_t mid = a + ((e - a) >> 1);
-        if (idx[mid] < bound) a = mid + 1; else e = mid;
-    }
-    return a;
-}
-
 // CAP keys per row: list [0, L) + survivor buffer [L, CAP)
 template <int KB, int CAP, bool MASKED>
 __global__ __launch_bounds__(ex_nw(KB) * 64)
@@ -252,7 +244,7 @@ void k_explore(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_
     int64_t cur = 0, end = 0;
     if (seen_ptr && active) {
         end = seen_ptr[u + 1];
-        cur = lower_bound(seen_idx, seen_ptr[u], end, lo);                // first seen item >= lo
+        cur = walk::lower_bound(seen_idx, seen_ptr[u], end, lo);                // first seen item >= lo
     }
     int nxt = cur < end ? seen_idx[cur] : INT32_MAX;
 
@@ -299,7 +291,7 @@ void k_explore(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_
                 if constexpr (MASKED) {
                     // all 64 below the chunk: the cursor fell behind over skipped chunks - jump, do not walk
                     const int last = __builtin_amdgcn_readlane(s, 63);
-                    if (more && last < it0) cur = lower_bound(seen_idx, cur, end, it0);
+                    if (more && last < it0) cur = walk::lower_bound(seen_idx, cur, end, it0);
                 }
             }
             nxt = cur < end ? seen_idx[cur] : INT32_MAX;
@@ -460,10 +452,10 @@ void k_explore_lev(int64_t n, const float* __restrict__ Z, const float* __restri
     }
 }
 
-int ex_slices(int kb, int64_t nusers, int64_t n, int nslices) {
+int ex_rows_per_wg(int kb) {            // one wave per batch row; kb = als_padded_k(k) / 16
     static constexpr int nw[11] = {0,        ex_nw(1), ex_nw(2), ex_nw(3), ex_nw(4), ex_nw(5),
                                    ex_nw(6), ex_nw(7), ex_nw(8), ex_nw(9), ex_nw(10)};
-    return walk::plan_slices(nusers, nw[kb], n, nslices, ALS_RECOMMEND_MAX_SLICES);      // kb = als_padded_k(k) / 16
+    return nw[kb];
 }
 
 template <int KB>
@@ -502,9 +494,7 @@ extern "C" int als_row_whitener(int k, int ld, int64_t nrows, const int64_t* ind
 
 extern "C" size_t als_explore_workspace_bytes(int k, int64_t nusers, int64_t n, int topn, int nslices) {
     const int kp = als_padded_k(k);
-    if (kp < 0 || nusers <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
-    const int s = ex_slices(kp / 16, nusers, n, nslices);
-    return s > 1 ? (size_t)s * (size_t)nusers * (size_t)topn * sizeof(unsigned long long) : 0;
+    return kp < 0 ? 0 : topk::workspace_bytes(nusers, ex_rows_per_wg(kp / 16), n, topn, nslices);
 }
 
 extern "C" int als_explore_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
@@ -512,30 +502,23 @@ extern "C" int als_explore_topk(int k, int ld, int64_t nusers, const int32_t* us
                                 float beta, const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
                                 int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt,
                                 float* top_lev, void* workspace, size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
-        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES || !(beta == beta) || beta - beta != 0.f)
-        return ALS_E_BADARG;
+    const int bad = topk::check_shape(k, ld, nusers, n, topn, ALS_TOPK_MAX, nslices);
+    if (bad) return bad;
+    if (!(beta == beta) || beta - beta != 0.f) return ALS_E_BADARG;
     if (nusers == 0) return 0;
     if (!users || !U || !Z || !b_u || !b_i || !mu || !W || !top_val || !top_idx || !top_cnt || !top_lev ||
         (!seen_ptr != !seen_idx))
         return ALS_E_BADARG;
-    const int nsl = ex_slices(kp / 16, nusers, n, nslices);
-    const size_t need = als_explore_workspace_bytes(k, nusers, n, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    const topk::SlicePlan p = topk::plan(nusers, ex_rows_per_wg(ld / 16), n, nslices, nusers * topn,
+                                         sizeof(unsigned long long), workspace, workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_explore<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, W, beta, seen_ptr,
-                                                     seen_idx, allow, topn, top_val, top_idx, top_cnt, part, st));
+    ALS_DISPATCH_KB(ld / 16, rc = launch_explore<KB>(ld, nusers, users, n, p.nsl, U, Z, b_u, b_i, mu, W, beta, seen_ptr,
+                                                     seen_idx, allow, topn, top_val, top_idx, top_cnt, p.keys(), st));
+    if (rc == 0) rc = topk::merge_slices(p.nsl, p.keys(), nusers, topn, top_val, top_idx, top_cnt, st);
     if (rc != 0) return rc;
-    if (nsl > 1) {
-        hipLaunchKernelGGL(topk::k_merge_slices, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl,
-                           topn, part, top_val, top_idx, top_cnt);
-        if (hipGetLastError() != hipSuccess) return ALS_E_LAUNCH;
-    }
     ALS_DISPATCH_KB(ld / 16, hipLaunchKernelGGL(k_explore_lev<KB>, dim3((unsigned)nusers), dim3(64), 0, st, n, Z, W,
                                                 topn, top_idx, top_lev));
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return topk::launch_status();
 }

@@ -41,6 +41,7 @@
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 #include "topk_rows.hpp"
 
 namespace {
@@ -53,15 +54,6 @@ constexpr int GR_CHUNK = walk::CHUNK;
 constexpr int GR_NW = 8;            // groups (waves) per workgroup
 constexpr int GR_MAXM = ALS_GROUP_MAX_MEMBERS;
 static_assert(GR_MAXM == 64, "one member-table entry per lane, four tiles of 16");
-
-// first position in [a, e) of the ascending list whose entry is >= bound
-__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ idx, int64_t a, int64_t e, int64_t bound) {
-    while (a < e) {
-        const int64_t mid = a + ((e - a) >> 1);
-        if (idx[mid] < bound) a = mid + 1; else e = mid;
-    }
-    return a;
-}
 
 // the value of the lanes c, c + 16, c + 32, c + 48 folded, in all four
 __device__ __forceinline__ float fold_q_min(float v) {
@@ -138,7 +130,7 @@ void k_group(int ld, int64_t ngroups, const int64_t* __restrict__ g_ptr, const i
     int64_t cur = 0, end = 0;
     if (seen_ptr && active) {
         end = seen_ptr[b + 1];
-        cur = lower_bound(seen_idx, seen_ptr[b], end, lo);               // first seen item >= lo
+        cur = walk::lower_bound(seen_idx, seen_ptr[b], end, lo);               // first seen item >= lo
     }
     int nxt = cur < end ? seen_idx[cur] : INT32_MAX;
 
@@ -185,7 +177,7 @@ void k_group(int ld, int64_t ngroups, const int64_t* __restrict__ g_ptr, const i
                 if constexpr (MASKED) {
                     // all 64 below the chunk: the cursor fell behind over skipped chunks - jump, do not walk
                     const int last = __builtin_amdgcn_readlane(s, 63);
-                    if (more && last < it0) cur = lower_bound(seen_idx, cur, end, it0);
+                    if (more && last < it0) cur = walk::lower_bound(seen_idx, cur, end, it0);
                 }
             }
             nxt = cur < end ? seen_idx[cur] : INT32_MAX;
@@ -326,10 +318,6 @@ void k_group(int ld, int64_t ngroups, const int64_t* __restrict__ g_ptr, const i
     }
 }
 
-int grp_slices(int64_t ngroups, int64_t n, int nslices) {
-    return walk::plan_slices(ngroups, GR_NW, n, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
-
 template <int KB>
 int launch_group(int ld, int64_t ngroups, const int64_t* g_ptr, const int32_t* g_users, int max_members, int64_t n,
                  int nsl, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
@@ -341,15 +329,13 @@ int launch_group(int ld, int64_t ngroups, const int64_t* g_ptr, const int32_t* g
                            : (allow ? k_group<KB, 256, true> : k_group<KB, 256, false>);
     hipLaunchKernelGGL(kern, grid, dim3(GR_NW * 64), 0, st, ld, ngroups, g_ptr, g_users, max_members, n, slice, U, Z,
                        b_u, b_i, mu, seen_ptr, seen_idx, allow, aggregate, topn, tv, ti, tc, part);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return topk::launch_status();
 }
 
 }  // namespace
 
 extern "C" size_t als_group_workspace_bytes(int64_t ngroups, int64_t n, int topn, int nslices) {
-    if (ngroups <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
-    const int s = grp_slices(ngroups, n, nslices);
-    return s > 1 ? (size_t)s * (size_t)ngroups * (size_t)topn * sizeof(unsigned long long) : 0;
+    return topk::workspace_bytes(ngroups, GR_NW, n, topn, nslices);
 }
 
 extern "C" int als_group_topk(int k, int ld, int64_t ngroups, const int64_t* g_ptr, const int32_t* g_users,
@@ -358,27 +344,22 @@ extern "C" int als_group_topk(int k, int ld, int64_t ngroups, const int64_t* g_p
                               const uint32_t* allow, int aggregate, int topn, int nslices, float* top_val,
                               int32_t* top_idx, int32_t* top_cnt, void* workspace, size_t workspace_bytes,
                               void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || ngroups < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
-        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES || max_members < 0 || max_members > ALS_GROUP_MAX_MEMBERS ||
+    const int bad = topk::check_shape(k, ld, ngroups, n, topn, ALS_TOPK_MAX, nslices);
+    if (bad) return bad;
+    if (max_members < 0 || max_members > ALS_GROUP_MAX_MEMBERS ||
         (aggregate != ALS_GROUP_MEAN && aggregate != ALS_GROUP_MIN && aggregate != ALS_GROUP_MAX))
         return ALS_E_BADARG;
     if (ngroups == 0) return 0;
     if (!g_ptr || !g_users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt ||
         (!seen_ptr != !seen_idx))
         return ALS_E_BADARG;
-    const int nsl = grp_slices(ngroups, n, nslices);
-    const size_t need = als_group_workspace_bytes(ngroups, n, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    const topk::SlicePlan p = topk::plan(ngroups, GR_NW, n, nslices, ngroups * topn, sizeof(unsigned long long),
+                                         workspace, workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_group<KB>(ld, ngroups, g_ptr, g_users, max_members, n, nsl, U, Z, b_u, b_i, mu,
-                                                   seen_ptr, seen_idx, allow, aggregate, topn, top_val, top_idx,
-                                                   top_cnt, part, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(topk::k_merge_slices, dim3((unsigned)((ngroups + 3) / 4)), dim3(256), 0, st, ngroups, nsl, topn,
-                       part, top_val, top_idx, top_cnt);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_group<KB>(ld, ngroups, g_ptr, g_users, max_members, n, p.nsl, U, Z, b_u, b_i,
+                                                   mu, seen_ptr, seen_idx, allow, aggregate, topn, top_val, top_idx,
+                                                   top_cnt, p.keys(), st));
+    return rc != 0 ? rc : topk::merge_slices(p.nsl, p.keys(), ngroups, topn, top_val, top_idx, top_cnt, st);
 }

@@ -36,6 +36,7 @@
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 
 namespace {
 
@@ -383,37 +384,52 @@ void k_rank_reduce(int64_t nt, int64_t nq, int nslices, const int32_t* __restric
 
 constexpr int rk_waves(int KB) { return KB <= 4 ? 8 : 4; }      // 16-row tiles per workgroup (VGPR budget: DESIGN 15)
 
-int rank_slices(int ld, int64_t nq, int64_t n, int nslices) {
-    return walk::plan_slices(nq, rk_waves(ld / 16) * 16, n, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
-
+// seg: the SEG instantiations (`allow` is then the eligibility table); otherwise MASKED when there is a bitmap
 template <int KB>
 int launch_rank(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, const int32_t* q_items, int64_t n,
                 int nsl, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
-                const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, float* t_score, int32_t* above,
-                int32_t* n_cand, int64_t slice_stride, hipStream_t st) {
+                const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, bool seg, int64_t nseg,
+                int64_t seg_stride, const int32_t* row_seg, float* t_score, int32_t* above, int32_t* n_cand,
+                int64_t slice_stride, hipStream_t st) {
     constexpr int NW = rk_waves(KB);
     const int64_t slice = walk::slice_items(n, nsl);
     const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
-    auto kern = allow ? k_rank_count<KB, NW, true> : k_rank_count<KB, NW, false>;
+    const auto kern = seg     ? k_rank_count<KB, NW, false, true>
+                      : allow ? k_rank_count<KB, NW, true>
+                              : k_rank_count<KB, NW, false>;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n, slice, U, Z, b_u, b_i, mu,
-                       seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, allow, (int64_t)0, (int64_t)0, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+                       seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, allow, nseg, seg_stride, row_seg);
+    return topk::launch_status();
 }
 
-template <int KB>
-int launch_rank_seg(int ld, int64_t nq, const int32_t* users, const int64_t* q_ptr, const int32_t* q_items, int64_t n,
-                    int nsl, const float* U, const float* Z, const float* b_u, const float* b_i, const double* mu,
-                    const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* seg_allow, int64_t nseg,
-                    int64_t seg_stride, const int32_t* row_seg, float* t_score, int32_t* above, int32_t* n_cand,
-                    int64_t slice_stride, hipStream_t st) {
-    constexpr int NW = rk_waves(KB);
-    const int64_t slice = walk::slice_items(n, nsl);
-    const dim3 grid((unsigned)((nq + NW * 16 - 1) / (NW * 16)), (unsigned)nsl);
-    hipLaunchKernelGGL((k_rank_count<KB, NW, false, true>), grid, dim3(NW * 64), 0, st, ld, nq, users, q_ptr, q_items, n,
-                       slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, t_score, above, n_cand, slice_stride, seg_allow,
-                       nseg, seg_stride, row_seg);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+// the body of als_rank_count_masked (seg false: nseg, seg_stride and row_seg are 0) and _segmented
+int rank_count(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u, const float* b_i,
+               const double* mu, const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow, bool seg,
+               int64_t nseg, int64_t seg_stride, const int32_t* row_seg, int64_t nq, const int32_t* q_users,
+               const int64_t* q_ptr, const int32_t* q_items, int64_t nt, int nslices, float* t_score, int32_t* above,
+               int32_t* n_cand, void* workspace, size_t workspace_bytes, void* stream) {
+    const int bad = topk::check_shape(k, ld, nq, n, 1, 1, nslices);
+    if (bad) return bad;
+    if (nt < 0 || (seg && (nseg < 1 || seg_stride < (n + 31) / 32))) return ALS_E_BADARG;
+    if (nq == 0) return 0;
+    if (!q_users || !q_ptr || !U || !Z || !b_u || !b_i || !mu || !n_cand || (!seen_ptr != !seen_idx) ||
+        (nt > 0 && (!q_items || !t_score || !above)) || (seg && (!allow || !row_seg)))
+        return ALS_E_BADARG;
+    // sliced: slice s writes its counts to part[s][0 .. nt) and part[s][nt .. nt + nq)
+    const topk::SlicePlan p = topk::plan(nq, rk_waves(ld / 16) * 16, n, nslices, nt + nq, sizeof(int32_t), workspace,
+                                         workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* part = (int32_t*)p.part;
+    int rc;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, p.nsl, U, Z, b_u, b_i, mu, seen_ptr,
+                                                  seen_idx, allow, seg, nseg, seg_stride, row_seg, t_score,
+                                                  part ? part : above, part ? part + nt : n_cand, part ? nt + nq : 0,
+                                                  st));
+    if (rc != 0 || p.nsl == 1) return rc;
+    hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, p.nsl, part,
+                       above, n_cand);
+    return topk::launch_status();
 }
 
 }  // namespace
@@ -421,8 +437,7 @@ int launch_rank_seg(int ld, int64_t nq, const int32_t* users, const int64_t* q_p
 extern "C" size_t als_rank_count_workspace_bytes(int k, int64_t nq, int64_t nt, int64_t n, int nslices) {
     const int kp = als_padded_k(k);
     if (kp < 0 || nq <= 0 || nt < 0 || n <= 0 || nslices < 0) return 0;
-    const int s = rank_slices(kp, nq, n, nslices);
-    return s > 1 ? (size_t)s * (size_t)(nt + nq) * sizeof(int32_t) : 0;
+    return topk::slice_bytes(topk::slices(nq, rk_waves(kp / 16) * 16, n, nslices), nt + nq, sizeof(int32_t));
 }
 
 extern "C" int als_rank_count_masked(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
@@ -431,29 +446,8 @@ extern "C" int als_rank_count_masked(int k, int ld, int64_t n, const float* U, c
                                      const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items, int64_t nt,
                                      int nslices, float* t_score, int32_t* above, int32_t* n_cand, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nq < 0 || nt < 0 || n < 1 || n >= ((int64_t)1 << 31) || nslices < 0 ||
-        nslices > ALS_RECOMMEND_MAX_SLICES)
-        return ALS_E_BADARG;
-    if (nq == 0) return 0;
-    if (!q_users || !q_ptr || !U || !Z || !b_u || !b_i || !mu || !n_cand || (!seen_ptr != !seen_idx) ||
-        (nt > 0 && (!q_items || !t_score || !above)))
-        return ALS_E_BADARG;
-    const int nsl = rank_slices(ld, nq, n, nslices);
-    const size_t need = als_rank_count_workspace_bytes(k, nq, nt, n, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    // sliced: slice s writes its counts to part[s][0 .. nt) and part[s][nt .. nt + nq)
-    int32_t* part = nsl > 1 ? (int32_t*)workspace : nullptr;
-    int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_rank<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
-                                                  seen_idx, allow, t_score, part ? part : above,
-                                                  part ? part + nt : n_cand, part ? nt + nq : 0, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
-                       above, n_cand);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return rank_count(k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, false, 0, 0, nullptr, nq, q_users, q_ptr,
+                      q_items, nt, nslices, t_score, above, n_cand, workspace, workspace_bytes, stream);
 }
 
 extern "C" int als_rank_count_segmented(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,
@@ -463,29 +457,9 @@ extern "C" int als_rank_count_segmented(int k, int ld, int64_t n, const float* U
                                         const int32_t* q_users, const int64_t* q_ptr, const int32_t* q_items,
                                         int64_t nt, int nslices, float* t_score, int32_t* above, int32_t* n_cand,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nq < 0 || nt < 0 || n < 1 || n >= ((int64_t)1 << 31) || nslices < 0 ||
-        nslices > ALS_RECOMMEND_MAX_SLICES || nseg < 1 || seg_stride_words < (n + 31) / 32)
-        return ALS_E_BADARG;
-    if (nq == 0) return 0;
-    if (!q_users || !q_ptr || !U || !Z || !b_u || !b_i || !mu || !n_cand || (!seen_ptr != !seen_idx) ||
-        (nt > 0 && (!q_items || !t_score || !above)) || !seg_allow || !row_seg)
-        return ALS_E_BADARG;
-    const int nsl = rank_slices(ld, nq, n, nslices);
-    const size_t need = als_rank_count_workspace_bytes(k, nq, nt, n, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    int32_t* part = nsl > 1 ? (int32_t*)workspace : nullptr;
-    int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_rank_seg<KB>(ld, nq, q_users, q_ptr, q_items, n, nsl, U, Z, b_u, b_i, mu,
-                                                      seen_ptr, seen_idx, seg_allow, nseg, seg_stride_words, row_seg,
-                                                      t_score, part ? part : above, part ? part + nt : n_cand,
-                                                      part ? nt + nq : 0, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(k_rank_reduce, dim3((unsigned)((nt + nq + 255) / 256)), dim3(256), 0, st, nt, nq, nsl, part,
-                       above, n_cand);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return rank_count(k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, seg_allow, true, nseg, seg_stride_words,
+                      row_seg, nq, q_users, q_ptr, q_items, nt, nslices, t_score, above, n_cand, workspace,
+                      workspace_bytes, stream);
 }
 
 extern "C" int als_rank_count(int k, int ld, int64_t n, const float* U, const float* Z, const float* b_u,

@@ -17,8 +17,9 @@
 //
 // Item split: with few users (a batch of 1 ... 1000 fills a fraction of the CUs) the item range is cut into
 // nslices slices (grid.y); each workgroup writes its per-(slice, user) list as raw keys to the workspace, and
-// k_recommend_merge merges the lists of every user with the same 256-key sort.  The order is total, so the
-// result does not depend on the slice count.
+// topk::k_merge_slices (topk_rows.hpp) merges the lists of every user with the same 256-key sort.  The order is
+// total, so the result does not depend on the slice count.  The host side of the entry points - argument checks,
+// slice plan, workspace, merge launch - is topk_launch.hpp's.
 //
 // Allow bitmap (als_recommend_topk_masked; the MASKED instantiations): slices start at multiples of 32, so chunk ch
 // of a slice is word lo / 32 + ch of the bitmap - one wave-uniform word per chunk.  Its low half joins block 0's
@@ -55,6 +56,8 @@
 #include "catalogue_walk.hpp"
 #include "recommend_deep.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
+#include "topk_rows.hpp"
 
 namespace {
 
@@ -63,8 +66,8 @@ using topk::key_score;
 using topk::make_key;
 
 constexpr int RC_CHUNK = walk::CHUNK;
-constexpr int RC_WIDE = 64;         // users per workgroup, topn > 32: 4 waves, 256 keys per user (list 128)
-constexpr int RC_NARROW = 128;      // users per workgroup, topn <= 32: 8 waves, 128 keys per user (list 32)
+constexpr int RC_WIDE = topk::ROWS_WIDE;         // users per workgroup, topn > 32: 4 waves, 256 keys per user
+constexpr int RC_NARROW = topk::ROWS_NARROW;     // users per workgroup, topn <= 32: 8 waves, 128 keys per user
 
 __device__ __forceinline__ int readlane_i(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 
@@ -365,87 +368,23 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     }
 }
 
-// one wave per user: the nslices lists of (at most topn <= 128) keys folded into one by 256-key sorts
-__global__ __launch_bounds__(256)
-void k_recommend_merge(int64_t nusers, int nslices, int topn, const unsigned long long* __restrict__ part,
-                       float* __restrict__ top_val, int32_t* __restrict__ top_idx, int32_t* __restrict__ top_cnt) {
-    const int lane = threadIdx.x & 63;
-    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= nusers) return;                             // wave-uniform
-    unsigned long long k[4];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const int i = lane + 64 * v;
-        k[v] = i < topn ? part[b * topn + i] : 0ull;
-    }
-    for (int s = 1; s < nslices; ++s) {
-        const unsigned long long* src = part + ((int64_t)s * nusers + b) * topn;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int i = lane + 64 * v;
-            k[2 + v] = i < topn ? src[i] : 0ull;
-        }
-        topk::sort256_desc(k, lane);                     // elements 0 ... 127 (k[0], k[1]) hold the best 128
-    }
-    int cnt = 0;
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const int i = lane + 64 * v;
-        const bool ok = i < topn && k[v] != 0ull;
-        cnt += __popcll(__ballot(ok));
-        if (i < topn) {
-            top_val[b * topn + i] = ok ? key_score(k[v]) : -INFINITY;
-            top_idx[b * topn + i] = ok ? key_index(k[v]) : -1;
-        }
-    }
-    if (lane == 0) top_cnt[b] = cnt;
-}
-
-int rec_slices(int64_t nusers, int64_t n, int topn, int nslices) {
-    return walk::plan_slices(nusers, topn <= 32 ? RC_NARROW : RC_WIDE, n, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
-
+// seg: the SEG instantiations (`allow` is then the eligibility table); otherwise MASKED when there is a bitmap
 template <int KB>
 int launch_recommend(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
                      const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
-                     const int32_t* seen_idx, const uint32_t* allow, int topn, float* tv, int32_t* ti, int32_t* tc,
-                     unsigned long long* part, hipStream_t st) {
-    const int64_t slice = walk::slice_items(n, nsl);
-    if (topn <= 32) {
-        const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
-        auto kern = allow ? k_recommend<KB, RC_NARROW / 16, 128, true> : k_recommend<KB, RC_NARROW / 16, 128, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(RC_NARROW * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr, (int64_t)0, (int64_t)0,
-                           nullptr);
-    } else {
-        const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
-        auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true> : k_recommend<KB, RC_WIDE / 16, 256, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu,
-                           seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr, (int64_t)0, (int64_t)0,
-                           nullptr);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
-}
-
-template <int KB>
-int launch_recommend_seg(int ld, int64_t nusers, const int32_t* users, int64_t n, int nsl, const float* U, const float* Z,
-                         const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
-                         const int32_t* seen_idx, const uint32_t* seg_allow, int64_t nseg, int64_t seg_stride,
-                         const int32_t* row_seg, int topn, float* tv, int32_t* ti, int32_t* tc,
-                         unsigned long long* part, hipStream_t st) {
-    const int64_t slice = walk::slice_items(n, nsl);
-    if (topn <= 32) {
-        const dim3 grid((unsigned)((nusers + RC_NARROW - 1) / RC_NARROW), (unsigned)nsl);
-        hipLaunchKernelGGL((k_recommend<KB, RC_NARROW / 16, 128, false, false, true>), grid, dim3(RC_NARROW * 4), 0, st,
-                           ld, nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part,
-                           seg_allow, nullptr, nullptr, nseg, seg_stride, row_seg);
-    } else {
-        const dim3 grid((unsigned)((nusers + RC_WIDE - 1) / RC_WIDE), (unsigned)nsl);
-        hipLaunchKernelGGL((k_recommend<KB, RC_WIDE / 16, 256, false, false, true>), grid, dim3(RC_WIDE * 4), 0, st, ld,
-                           nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part,
-                           seg_allow, nullptr, nullptr, nseg, seg_stride, row_seg);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+                     const int32_t* seen_idx, const uint32_t* allow, bool seg, int64_t nseg, int64_t seg_stride,
+                     const int32_t* row_seg, int topn, float* tv, int32_t* ti, int32_t* tc, unsigned long long* part,
+                     hipStream_t st) {
+    constexpr int NN = RC_NARROW / 16, NWD = RC_WIDE / 16;
+    const auto narrow = seg     ? k_recommend<KB, NN, 128, false, false, true>
+                        : allow ? k_recommend<KB, NN, 128, true>
+                                : k_recommend<KB, NN, 128, false>;
+    const auto wide = seg     ? k_recommend<KB, NWD, 256, false, false, true>
+                      : allow ? k_recommend<KB, NWD, 256, true>
+                              : k_recommend<KB, NWD, 256, false>;
+    return topk::launch_by_width(narrow, wide, topn, nusers, nsl, st, ld, nusers, users, n, walk::slice_items(n, nsl), U,
+                                 Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, tv, ti, tc, part, allow, nullptr, nullptr,
+                                 nseg, seg_stride, row_seg);
 }
 
 template <int KB>
@@ -458,7 +397,31 @@ int launch_recommend_ceil(int ld, int64_t nusers, const int32_t* users, int64_t 
     auto kern = allow ? k_recommend<KB, RC_WIDE / 16, 256, true, true> : k_recommend<KB, RC_WIDE / 16, 256, false, true>;
     hipLaunchKernelGGL(kern, grid, dim3(RC_WIDE * 4), 0, st, ld, nusers, users, n, slice, U, Z, b_u, b_i, mu, seen_ptr,
                        seen_idx, ALS_TOPK_MAX, nullptr, nullptr, nullptr, part, allow, ceil, go, (int64_t)0, (int64_t)0, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return topk::launch_status();
+}
+
+// the body of als_recommend_topk_masked (seg false: nseg, seg_stride and row_seg are 0) and _segmented
+int recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U, const float* Z,
+                   const float* b_u, const float* b_i, const double* mu, const int64_t* seen_ptr,
+                   const int32_t* seen_idx, const uint32_t* allow, bool seg, int64_t nseg, int64_t seg_stride,
+                   const int32_t* row_seg, int topn, int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    const int bad = topk::check_shape(k, ld, nusers, n, topn, ALS_TOPK_MAX, nslices);
+    if (bad) return bad;
+    if (seg && (nseg < 1 || seg_stride < (n + 31) / 32)) return ALS_E_BADARG;
+    if (nusers == 0) return 0;
+    if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx) ||
+        (seg && (!allow || !row_seg)))
+        return ALS_E_BADARG;
+    const topk::SlicePlan p = topk::plan(nusers, topk::rows_per_wg(topn), n, nslices, nusers * topn,
+                                         sizeof(unsigned long long), workspace, workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend<KB>(ld, nusers, users, n, p.nsl, U, Z, b_u, b_i, mu, seen_ptr,
+                                                       seen_idx, allow, seg, nseg, seg_stride, row_seg, topn, top_val,
+                                                       top_idx, top_cnt, p.keys(), st));
+    return rc != 0 ? rc : topk::merge_slices(p.nsl, p.keys(), nusers, topn, top_val, top_idx, top_cnt, st);
 }
 
 }  // namespace
@@ -473,14 +436,10 @@ int deep::score_round(int ld, int64_t nusers, const int32_t* users, int64_t n, i
                                                             seen_idx, allow, part, ceil, go, st));
     return rc;
 }
-int deep::plan_slices(int64_t nusers, int64_t n, int nslices) {
-    return walk::plan_slices(nusers, RC_WIDE, n, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
+int deep::plan_slices(int64_t nusers, int64_t n, int nslices) { return topk::slices(nusers, RC_WIDE, n, nslices); }
 
 extern "C" size_t als_recommend_workspace_bytes(int64_t nusers, int64_t n, int topn, int nslices) {
-    if (nusers <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
-    const int s = rec_slices(nusers, n, topn, nslices);
-    return s > 1 ? (size_t)s * (size_t)nusers * (size_t)topn * sizeof(unsigned long long) : 0;
+    return topk::workspace_bytes(nusers, topk::rows_per_wg(topn), n, topn, nslices);
 }
 
 extern "C" int als_recommend_topk_masked(int k, int ld, int64_t nusers, const int32_t* users, int64_t n,
@@ -489,26 +448,8 @@ extern "C" int als_recommend_topk_masked(int k, int ld, int64_t nusers, const in
                                          const uint32_t* allow, int topn, int nslices, float* top_val,
                                          int32_t* top_idx, int32_t* top_cnt, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
-        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES)
-        return ALS_E_BADARG;
-    if (nusers == 0) return 0;
-    if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx))
-        return ALS_E_BADARG;
-    const int nsl = rec_slices(nusers, n, topn, nslices);
-    const size_t need = als_recommend_workspace_bytes(nusers, n, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr, seen_idx,
-                                                       allow, topn, top_val, top_idx, top_cnt, part, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
-                       top_val, top_idx, top_cnt);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return recommend_topk(k, ld, nusers, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, false, 0, 0, nullptr,
+                          topn, nslices, top_val, top_idx, top_cnt, workspace, workspace_bytes, stream);
 }
 
 extern "C" int als_recommend_topk_segmented(int k, int ld, int64_t nusers, const int32_t* users, int64_t n,
@@ -518,28 +459,9 @@ extern "C" int als_recommend_topk_segmented(int k, int ld, int64_t nusers, const
                                             const int32_t* row_seg, int topn, int nslices, float* top_val,
                                             int32_t* top_idx, int32_t* top_cnt, void* workspace,
                                             size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX ||
-        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES || nseg < 1 || seg_stride_words < (n + 31) / 32)
-        return ALS_E_BADARG;
-    if (nusers == 0) return 0;
-    if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx) ||
-        !seg_allow || !row_seg)
-        return ALS_E_BADARG;
-    const int nsl = rec_slices(nusers, n, topn, nslices);
-    const size_t need = als_recommend_workspace_bytes(nusers, n, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_recommend_seg<KB>(ld, nusers, users, n, nsl, U, Z, b_u, b_i, mu, seen_ptr,
-                                                           seen_idx, seg_allow, nseg, seg_stride_words, row_seg, topn,
-                                                           top_val, top_idx, top_cnt, part, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(k_recommend_merge, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, part,
-                       top_val, top_idx, top_cnt);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return recommend_topk(k, ld, nusers, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, seg_allow, true, nseg,
+                          seg_stride_words, row_seg, topn, nslices, top_val, top_idx, top_cnt, workspace,
+                          workspace_bytes, stream);
 }
 
 extern "C" int als_recommend_topk(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,

@@ -25,6 +25,7 @@
 #include "als_hip.h"
 #include "recommend_deep.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 
 namespace {
 
@@ -183,7 +184,7 @@ int launch_merge(int64_t nusers, int nsl, int topn, int round, int nrounds, cons
                  int32_t* ti, int32_t* tc, hipStream_t st) {
     hipLaunchKernelGGL(k_deep_merge<V>, dim3((unsigned)((nusers + 3) / 4)), dim3(256), 0, st, nusers, nsl, topn, round,
                        nrounds, part, list, ceil, flags, rounds, tv, ti, tc);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return topk::launch_status();
 }
 
 }  // namespace
@@ -200,11 +201,8 @@ extern "C" int als_recommend_deep(int k, int ld, int64_t nusers, const int32_t* 
                                   const unsigned long long* after_key, int topn, int nslices, float* top_val,
                                   int32_t* top_idx, int32_t* top_cnt, int32_t* rounds, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nusers < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_DEEP_MAX ||
-        nslices < 0 || nslices > ALS_RECOMMEND_MAX_SLICES)
-        return ALS_E_BADARG;
+    const int bad = topk::check_shape(k, ld, nusers, n, topn, ALS_TOPK_DEEP_MAX, nslices);
+    if (bad) return bad;
     if (nusers == 0) return 0;
     if (!users || !U || !Z || !b_u || !b_i || !mu || !top_val || !top_idx || !top_cnt || (!seen_ptr != !seen_idx))
         return ALS_E_BADARG;

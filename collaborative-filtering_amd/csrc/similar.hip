@@ -23,6 +23,7 @@
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 #include "topk_rows.hpp"
 
 namespace {
@@ -30,8 +31,6 @@ namespace {
 using topk::make_key;
 
 constexpr int SM_CHUNK = walk::CHUNK;
-constexpr int SM_WIDE = 64;         // queries per workgroup, topn > 32: 4 waves, 256 keys per query (list 128)
-constexpr int SM_NARROW = 128;      // queries per workgroup, topn <= 32: 8 waves, 128 keys per query (list 32)
 
 // 16 lanes per row: lane c takes the float4 groups c, c + 16, ... of the row (padding columns are zero)
 __global__ __launch_bounds__(256)
@@ -165,28 +164,16 @@ void k_similar(int ld, int64_t nq, const int32_t* __restrict__ q_ids, const floa
         topk::finish_row<CAP>(kw, st, R, topn, lane, b0 + R, nq, (int64_t)blockIdx.y, part, top_val, top_idx, top_cnt);
 }
 
-int sim_slices(int64_t nq, int64_t n, int topn, int nslices) {
-    return walk::plan_slices(nq, topn <= 32 ? SM_NARROW : SM_WIDE, n, nslices, ALS_RECOMMEND_MAX_SLICES);
-}
-
 template <int KB>
 int launch_similar(int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_inv,
                    const int32_t* self_ids, int64_t n, int nsl, const float* T, const float* t_inv,
                    const uint32_t* allow, int topn, float* tv, int32_t* ti, int32_t* tc, unsigned long long* part,
                    hipStream_t st) {
-    const int64_t slice = walk::slice_items(n, nsl);
-    if (topn <= 32) {
-        const dim3 grid((unsigned)((nq + SM_NARROW - 1) / SM_NARROW), (unsigned)nsl);
-        auto kern = allow ? k_similar<KB, SM_NARROW / 16, 128, true> : k_similar<KB, SM_NARROW / 16, 128, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(SM_NARROW * 4), 0, st, ld, nq, q_ids, Q, q_inv, self_ids, n, slice, T, t_inv,
-                           allow, topn, tv, ti, tc, part);
-    } else {
-        const dim3 grid((unsigned)((nq + SM_WIDE - 1) / SM_WIDE), (unsigned)nsl);
-        auto kern = allow ? k_similar<KB, SM_WIDE / 16, 256, true> : k_similar<KB, SM_WIDE / 16, 256, false>;
-        hipLaunchKernelGGL(kern, grid, dim3(SM_WIDE * 4), 0, st, ld, nq, q_ids, Q, q_inv, self_ids, n, slice, T, t_inv,
-                           allow, topn, tv, ti, tc, part);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    constexpr int NN = topk::ROWS_NARROW / 16, NWD = topk::ROWS_WIDE / 16;
+    return topk::launch_by_width(allow ? k_similar<KB, NN, 128, true> : k_similar<KB, NN, 128, false>,
+                                 allow ? k_similar<KB, NWD, 256, true> : k_similar<KB, NWD, 256, false>, topn, nq, nsl,
+                                 st, ld, nq, q_ids, Q, q_inv, self_ids, n, walk::slice_items(n, nsl), T, t_inv, allow,
+                                 topn, tv, ti, tc, part);
 }
 
 }  // namespace
@@ -199,36 +186,27 @@ extern "C" int als_row_inv_norms(int k, int ld, int64_t nrows, const float* T, f
     if (!T || !inv_norm) return ALS_E_BADARG;
     hipLaunchKernelGGL(k_row_inv_norms, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, ld,
                        nrows, T, inv_norm);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    return topk::launch_status();
 }
 
 extern "C" size_t als_similar_workspace_bytes(int64_t nq, int64_t n, int topn, int nslices) {
-    if (nq <= 0 || n <= 0 || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0) return 0;
-    const int s = sim_slices(nq, n, topn, nslices);
-    return s > 1 ? (size_t)s * (size_t)nq * (size_t)topn * sizeof(unsigned long long) : 0;
+    return topk::workspace_bytes(nq, topk::rows_per_wg(topn), n, topn, nslices);
 }
 
 extern "C" int als_similar_topk(int k, int ld, int64_t nq, const int32_t* q_ids, const float* Q, const float* q_inv,
                                 const int32_t* self_ids, int64_t n, const float* T, const float* t_inv,
                                 const uint32_t* allow, int topn, int nslices, float* top_val, int32_t* top_idx,
                                 int32_t* top_cnt, void* workspace, size_t workspace_bytes, void* stream) {
-    const int kp = als_padded_k(k);
-    if (kp < 0) return ALS_E_BADK;
-    if (ld != kp || nq < 0 || n < 1 || n >= ((int64_t)1 << 31) || topn < 1 || topn > ALS_TOPK_MAX || nslices < 0 ||
-        nslices > ALS_RECOMMEND_MAX_SLICES)
-        return ALS_E_BADARG;
+    const int bad = topk::check_shape(k, ld, nq, n, topn, ALS_TOPK_MAX, nslices);
+    if (bad) return bad;
     if (nq == 0) return 0;
     if (!q_ids || !Q || !q_inv || !T || !t_inv || !top_val || !top_idx || !top_cnt) return ALS_E_BADARG;
-    const int nsl = sim_slices(nq, n, topn, nslices);
-    const size_t need = als_similar_workspace_bytes(nq, n, topn, nslices);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return ALS_E_BADARG;
-    unsigned long long* part = nsl > 1 ? (unsigned long long*)workspace : nullptr;
+    const topk::SlicePlan p = topk::plan(nq, topk::rows_per_wg(topn), n, nslices, nq * topn,
+                                         sizeof(unsigned long long), workspace, workspace_bytes);
+    if (!p.nsl) return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    ALS_DISPATCH_KB(ld / 16, rc = launch_similar<KB>(ld, nq, q_ids, Q, q_inv, self_ids, n, nsl, T, t_inv, allow, topn,
-                                                     top_val, top_idx, top_cnt, part, st));
-    if (rc != 0 || nsl == 1) return rc;
-    hipLaunchKernelGGL(topk::k_merge_slices, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, nq, nsl, topn, part,
-                       top_val, top_idx, top_cnt);
-    return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
+    ALS_DISPATCH_KB(ld / 16, rc = launch_similar<KB>(ld, nq, q_ids, Q, q_inv, self_ids, n, p.nsl, T, t_inv, allow, topn,
+                                                     top_val, top_idx, top_cnt, p.keys(), st));
+    return rc != 0 ? rc : topk::merge_slices(p.nsl, p.keys(), nq, topn, top_val, top_idx, top_cnt, st);
 }

@@ -1,5 +1,5 @@
-// Keys and sorts for per-row top-k selection under a total order: the 64-bit keys for k_recommend /
-// k_recommend_merge (recommend.hip), k_rank_count (rank_eval.hip: it compares keys and never sorts), explain.hip and
+// Keys and sorts for per-row top-k selection under a total order: the 64-bit keys for k_recommend (recommend.hip),
+// topk::k_merge_slices (topk_rows.hpp), k_rank_count (rank_eval.hip: it compares keys and never sorts), explain.hip and
 // diversify.hip; the float encoding and the bitonic sorts also for k_topk_sim (graph_build.hip).
 //
 // A candidate is one 64-bit key: the high word is enc_f32(score) - an unsigned encoding whose integer order is the

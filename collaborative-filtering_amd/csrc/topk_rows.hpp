@@ -1,7 +1,8 @@
 // Per-row selection state of a wave that serves 16 batch rows of a catalogue walk, and the merge of per-slice lists:
-// what k_recommend (recommend.hip) keeps in lambdas, in shared form.  Only similar.hip includes this header -
-// recommend.hip and rank_eval.hip keep their own text (catalogue_walk.hpp says why: sharing it moved their register
-// allocation).
+// what k_recommend (recommend.hip) keeps in lambdas, in shared form.  k_similar and k_audience use the per-row state;
+// k_group and k_explore keep one list per wave and use the merge alone, as does recommend.hip, whose kernel keeps its
+// own text of the state (catalogue_walk.hpp says why: sharing it moved the register allocation).  The merge is
+// launched by topk::merge_slices below, with the slice plan of topk_launch.hpp.
 //
 // Layout: lane (c, q) = (lane & 15, lane >> 4) holds the state of the rows 4q + r, r = 0 ... 3, the same value in the 16
 // lanes of a q group; row R of the wave owns kw[R][0 .. CAP): the sorted list [0, L) and the survivor buffer
@@ -11,6 +12,7 @@
 #pragma once
 #include "als_device.hpp"
 #include "topk_common.hpp"
+#include "topk_launch.hpp"
 
 namespace topk {
 
@@ -146,6 +148,16 @@ void k_merge_slices(int64_t nrows, int nslices, int topn, const unsigned long lo
         }
     }
     if (lane == 0) top_cnt[b] = cnt;
+}
+
+// host: the lists of nsl slices (raw keys in `part`) folded into the outputs; nothing to do with one slice.  Here and
+// not in topk_launch.hpp: a file that sees this launch emits the kernel, and rank_eval.hip has no use for it
+inline int merge_slices(int nsl, const unsigned long long* part, int64_t nrows, int topn, float* top_val,
+                        int32_t* top_idx, int32_t* top_cnt, hipStream_t st) {
+    if (nsl == 1) return 0;
+    hipLaunchKernelGGL(k_merge_slices, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, nrows, nsl, topn, part,
+                       top_val, top_idx, top_cnt);
+    return launch_status();
 }
 
 }  // namespace topk

@@ -210,6 +210,18 @@ class _Serving:
             seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
         return lambda b0, nb: (users[b0: b0 + nb], self.U, self.b_u, seen_ptr, seen_idx)
 
+    def _side(self, features, folded: Optional["FoldedItems"] = None) -> dict:
+        """The item tables a call scores against: the fitted items with the Z of `predict`, followed with `folded`
+        by the folded ones (`_joint_side`)."""
+        return self._item_side(self._compose_for(features)) if folded is None else self._joint_side(features, folded)
+
+    def _catalogue(self, users_t: torch.Tensor, features, exclude_seen: bool, folded: Optional["FoldedItems"] = None):
+        """(side, rows) of a call for users of the fit: the item tables of `_side` and the chunk source that goes
+        with them - `_fitted_rows`, or `_joint_rows` over the joint catalogue."""
+        if folded is None:
+            return self._side(features), self._fitted_rows(users_t, exclude_seen)
+        return self._side(features, folded), self._joint_rows(users_t, exclude_seen, folded)
+
     def _table_rows(self, B: int, U, b_u, seen=None):
         """Chunk source for a table made for the call (batch row b = table row b): the chunk is addressed as rows
         0 .. nb of the tables advanced to b0.  `seen` = (host indptr, device indptr, device indices) or None."""
@@ -223,70 +235,87 @@ class _Serving:
             return users[:nb], U[b0:], b_u[b0:], seen_ptr, seen_idx
         return rows
 
-    def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False,
-                     allow: Optional[torch.Tensor] = None, seg=None):
-        """als_recommend_topk over B batch rows in REC_BATCH chunks.  rows(b0, nb) -> (users int32 [nb], U, b_u,
-        seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu); `allow`: the
-        bitmap of the call (`allow_bitmap`) - every chunk then goes through als_recommend_topk_masked; `seg` =
-        (eligibility table, row_seg int32 [B] on the device) instead: als_recommend_topk_segmented.  Returns host
-        (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk, or with `on_device` the kernel's own
-        (top_val fp32 [B, N], top_idx int32 [B, N])."""
-        if on_device:
-            top_val = torch.empty(B, N, dtype=torch.float32, device=self.dev)
-            top_idx = torch.empty(B, N, dtype=torch.int32, device=self.dev)
-            top_cnt = torch.empty(B, dtype=torch.int32, device=self.dev)
-        else:
-            out_items = np.empty((B, N), dtype=np.int64)
-            out_scores = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
-            if on_device:
-                tv, ti, tc = top_val[b0:], top_idx[b0:], top_cnt[b0:]
-            else:
-                tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-                ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-                tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            if seg is not None:
-                self.be.recommend_topk_segmented(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx,
-                                                 seg_allow=seg[0], row_seg=seg[1][b0: b0 + nb], topn=N, top_val=tv,
-                                                 top_idx=ti, top_cnt=tc, **items)
-            elif allow is None:
-                self.be.recommend_topk(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N,
-                                       top_val=tv, top_idx=ti, top_cnt=tc, **items)
-            else:
-                self.be.recommend_topk_masked(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx,
-                                              allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
-            if not on_device:
-                out_items[b0: b0 + nb] = ti.cpu().numpy()
-                out_scores[b0: b0 + nb] = tv.cpu().numpy()
-        return (top_val, top_idx) if on_device else (out_items, out_scores)
+    # ------------------------------------------------------- chunked drivers
+    @staticmethod
+    def _chunks(B: int, step: int):
+        """(b0, nb) of the chunks of B batch rows, `step` rows each but the last."""
+        for b0 in range(0, B, step):
+            yield b0, min(step, B - b0)
 
-    def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, Z,
-                     allow: Optional[torch.Tensor] = None, seg=None, side: Optional[dict] = None):
+    def _topn_out(self, nb: int, N: int):
+        """The outputs of a top-N call over nb rows on the device: (top_val fp32 [nb, N], top_idx int32 [nb, N],
+        top_cnt int32 [nb])."""
+        return (torch.empty(nb, N, dtype=torch.float32, device=self.dev),
+                torch.empty(nb, N, dtype=torch.int32, device=self.dev),
+                torch.empty(nb, dtype=torch.int32, device=self.dev))
+
+    def _collect(self, B: int, step: int, specs, call) -> tuple:
+        """call(b0, nb) -> one device tensor [nb, ...] per entry of `specs` = ((trailing shape, host dtype), ...) for
+        every chunk of `_chunks(B, step)`; returns the host arrays [B, ...], copied chunk by chunk - nothing of B rows
+        exists on the device."""
+        outs = tuple(np.empty((B, *shape), dtype=dtype) for shape, dtype in specs)
+        for b0, nb in self._chunks(B, step):
+            for out, t in zip(outs, call(b0, nb)):
+                out[b0: b0 + nb] = t.cpu().numpy()
+        return outs
+
+    def _collect_topn(self, B: int, N: int, step: int, call, extra=()) -> tuple:
+        """`_collect` of a top-N call: call(b0, nb, top_val, top_idx, top_cnt) fills the `_topn_out` of the chunk and
+        returns further device tensors [nb, ...] of the trailing shapes `extra` (or None).  Returns host (ids int64
+        [B, N], values float64 [B, N], and the extras as float64)."""
+        def chunk(b0, nb):
+            tv, ti, tc = self._topn_out(nb, N)
+            return (ti, tv, *(call(b0, nb, tv, ti, tc) or ()))
+        specs = (((N,), np.int64), ((N,), np.float64), *((shape, np.float64) for shape in extra))
+        return self._collect(B, step, specs, chunk)
+
+    def _restricted(self, name: str, allow, seg, b0: int, nb: int, **kw):
+        """The backend call `name` over the catalogue the chunk [b0, b0 + nb) may see: `name`_segmented with seg =
+        (eligibility table, row_seg int32 [B] on the device), `name`_masked with the bitmap `allow`, else `name`."""
+        if seg is not None:
+            getattr(self.be, name + "_segmented")(seg_allow=seg[0], row_seg=seg[1][b0: b0 + nb], **kw)
+        elif allow is not None:
+            getattr(self.be, name + "_masked")(allow=allow, **kw)
+        else:
+            getattr(self.be, name)(**kw)
+
+    def _topk_chunks(self, B: int, N: int, rows, items: dict, on_device: bool = False, filters=None, seg=None):
+        """als_recommend_topk over B batch rows in REC_BATCH chunks.  rows(b0, nb) -> (users int32 [nb], U, b_u,
+        seen_ptr, seen_idx) of chunk [b0, b0 + nb); `items`: the item tables (k, ld, n, Z, b_i, mu); `filters`: the
+        validated (items, filter_items) pair of the call - its bitmap (`allow_bitmap`) is made once and every chunk
+        goes through als_recommend_topk_masked; `seg` instead: als_recommend_topk_segmented (`_restricted`).  Returns
+        host (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk, or with `on_device` the kernel's own
+        (top_val fp32 [B, N], top_idx int32 [B, N])."""
+        allow = self.allow_bitmap(filters, items["n"])
+
+        def call(b0, nb, tv, ti, tc):
+            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+            self._restricted("recommend_topk", allow, seg, b0, nb, users=users, U=U, b_u=b_u, seen_ptr=seen_ptr,
+                             seen_idx=seen_idx, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
+        if not on_device:
+            return self._collect_topn(B, N, self.REC_BATCH, call)
+        top_val, top_idx, top_cnt = self._topn_out(B, N)
+        for b0, nb in self._chunks(B, self.REC_BATCH):
+            call(b0, nb, top_val[b0:], top_idx[b0:], top_cnt[b0:])
+        return top_val, top_idx
+
+    def _rank_chunks(self, rows, t_ptr: torch.Tensor, t_ptr_h: np.ndarray, q_items: torch.Tensor, items: dict,
+                     filters=None, seg=None):
         """als_rank_count over the batch rows of the prefix sum `t_ptr` (device; `t_ptr_h` its host copy) in
-        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]], `rows`, `allow` and `seg` as in
-        `_topk_chunks` (als_rank_count_masked, als_rank_count_segmented); `side`: the item tables when they are not
-        the fitted ones of Z (`_joint_side`).
+        REC_BATCH chunks: row b's targets are q_items[t_ptr[b]:t_ptr[b + 1]]; `rows`, `items`, `filters` and `seg` as
+        in `_topk_chunks` (als_rank_count_masked, als_rank_count_segmented).
         Returns device (above int32 [P], n_cand int32 [rows], score fp32 [P])."""
         B, P = t_ptr_h.size - 1, q_items.numel()
+        allow = self.allow_bitmap(filters, items["n"])
         above = torch.empty(P, dtype=torch.int32, device=self.dev)
         score = torch.empty(P, dtype=torch.float32, device=self.dev)
         ncand = torch.empty(B, dtype=torch.int32, device=self.dev)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
+        for b0, nb in self._chunks(B, self.REC_BATCH):
             users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
             t0, t1 = int(t_ptr_h[b0]), int(t_ptr_h[b0 + nb])
-            kw = dict(U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, q_users=users,
-                      q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
-                      t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb],
-                      **(self._item_side(Z) if side is None else side))
-            if seg is not None:
-                self.be.rank_count_segmented(seg_allow=seg[0], row_seg=seg[1][b0: b0 + nb], **kw)
-            elif allow is None:
-                self.be.rank_count(**kw)
-            else:
-                self.be.rank_count_masked(allow=allow, **kw)
+            self._restricted("rank_count", allow, seg, b0, nb, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx,
+                             q_users=users, q_ptr=(t_ptr[b0: b0 + nb + 1] - t0).contiguous(), q_items=q_items[t0:t1],
+                             t_score=score[t0:t1], above=above[t0:t1], n_cand=ncand[b0: b0 + nb], **items)
         return above, ncand, score
 
     def _group_by_user(self, us: torch.Tensor):
@@ -328,9 +357,8 @@ class _Serving:
         """Top-N items of the users in `users_t` (int32, device): (items int64 [B, N], scores float64 [B, N]),
         unused slots -1 / -inf.  Z is composed as in `predict`; the seen items are the training CSR of this fit.
         `filters`: here and below the validated (items, filter_items) pair of the call, or None."""
-        Z = self._compose_for(features)
-        return self._topk_chunks(users_t.numel(), N, self._fitted_rows(users_t, exclude_seen), self._item_side(Z),
-                                 allow=self.allow_bitmap(filters, self.n))
+        side, rows = self._catalogue(users_t, features, exclude_seen)
+        return self._topk_chunks(users_t.numel(), N, rows, side, filters=filters)
 
     def _rank_outputs(self, above, ncand_rows, counts, score, inv=None):
         rank = above.to(torch.int64)
@@ -343,10 +371,14 @@ class _Serving:
         """Ranks of the pairs (us[p], is_[p]) (int32, device): the pairs are grouped by user on the device, every
         user of a REC_BATCH chunk is scored once (als_rank_count), and the outputs go back to the pairs' order:
         (rank int64 [P], n_candidates int64 [P], scores float32 [P]).  Z and the seen items as in `recommend`."""
-        Z = self._compose_for(features)
+        return self._rank_pairs(us, is_, features, exclude_seen, filters=filters)
+
+    def _rank_pairs(self, us, is_, features, exclude_seen: bool, folded=None, filters=None, elig=None, pair_seg=None):
+        """`rank_of` / `rank_of_eligible`: with `elig` the segment of a user's row is that of its first pair."""
         order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
-        above, ncand, score = self._rank_chunks(self._fitted_rows(uniq, exclude_seen), ptr, ptr_h,
-                                                is_[order].contiguous(), Z, self.allow_bitmap(filters, self.n))
+        seg = None if elig is None else (elig.table, pair_seg[order][ptr[:-1]].contiguous())
+        side, rows = self._catalogue(uniq, features, exclude_seen, folded)
+        above, ncand, score = self._rank_chunks(rows, ptr, ptr_h, is_[order].contiguous(), side, filters, seg)
         return self._rank_outputs(above, ncand, counts, score, inv)
 
     def explain(self, us: torch.Tensor, is_: torch.Tensor, M: int, features, n_sweeps: int, largest: bool):
@@ -389,11 +421,14 @@ class _Serving:
         _raise_unless_solved(status, "fold-in")
         return U, b, ptr_d, idx_d
 
-    def _folded_rows(self, indptr: np.ndarray, indices, vals, Z, n_sweeps: int, exclude_seen: bool):
-        """Fold in, then the chunk source of the folded table: batch row b = new row b, the given ratings as the
-        seen CSR."""
+    def _new_catalogue(self, indptr: np.ndarray, indices, vals, features, n_sweeps: int, exclude_seen: bool):
+        """`_catalogue` for rows outside the fit: fold in against the Z of `predict`, then the chunk source of the
+        folded table - batch row b = new row b, the given ratings as the seen CSR.  Returns (side, rows, and the
+        device row pointers and indices of the ratings)."""
+        Z = self._compose_for(features)
         U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
-        return self._table_rows(indptr.size - 1, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
+        rows = self._table_rows(indptr.size - 1, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
+        return self._item_side(Z), rows, ptr_d, idx_d
 
     def fold_in(self, indptr, indices, vals, features, n_sweeps: int):
         """Factors / biases of new users (host CSR, rows sorted) against this fit's item side: device fp32
@@ -405,20 +440,17 @@ class _Serving:
                       filters=None):
         """Fold in, then als_recommend_topk on the folded table in REC_BATCH chunks: (items int64 [B, N], scores
         float64 [B, N])."""
-        Z = self._compose_for(features)
-        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
-        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z),
-                                 allow=self.allow_bitmap(filters, self.n))
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._topk_chunks(indptr.size - 1, N, rows, side, filters=filters)
 
     def rank_of_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, features, n_sweeps: int,
                     exclude_seen: bool, filters=None):
         """Fold in, then als_rank_count on the folded table (as `recommend_new` composes it) for the targets
         titems[tptr[b]:tptr[b + 1]], in REC_BATCH chunks."""
-        Z = self._compose_for(features)
-        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
         tptr_d = torch.from_numpy(tptr).to(self.dev)
-        above, ncand, score = self._rank_chunks(rows, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), Z,
-                                                self.allow_bitmap(filters, self.n))
+        above, ncand, score = self._rank_chunks(rows, tptr_d, tptr, torch.from_numpy(titems).to(self.dev), side,
+                                                filters)
         return self._rank_outputs(above, ncand, tptr_d[1:] - tptr_d[:-1], score)
 
     def explain_new(self, indptr, indices, vals, tptr: np.ndarray, titems: np.ndarray, M: int, features,
@@ -446,8 +478,7 @@ class _Serving:
         b_u = torch.empty(W, **f64)
         status = torch.zeros(1, dtype=torch.int32, device=self.dev)
         ptr_d, idx_d, val_d = self._csr_dev(*csr)
-        for b0 in range(0, W, self.REC_BATCH):
-            nb = min(self.REC_BATCH, W - b0)
+        for b0, nb in self._chunks(W, self.REC_BATCH):
             t0, t1 = int(tptr_h[b0]), int(tptr_h[b0 + nb])
             if t1 == t0:
                 b_u[b0: b0 + nb] = float("nan")                          # rows without targets: never read
@@ -549,30 +580,34 @@ class _Serving:
         """Chunk source over the joint catalogue: the batch's user rows are gathered (batch row r = user
         users_t[r]) and their seen lists are the training row followed by the folded items they rated - ascending,
         as the new ids come last."""
-        if exclude_seen:
-            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item
-            rp, ri = folded.ratings[0], folded.ratings[1]
-            new_u = ri.astype(np.int64)
-            new_i = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
-            o = np.lexsort((new_i, new_u))
-            new_u_d = torch.from_numpy(new_u[o]).to(self.dev)
-            new_i_d = torch.from_numpy(new_i[o].astype(np.int32)).to(self.dev)
+        pairs = self._folded_rater_pairs(folded) if exclude_seen else None
 
         def rows(b0, nb):
             us = users_t[b0: b0 + nb].to(torch.int64)
-            seen_ptr, seen_idx = self._merged_seen(us, new_u_d, new_i_d) if exclude_seen else (None, None)
+            seen_ptr, seen_idx = self._merged_seen(us, *pairs) if exclude_seen else (None, None)
             return (torch.arange(nb, dtype=torch.int32, device=self.dev), self.U.index_select(0, us),
                     self.b_u.index_select(0, us), seen_ptr, seen_idx)
         return rows
+
+    def _folded_rater_pairs(self, folded: Optional["FoldedItems"]):
+        """The raters of the folded items, transposed: device (user int64, item n + b int32) pairs sorted by user,
+        then item - what `_merged_seen` appends to the training rows.  No pairs without `folded`."""
+        if folded is None:
+            return (torch.empty(0, dtype=torch.int64, device=self.dev),
+                    torch.empty(0, dtype=torch.int32, device=self.dev))
+        rp, ri = folded.ratings[0], folded.ratings[1]
+        new_u = ri.astype(np.int64)
+        new_i = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
+        o = np.lexsort((new_i, new_u))
+        return torch.from_numpy(new_u[o]).to(self.dev), torch.from_numpy(new_i[o].astype(np.int32)).to(self.dev)
 
     def recommend_with_items(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
                              folded: "FoldedItems", filters=None):
         """`recommend` over the n fitted items and the folded ones (ids n + b): one als_recommend_topk on the
         concatenated Z / b_i tables (`_joint_side`) with the gathered user rows and merged seen lists of
         `_joint_rows`.  The bitmap of `filters` spans the n + B ids of the concatenated table."""
-        side = self._joint_side(features, folded)
-        return self._topk_chunks(users_t.numel(), N, self._joint_rows(users_t, exclude_seen, folded), side,
-                                 allow=self.allow_bitmap(filters, side["n"]))
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
+        return self._topk_chunks(users_t.numel(), N, rows, side, filters=filters)
 
     # ----------------------------------------------------------- eligibility
     def eligibility_table(self, kind: str, payload, filters, n_total: int) -> "ItemEligibility":
@@ -595,146 +630,99 @@ class _Serving:
                            folded: Optional["FoldedItems"] = None):
         """`recommend` (or `recommend_with_items` with `folded`) with the catalogue of batch row b restricted to row
         row_seg[b] (int32 [B], device) of the table `elig`: als_recommend_topk_segmented in REC_BATCH chunks."""
-        if folded is None:
-            side = self._item_side(self._compose_for(features))
-            rows = self._fitted_rows(users_t, exclude_seen)
-        else:
-            side = self._joint_side(features, folded)
-            rows = self._joint_rows(users_t, exclude_seen, folded)
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
         return self._topk_chunks(users_t.numel(), N, rows, side, seg=(elig.table, row_seg))
 
     def recommend_new_eligible(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
                                elig, row_seg):
         """Fold in, then als_recommend_topk_segmented on the folded table, as `recommend_new`."""
-        Z = self._compose_for(features)
-        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
-        return self._topk_chunks(indptr.size - 1, N, rows, self._item_side(Z), seg=(elig.table, row_seg))
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._topk_chunks(indptr.size - 1, N, rows, side, seg=(elig.table, row_seg))
 
     def rank_of_eligible(self, us: torch.Tensor, is_: torch.Tensor, features, exclude_seen: bool, elig, pair_seg,
                          folded: Optional["FoldedItems"] = None):
         """`rank_of` among the items eligible for each pair's segment (pair_seg int32 [P], device; the pairs of a
         user agree on it - the facade checked): grouped by user as `rank_of`, the segment of a user's row that of
         its first pair, als_rank_count_segmented in REC_BATCH chunks."""
-        order, inv, uniq, counts, ptr, ptr_h = self._group_by_user(us)
-        row_seg = pair_seg[order][ptr[:-1]].contiguous()
-        if folded is None:
-            Z, side = self._compose_for(features), None
-            rows = self._fitted_rows(uniq, exclude_seen)
-        else:
-            side = self._joint_side(features, folded)
-            Z, rows = side["Z"], self._joint_rows(uniq, exclude_seen, folded)
-        above, ncand, score = self._rank_chunks(rows, ptr, ptr_h, is_[order].contiguous(), Z,
-                                                seg=(elig.table, row_seg), side=side)
-        return self._rank_outputs(above, ncand, counts, score, inv)
+        return self._rank_pairs(us, is_, features, exclude_seen, folded, elig=elig, pair_seg=pair_seg)
 
     # ------------------------------------------------------------ deep lists
-    def _deep_chunks(self, B: int, N: int, rows, items: dict, allow: Optional[torch.Tensor], after):
-        """als_recommend_deep over B batch rows in chunks (DEEP_BATCH, DEEP_WS_BYTES); `rows`, `items`, `allow` as in
-        `_topk_chunks`, `after` the validated (after_items int64 [B], after_scores float64 [B]) cursor or None.  Returns host (items
-        int64 [B, N], scores float64 [B, N]), copied chunk by chunk."""
+    def _deep_chunks(self, B: int, N: int, rows, items: dict, filters, after):
+        """als_recommend_deep over B batch rows in chunks (DEEP_BATCH, DEEP_WS_BYTES); `rows`, `items`, `filters` as
+        in `_topk_chunks`, `after` the validated (after_items int64 [B], after_scores float64 [B]) cursor or None.
+        Returns host (items int64 [B, N], scores float64 [B, N]), copied chunk by chunk."""
+        allow = self.allow_bitmap(filters, items["n"])
         keys = None if after is None else torch.from_numpy(cursor_keys(*after)).to(self.dev)
-        out_items = np.empty((B, N), dtype=np.int64)
-        out_scores = np.empty((B, N), dtype=np.float64)
         step = min(B, self.DEEP_BATCH, self.REC_BATCH)     # the chunk sources are sized for REC_BATCH rows at most
         while step > 1 and self.be.recommend_deep_workspace_bytes(step, items["n"], N) > self.DEEP_WS_BYTES:
             step = (step + 1) // 2
-        for b0 in range(0, B, step):
-            nb = min(step, B - b0)
+
+        def call(b0, nb, tv, ti, tc):
             users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
             self.be.recommend_deep(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, allow=allow,
                                    after_key=None if keys is None else keys[b0: b0 + nb], topn=N, top_val=tv,
                                    top_idx=ti, top_cnt=tc, **items)
-            out_items[b0: b0 + nb] = ti.cpu().numpy()
-            out_scores[b0: b0 + nb] = tv.cpu().numpy()
-        return out_items, out_scores
+        return self._collect_topn(B, N, step, call)
 
     def recommend_deep(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool,
                        folded: Optional["FoldedItems"] = None, filters=None, after=None):
         """`recommend` (or `recommend_with_items` with `folded`) for N up to RECOMMEND_DEEP_MAX_N, below the cursor
         `after` when given: als_recommend_deep in the chunks of `_deep_chunks`."""
-        if folded is None:
-            side = self._item_side(self._compose_for(features))
-            rows = self._fitted_rows(users_t, exclude_seen)
-        else:
-            side = self._joint_side(features, folded)
-            rows = self._joint_rows(users_t, exclude_seen, folded)
-        return self._deep_chunks(users_t.numel(), N, rows, side, self.allow_bitmap(filters, side["n"]), after)
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
+        return self._deep_chunks(users_t.numel(), N, rows, side, filters, after)
 
     def recommend_new_deep(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
                            filters=None, after=None):
         """Fold in, then als_recommend_deep on the folded table, as `recommend_new`."""
-        Z = self._compose_for(features)
-        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
-        return self._deep_chunks(indptr.size - 1, N, rows, self._item_side(Z), self.allow_bitmap(filters, self.n),
-                                 after)
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._deep_chunks(indptr.size - 1, N, rows, side, filters, after)
 
     # ------------------------------------------------------------ diversity
-    def _pool_chunks(self, B: int, N: int, pool: int, rows, items: dict, allow, with_stat: bool, rerank):
+    def _pool_chunks(self, B: int, N: int, pool: int, rows, items: dict, filters, with_stat: bool, rerank):
         """The pool - `_topk_chunks` with N = pool, kept on the device - re-ranked in REC_BATCH chunks by
         rerank(b0, nb, cand_val, cand_idx, top_val, top_idx, top_cnt, stat): the chunk's pool rows, its [nb, N] outputs
         and `stat`, a fp32 [nb] per-list statistic the kernel writes (None without `with_stat`).  Only the [B, N]
         results come back: (items int64, scores float64, and the statistic float64 [B] or None)."""
-        pool_val, pool_idx = self._topk_chunks(B, pool, rows, items, on_device=True, allow=allow)
-        out_items = np.empty((B, N), dtype=np.int64)
-        out_scores = np.empty((B, N), dtype=np.float64)
-        out_stat = np.empty(B, dtype=np.float64) if with_stat else None
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
+        pool_val, pool_idx = self._topk_chunks(B, pool, rows, items, on_device=True, filters=filters)
+
+        def call(b0, nb, tv, ti, tc):
             stat = torch.empty(nb, dtype=torch.float32, device=self.dev) if with_stat else None
             rerank(b0, nb, pool_val[b0: b0 + nb], pool_idx[b0: b0 + nb], tv, ti, tc, stat)
-            out_items[b0: b0 + nb] = ti.cpu().numpy()
-            out_scores[b0: b0 + nb] = tv.cpu().numpy()
-            if with_stat:
-                out_stat[b0: b0 + nb] = stat.cpu().numpy()
-        return out_items, out_scores, out_stat
+            return (stat,) if with_stat else ()
+        out = self._collect_topn(B, N, self.REC_BATCH, call, extra=((),) if with_stat else ())
+        return out if with_stat else (*out, None)
 
-    def _rerank_chunks(self, B: int, N: int, pool: int, lam: float, rows, items: dict, allow, with_ild: bool):
+    def _rerank_chunks(self, B: int, N: int, pool: int, lam: float, rows, items: dict, filters, with_ild: bool):
         """`_pool_chunks` with als_mmr_rerank against the Z the pool was scored with: (items int64, scores float64,
         and ild float64 [B] or None)."""
         def rerank(b0, nb, cand_val, cand_idx, tv, ti, tc, ild):
             self.be.mmr_rerank(k=items["k"], ld=items["ld"], n=items["n"], Z=items["Z"], cand_val=cand_val,
                                cand_idx=cand_idx, lam=lam, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_ild=ild)
-        return self._pool_chunks(B, N, pool, rows, items, allow, with_ild, rerank)
+        return self._pool_chunks(B, N, pool, rows, items, filters, with_ild, rerank)
 
     def recommend_diverse(self, users_t: torch.Tensor, N: int, pool: int, lam: float, features, exclude_seen: bool,
                           folded: Optional["FoldedItems"] = None, filters=None, with_ild: bool = False):
         """`recommend(N=pool)` (or `recommend_with_items` with `folded`) on the device, then the MMR re-rank."""
-        if folded is None:
-            side = self._item_side(self._compose_for(features))
-            rows = self._fitted_rows(users_t, exclude_seen)
-        else:
-            side = self._joint_side(features, folded)
-            rows = self._joint_rows(users_t, exclude_seen, folded)
-        return self._rerank_chunks(users_t.numel(), N, pool, lam, rows, side, self.allow_bitmap(filters, side["n"]),
-                                   with_ild)
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
+        return self._rerank_chunks(users_t.numel(), N, pool, lam, rows, side, filters, with_ild)
 
     def recommend_new_diverse(self, indptr, indices, vals, N: int, pool: int, lam: float, features, n_sweeps: int,
                               exclude_seen: bool, filters=None, with_ild: bool = False):
         """`recommend_new(N=pool)` on the device, then the MMR re-rank."""
-        Z = self._compose_for(features)
-        rows = self._folded_rows(indptr, indices, vals, Z, n_sweeps, exclude_seen)
-        return self._rerank_chunks(indptr.size - 1, N, pool, lam, rows, self._item_side(Z),
-                                   self.allow_bitmap(filters, self.n), with_ild)
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._rerank_chunks(indptr.size - 1, N, pool, lam, rows, side, filters, with_ild)
 
     def list_diversity(self, lists: torch.Tensor, features, folded: Optional["FoldedItems"] = None) -> np.ndarray:
         """ILD float64 [B] of the id lists `lists` (int32 [B, L], -1 padded, device): als_list_diversity in
         REC_BATCH chunks against the Z of `recommend` (the joint table with `folded`)."""
-        side = self._item_side(self._compose_for(features)) if folded is None else self._joint_side(features, folded)
-        B = lists.shape[0]
-        out = np.empty(B, dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
+        side = self._side(features, folded)
+
+        def call(b0, nb):
             ild = torch.empty(nb, dtype=torch.float32, device=self.dev)
             self.be.list_diversity(k=side["k"], ld=side["ld"], n=side["n"], Z=side["Z"], idx=lists[b0: b0 + nb],
                                    ild=ild)
-            out[b0: b0 + nb] = ild.cpu().numpy()
-        return out
+            return (ild,)
+        return self._collect(lists.shape[0], self.REC_BATCH, (((), np.float64),), call)[0]
 
     # ---------------------------------------------------------- calibration
     def _fitted_history(self, users_t: torch.Tensor):
@@ -756,7 +744,7 @@ class _Serving:
         self.be.category_profile(ncat=ncat, indptr=indptr, indices=indices, rows=rows, n=C.shape[0], C=C, P_out=P)
         return P
 
-    def _calibrate_chunks(self, B: int, N: int, pool: int, lam: float, alpha: float, rows, items: dict, allow,
+    def _calibrate_chunks(self, B: int, N: int, pool: int, lam: float, alpha: float, rows, items: dict, filters,
                           table: np.ndarray, ncat: int, hist, target: Optional[np.ndarray], with_kl: bool):
         """`_pool_chunks` with als_calibrated_rerank over the category table `table` (validate.category_table of the
         catalogue scored, uploaded once): per chunk the targets are the rows of `target` (validate.target_rows) or,
@@ -769,21 +757,15 @@ class _Serving:
             P = T[b0: b0 + nb] if T is not None else self._profile_chunk(C, ncat, hist, b0, nb)
             self.be.calibrated_rerank(ncat=ncat, n=items["n"], C=C, P=P, cand_val=cand_val, cand_idx=cand_idx,
                                       lam=lam, alpha=alpha, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_kl=kl)
-        return self._pool_chunks(B, N, pool, rows, items, allow, with_kl, rerank)
+        return self._pool_chunks(B, N, pool, rows, items, filters, with_kl, rerank)
 
     def recommend_calibrated(self, users_t: torch.Tensor, N: int, pool: int, lam: float, alpha: float,
                              table: np.ndarray, ncat: int, target, features, exclude_seen: bool,
                              folded: Optional["FoldedItems"] = None, filters=None, with_kl: bool = False):
         """`recommend(N=pool)` (or `recommend_with_items` with `folded`) on the device, then the calibrated re-rank
         towards the profile of the user's training row (or `target`)."""
-        if folded is None:
-            side = self._item_side(self._compose_for(features))
-            rows = self._fitted_rows(users_t, exclude_seen)
-        else:
-            side = self._joint_side(features, folded)
-            rows = self._joint_rows(users_t, exclude_seen, folded)
-        return self._calibrate_chunks(users_t.numel(), N, pool, lam, alpha, rows, side,
-                                      self.allow_bitmap(filters, side["n"]), table, ncat,
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
+        return self._calibrate_chunks(users_t.numel(), N, pool, lam, alpha, rows, side, filters, table, ncat,
                                       self._fitted_history(users_t), target, with_kl)
 
     def recommend_new_calibrated(self, indptr, indices, vals, N: int, pool: int, lam: float, alpha: float,
@@ -791,12 +773,8 @@ class _Serving:
                                  filters=None, with_kl: bool = False):
         """`recommend_new(N=pool)` on the device, then the calibrated re-rank towards the profile of the given
         ratings (or `target`)."""
-        Z = self._compose_for(features)
-        B = indptr.size - 1
-        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
-        rows = self._table_rows(B, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
-        return self._calibrate_chunks(B, N, pool, lam, alpha, rows, self._item_side(Z),
-                                      self.allow_bitmap(filters, self.n), table, ncat,
+        side, rows, ptr_d, idx_d = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._calibrate_chunks(indptr.size - 1, N, pool, lam, alpha, rows, side, filters, table, ncat,
                                       self._table_history(ptr_d, idx_d), target, with_kl)
 
     def category_profile(self, users_t: torch.Tensor, table: np.ndarray, ncat: int) -> np.ndarray:
@@ -804,12 +782,8 @@ class _Serving:
         als_category_profile in REC_BATCH chunks."""
         C = torch.from_numpy(table).to(self.dev)
         hist = self._fitted_history(users_t)
-        B = users_t.numel()
-        out = np.empty((B, ncat), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            out[b0: b0 + nb] = self._profile_chunk(C, ncat, hist, b0, nb)[:, :ncat].cpu().numpy()
-        return out
+        return self._collect(users_t.numel(), self.REC_BATCH, (((ncat,), np.float64),),
+                             lambda b0, nb: (self._profile_chunk(C, ncat, hist, b0, nb)[:, :ncat],))[0]
 
     def list_miscalibration(self, lists: torch.Tensor, table: np.ndarray, ncat: int, alpha: float,
                             users_t: Optional[torch.Tensor], target: Optional[np.ndarray]) -> np.ndarray:
@@ -818,44 +792,36 @@ class _Serving:
         C = torch.from_numpy(table).to(self.dev)
         T = None if target is None else torch.from_numpy(target).to(self.dev)
         hist = None if users_t is None else self._fitted_history(users_t)
-        B = lists.shape[0]
-        out = np.empty(B, dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
+
+        def call(b0, nb):
             P = T[b0: b0 + nb] if T is not None else self._profile_chunk(C, ncat, hist, b0, nb)
             kl = torch.empty(nb, dtype=torch.float32, device=self.dev)
             self.be.list_miscalibration(ncat=ncat, n=C.shape[0], C=C, P=P, idx=lists[b0: b0 + nb], alpha=alpha, kl=kl)
-            out[b0: b0 + nb] = kl.cpu().numpy()
-        return out
+            return (kl,)
+        return self._collect(lists.shape[0], self.REC_BATCH, (((), np.float64),), call)[0]
 
     # ----------------------------------------------------------- neighbours
-    def _similar_chunks(self, T: torch.Tensor, ids: torch.Tensor, N: int, allow: Optional[torch.Tensor] = None):
+    def _similar_chunks(self, T: torch.Tensor, ids: torch.Tensor, N: int, filters=None):
         """The N rows of the table T [rows, ld] most similar (cosine) to each of its rows `ids` (int32, device), a row
         never its own neighbour: one als_row_inv_norms launch over T per call (nothing is kept between calls, so a
-        refit or other features cannot meet stale norms), then als_similar_topk in REC_BATCH chunks.  `allow`: the
-        bitmap of the call (`allow_bitmap`) or None.  Returns host (ids int64 [B, N], sims float64 [B, N]), unused
+        refit or other features cannot meet stale norms), then als_similar_topk in REC_BATCH chunks.  `filters`: as
+        in `_topk_chunks`, over the rows of T.  Returns host (ids int64 [B, N], sims float64 [B, N]), unused
         slots -1 / -inf."""
         B, rows = ids.numel(), T.shape[0]
+        allow = self.allow_bitmap(filters, rows)
         inv = torch.empty(rows, dtype=torch.float32, device=self.dev)
         self.be.row_inv_norms(k=self.k, ld=self.ld, T=T, inv_norm=inv)
-        out_ids = np.empty((B, N), dtype=np.int64)
-        out_sims = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
+
+        def call(b0, nb, tv, ti, tc):
             q = ids[b0: b0 + nb]
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
             self.be.similar_topk(k=self.k, ld=self.ld, q_ids=q, Q=T, q_inv=inv, self_ids=q, n=rows, T=T, t_inv=inv,
                                  allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc)
-            out_ids[b0: b0 + nb] = ti.cpu().numpy()
-            out_sims[b0: b0 + nb] = tv.cpu().numpy()
-        return out_ids, out_sims
+        return self._collect_topn(B, N, self.REC_BATCH, call)
 
     def similar_items(self, items_t: torch.Tensor, N: int, features, filters=None):
         """Nearest items of the items `items_t` (int32, device) by the cosine of their rows of Z, composed as in
         `list_diversity`; `filters` restricts the neighbours, not the queries."""
-        return self._similar_chunks(self._compose_for(features), items_t, N, self.allow_bitmap(filters, self.n))
+        return self._similar_chunks(self._compose_for(features), items_t, N, filters)
 
     def similar_users(self, users_t: torch.Tensor, N: int):
         """Nearest users of the users `users_t` (int32, device) by the cosine of their rows of U."""
@@ -883,27 +849,15 @@ class _Serving:
         int64 [B, N], scores float64 [B, N]), unused slots -1 / -inf - als_audience_topk in REC_BATCH chunks.  The
         query table is the Z of `predict` (the joint table of `_joint_side` with `folded`), the raters left out are
         `_rater_rows`; `filters`: the validated user allow / block pair of the call over the m users, or None."""
-        if folded is None:
-            Q, q_bias = self._compose_for(features), self.b_i
-        else:
-            side = self._joint_side(features, folded)
-            Q, q_bias = side["Z"], side["b_i"]
+        side = self._side(features, folded)
         seen_ptr, seen_idx = self._rater_rows(folded) if exclude_seen else (None, None)
         allow = self.allow_bitmap(filters, self.m)
-        B = items_t.numel()
-        out_users = np.empty((B, N), dtype=np.int64)
-        out_scores = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, self.REC_BATCH):
-            nb = min(self.REC_BATCH, B - b0)
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
-            self.be.audience_topk(k=self.k, ld=self.ld, q_ids=items_t[b0: b0 + nb], Q=Q, q_bias=q_bias, m=self.m,
-                                  U=self.U, b_u=self.b_u, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx,
+
+        def call(b0, nb, tv, ti, tc):
+            self.be.audience_topk(k=self.k, ld=self.ld, q_ids=items_t[b0: b0 + nb], Q=side["Z"], q_bias=side["b_i"],
+                                  m=self.m, U=self.U, b_u=self.b_u, mu=self.mu, seen_ptr=seen_ptr, seen_idx=seen_idx,
                                   allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc)
-            out_users[b0: b0 + nb] = ti.cpu().numpy()
-            out_scores[b0: b0 + nb] = tv.cpu().numpy()
-        return out_users, out_scores
+        return self._collect_topn(items_t.numel(), N, self.REC_BATCH, call)
 
     # --------------------------------------------------------------- groups
     def _group_seen(self, members: torch.Tensor, ptr: torch.Tensor, n_total: int, new_u: torch.Tensor,
@@ -931,41 +885,24 @@ class _Serving:
         chunks of groups.  The item tables are the Z of `predict` (the joint table of `_joint_side` with `folded`);
         the members index the resident U / b_u; per chunk the seen rows of the groups are `_group_seen`; `filters`:
         the validated item allow / block pair of the call over the catalogue scored, or None."""
-        side = self._item_side(self._compose_for(features)) if folded is None else self._joint_side(features, folded)
+        side = self._side(features, folded)
         allow = self.allow_bitmap(filters, side["n"])
-        G = g_ptr.size - 1
         sizes = np.diff(g_ptr)
         ptr_d = torch.from_numpy(g_ptr).to(self.dev)
         users_d = torch.from_numpy(g_users).to(self.dev)
-        new_u = torch.empty(0, dtype=torch.int64, device=self.dev)
-        new_i = torch.empty(0, dtype=torch.int32, device=self.dev)
-        if exclude_seen and folded is not None:
-            # the folded items' raters, transposed: (user, n + b) pairs sorted by user, then item (as `_joint_rows`)
-            rp, ri = folded.ratings[0], folded.ratings[1]
-            fu = ri.astype(np.int64)
-            fi = self.n + np.repeat(np.arange(folded.n_items, dtype=np.int64), np.diff(rp))
-            o = np.lexsort((fi, fu))
-            new_u = torch.from_numpy(fu[o]).to(self.dev)
-            new_i = torch.from_numpy(fi[o].astype(np.int32)).to(self.dev)
-        out_items = np.empty((G, N), dtype=np.int64)
-        out_scores = np.empty((G, N), dtype=np.float64)
-        for b0 in range(0, G, self.REC_BATCH):
-            nb = min(self.REC_BATCH, G - b0)
+        new_u, new_i = self._folded_rater_pairs(folded if exclude_seen else None)
+
+        def call(b0, nb, tv, ti, tc):
             p0, p1 = int(g_ptr[b0]), int(g_ptr[b0 + nb])
             ptr = (ptr_d[b0: b0 + nb + 1] - p0).contiguous()
             members = users_d[p0:p1]
             seen_ptr = seen_idx = None
             if exclude_seen and (self.nnz > 0 or new_u.numel() > 0):
                 seen_ptr, seen_idx = self._group_seen(members, ptr, side["n"], new_u, new_i)
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
             self.be.group_topk(g_ptr=ptr, g_users=members, max_members=int(sizes[b0: b0 + nb].max()), U=self.U,
                                b_u=self.b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, allow=allow, aggregate=aggregate,
                                topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **side)
-            out_items[b0: b0 + nb] = ti.cpu().numpy()
-            out_scores[b0: b0 + nb] = tv.cpu().numpy()
-        return out_items, out_scores
+        return self._collect_topn(g_ptr.size - 1, N, self.REC_BATCH, call)
 
     def _merged_seen(self, us: torch.Tensor, new_u: torch.Tensor, new_i: torch.Tensor):
         """Seen CSR of batch rows r = user us[r] (device): the user's training row, then the folded items
@@ -1001,49 +938,39 @@ class _Serving:
         eps [B, ld] standard normal, zero in the padding columns) - cov(W^T eps) = W^T W = A^-1."""
         return U + beta * torch.bmm(W.transpose(1, 2), eps.unsqueeze(2)).squeeze(2)
 
-    def _explore_chunks(self, B: int, N: int, beta: float, eps, rows, table_rows, wrows, items: dict, allow, row_name):
+    def _explore_chunks(self, B: int, N: int, beta: float, eps, rows, table_rows, wrows, items: dict, filters,
+                        row_name):
         """als_row_whitener + als_explore_topk over B batch rows in chunks of `EXPLORE_BATCH` rows.  rows(b0, nb) as in
-        `_topk_chunks` (the seen CSR by USER ID); wrows(b0, nb) -> (indptr, indices, rows) of the whitener's work
-        rows; `eps` (fp32 [B, ld], device) switches to Thompson sampling: table_rows(b0, nb) -> (U, b_u, seen_ptr,
-        seen_idx) gathered by BATCH ROW, the sampled table of `thompson_table` goes through als_recommend_topk and the
-        leverages of the returned items are formed from W in torch.  Returns host (items int64, keys float64,
-        leverage float64), each [B, N], unused slots -1 / -inf / 0."""
+        `_topk_chunks` (the seen CSR by USER ID), as are `items` and `filters`; wrows(b0, nb) -> (indptr, indices,
+        rows) of the whitener's work rows; `eps` (fp32 [B, ld], device) switches to Thompson sampling: table_rows(b0,
+        nb) -> (U, b_u, seen_ptr, seen_idx) gathered by BATCH ROW, the sampled table of `thompson_table` goes through
+        als_recommend_topk and the leverages of the returned items are formed from W in torch.  Returns host (items
+        int64, keys float64, leverage float64), each [B, N], unused slots -1 / -inf / 0."""
         md, ld = self.model, self.ld
+        allow = self.allow_bitmap(filters, items["n"])
         cb = min(self.REC_BATCH, self.EXPLORE_BATCH or max(1, self.EXPLORE_W_BYTES // (4 * ld * ld)))
         W = torch.empty(min(B, cb), ld, ld, dtype=torch.float32, device=self.dev)
         status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        out_items = np.empty((B, N), dtype=np.int64)
-        out_keys = np.empty((B, N), dtype=np.float64)
-        out_lev = np.empty((B, N), dtype=np.float64)
-        for b0 in range(0, B, cb):
-            nb = min(cb, B - b0)
+
+        def call(b0, nb, tv, ti, tc):
             indptr, indices, wr = wrows(b0, nb)
             self.be.row_whitener(k=self.k, ld=ld, indptr=indptr, indices=indices, rows=wr, n=self.n, Z=items["Z"],
                                  lam_u=md.lambda_u, W_out=W, status=status)
             _raise_unless_solved(status, "explore", lambda r: row_name(b0 + r))
-            tv = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
-            ti = torch.empty(nb, N, dtype=torch.int32, device=self.dev)
-            tc = torch.empty(nb, dtype=torch.int32, device=self.dev)
             if eps is None:
                 tl = torch.empty(nb, N, dtype=torch.float32, device=self.dev)
                 users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
                 self.be.explore_topk(users=users, U=U, b_u=b_u, W=W, beta=beta, seen_ptr=seen_ptr, seen_idx=seen_idx,
                                      allow=allow, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, top_lev=tl, **items)
-            else:
-                U, b_u, seen_ptr, seen_idx = table_rows(b0, nb)
-                kw = dict(users=torch.arange(nb, dtype=torch.int32, device=self.dev),
-                          U=self.thompson_table(U[:nb], W[:nb], eps[b0: b0 + nb], beta).contiguous(), b_u=b_u,
-                          seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
-                if allow is None:
-                    self.be.recommend_topk(**kw)
-                else:
-                    self.be.recommend_topk_masked(allow=allow, **kw)
-                y = torch.bmm(items["Z"][ti.clamp(min=0).to(torch.int64)], W[:nb].transpose(1, 2))     # [nb, N, ld]
-                tl = torch.where(ti >= 0, (y * y).sum(dim=2), torch.zeros((), device=self.dev))
-            out_items[b0: b0 + nb] = ti.cpu().numpy()
-            out_keys[b0: b0 + nb] = tv.cpu().numpy()
-            out_lev[b0: b0 + nb] = tl.cpu().numpy()
-        return out_items, out_keys, out_lev
+                return (tl,)
+            U, b_u, seen_ptr, seen_idx = table_rows(b0, nb)
+            self._restricted("recommend_topk", allow, None, b0, nb,
+                             users=torch.arange(nb, dtype=torch.int32, device=self.dev),
+                             U=self.thompson_table(U[:nb], W[:nb], eps[b0: b0 + nb], beta).contiguous(), b_u=b_u,
+                             seen_ptr=seen_ptr, seen_idx=seen_idx, topn=N, top_val=tv, top_idx=ti, top_cnt=tc, **items)
+            y = torch.bmm(items["Z"][ti.clamp(min=0).to(torch.int64)], W[:nb].transpose(1, 2))         # [nb, N, ld]
+            return (torch.where(ti >= 0, (y * y).sum(dim=2), torch.zeros((), device=self.dev)),)
+        return self._collect_topn(B, N, cb, call, extra=((N,),))
 
     def _thompson_eps(self, B: int, seed) -> Optional[torch.Tensor]:
         """default_rng(seed).standard_normal((B, k)) as fp32 on the device, zero padded to ld; None without a seed."""
@@ -1062,29 +989,22 @@ class _Serving:
         B = users_t.numel()
         ptr_d, idx_d, _ = self._csr_dev(self.csr.indptr, self.csr.indices, self.csr.vals)
         with_seen = exclude_seen and self.nnz > 0
-        none_u = torch.empty(0, dtype=torch.int64, device=self.dev)
-        none_i = torch.empty(0, dtype=torch.int32, device=self.dev)
+        no_pairs = self._folded_rater_pairs(None)
 
         def table_rows(b0, nb):
             us = users_t[b0: b0 + nb].to(torch.int64)
-            seen = self._merged_seen(us, none_u, none_i) if with_seen else (None, None)
+            seen = self._merged_seen(us, *no_pairs) if with_seen else (None, None)
             return (self.U.index_select(0, us), self.b_u.index_select(0, us), *seen)
         return self._explore_chunks(B, N, beta, self._thompson_eps(B, seed), self._fitted_rows(users_t, exclude_seen),
                                     table_rows, lambda b0, nb: (ptr_d, idx_d, users_t[b0: b0 + nb]),
-                                    self._item_side(Z), self.allow_bitmap(filters, self.n),
+                                    self._item_side(Z), filters,
                                     lambda w: f"user {int(users_t[w])}")
 
     def recommend_new_explore(self, indptr, indices, vals, N: int, beta: float, seed, features, n_sweeps: int,
                               exclude_seen: bool, filters=None):
         """`recommend_explore` for rows outside the fit (host CSR, rows sorted): fold in, whiten the same rows, rank."""
-        Z = self._compose_for(features)
         B = indptr.size - 1
-        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
-        rows = self._table_rows(B, U, b, (indptr, ptr_d, idx_d) if exclude_seen else None)
-
-        def table_rows(b0, nb):
-            _, Uc, bc, seen_ptr, seen_idx = rows(b0, nb)
-            return Uc, bc, seen_ptr, seen_idx
-        return self._explore_chunks(B, N, beta, self._thompson_eps(B, seed), rows, table_rows,
-                                    lambda b0, nb: (ptr_d[b0: b0 + nb + 1], idx_d, None), self._item_side(Z),
-                                    self.allow_bitmap(filters, self.n), lambda w: f"row {w}")
+        side, rows, ptr_d, idx_d = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._explore_chunks(B, N, beta, self._thompson_eps(B, seed), rows, lambda b0, nb: rows(b0, nb)[1:],
+                                    lambda b0, nb: (ptr_d[b0: b0 + nb + 1], idx_d, None), side,
+                                    filters, lambda w: f"row {w}")
