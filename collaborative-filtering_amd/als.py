@@ -40,7 +40,7 @@ from .containers import FitCache, _SideDev, _TasksDev, _side_to_dev, _tasks_to_d
 from .engine import EPS, SCALE_FACTOR, W_F64_BELOW, SweepNotResident, _Engine  # noqa: F401
 from . import serving
 from .serving import RECOMMEND_DEEP_MAX_N, RECOMMEND_MAX_N, Explanation, FoldedItems, _Serving, concat_features  # noqa: F401
-from .serving import ItemEligibility
+from .serving import CapacityInfo, ItemEligibility  # noqa: F401
 from .validate import _as_side, _check_csr, _validate_graph  # noqa: F401
 from .validate import fold_in_csr, new_item_features, new_item_graph_csr  # noqa: F401
 from .validate import host_features as _host_features
@@ -445,6 +445,74 @@ class ALS:
         with _on(self._eng.dev):
             return self._eng.rank_of_eligible(self._dev_i32(u), self._dev_i32(i), features, exclude_seen, elig,
                                               self._dev_i32(seg), new_items)
+
+    # -------------------------------------------------------- exposure caps
+    def recommend_capacity(self, users=None, N: int = 10, *, capacity,
+                           features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                           new_items: Optional[FoldedItems] = None, items=None, filter_items=None,
+                           max_rounds: Optional[int] = None, return_info: bool = False):
+        """Top-N lists for a whole batch under per-item exposure caps: item i appears in at most capacity[i] of the B
+        lists (stock on hand, seats, a campaign budget, a per-provider cap).  Returns (items int64 [B, N], scores
+        float64 [B, N]) padded with -1 / -inf, and with `return_info` a `CapacityInfo` (rounds, walked_rows, fill,
+        cutoff) as a third value.
+
+        `capacity`: an int array with one entry >= 0 per item (n entries, n + B with `new_items`), or an int scalar -
+        the same cap for every item.  None is not accepted.  Batch row b is users[b]; duplicates are separate rows and
+        each consumes capacity.  Everything else means what it means in `recommend`.
+
+        Definition: the candidate pairs (row b, item i) are `recommend`'s - not seen, allowed, score not NaN - with
+        capacity[i] > 0, scored bitwise as `predict`.  They are scanned once in the order (score descending, batch row
+        ascending, item ascending), and (b, i) is taken if row b holds fewer than N items and item i was taken fewer
+        than capacity[i] times.  Row b's list is its taken items in that order.  This is the greedy 1/2-approximation
+        of max-weight b-matching, and the unique stable assignment.  With every capacity >= B it is `recommend`,
+        element for element.
+
+        It is computed on the device in threshold rounds (als_recommend_topk_priced, als_capacity_settle; DESIGN.md
+        section 29): round 0 is one fused walk of all rows; every later round re-walks only the rows that lost an
+        item.  The host reads four bytes per round.  `max_rounds`: None runs to the fixed point (it is always reached);
+        an int raises RuntimeError when items are still over-demanded after that many rounds.  B N is limited to
+        serving.CAPACITY_MAX_PAIRS list slots.  Local to the calling rank."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        n_total = self._n_total(new_items)
+        u = validate.user_ids(users, self.U.shape[0])
+        cap = validate.item_capacity(capacity, n_total)
+        filters = validate.capacity_filters(validate.item_filters(items, filter_items, n_total), cap)
+        max_rounds = validate.max_rounds_arg(max_rounds)
+        if u.size == 0:
+            return self._capacity_result((np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64),
+                                          serving.CapacityInfo(0, 0, np.zeros(n_total, np.int64),
+                                                               np.full(n_total, np.nan))), return_info)
+        with _on(self._eng.dev):
+            return self._capacity_result(self._eng.recommend_capacity(self._dev_i32(u), N, features, exclude_seen, cap,
+                                                                      new_items, filters, max_rounds), return_info)
+
+    @staticmethod
+    def _capacity_result(out, return_info: bool):
+        return out if return_info else out[:2]
+
+    def recommend_new_capacity(self, R_new, N: int = 10, *, capacity,
+                               features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                               exclude_seen: bool = True, items=None, filter_items=None,
+                               max_rounds: Optional[int] = None, return_info: bool = False):
+        """`recommend_capacity` for users outside the fit: `fold_in(R_new, ...)` as in `recommend_new`, then the
+        definition of `recommend_capacity` with batch row b = row b of R_new; `capacity` spans the n fitted items."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        T = validate.sweeps(n_sweeps)
+        n = self.V.shape[0]
+        indptr, indices, vals = fold_in_csr(R_new, n)
+        cap = validate.item_capacity(capacity, n)
+        filters = validate.capacity_filters(validate.item_filters(items, filter_items, n), cap)
+        max_rounds = validate.max_rounds_arg(max_rounds)
+        if indptr.size == 1:
+            return self._capacity_result((np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64),
+                                          serving.CapacityInfo(0, 0, np.zeros(n, np.int64), np.full(n, np.nan))),
+                                         return_info)
+        with _on(self._eng.dev):
+            return self._capacity_result(self._eng.recommend_new_capacity(indptr, indices, vals, N, features, T,
+                                                                          exclude_seen, cap, filters, max_rounds),
+                                         return_info)
 
     # ----------------------------------------------------------- deep lists
     def recommend_deep(self, users=None, N: int = 500, *, features: Optional[Dict[str, np.ndarray]] = None,

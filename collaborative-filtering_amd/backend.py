@@ -437,6 +437,45 @@ class HipBackend:
                                                      self._bitmap(base_allow, n), _p(out), self._stream()),
                     "als_eligibility_bitmaps")
 
+    @staticmethod
+    def _keys(t: torch.Tensor, n: int, what: str):
+        """Pointer to n 64-bit keys carried as int64 bit patterns (as `recommend_deep` carries after_key), checked."""
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"{what} must be a contiguous int64 device tensor of {n} keys")
+        return _p(t)
+
+    def recommend_topk_priced(self, *, k, ld, users, row_ids, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow,
+                              floor_key, topn, top_val, top_idx, top_cnt):
+        """`recommend_topk_masked` (allow None: every item) where launched row b takes item i only if its item-side key
+        make_key(score, row_ids[b]) is >= floor_key[i]: als_recommend_topk_priced.  row_ids int32 [B]: the batch row of
+        every launched row; floor_key int64 [n]: the bits of the 64-bit floors."""
+        if row_ids.dtype != torch.int32 or not row_ids.is_cuda or not row_ids.is_contiguous() \
+                or row_ids.numel() != users.numel():
+            raise ValueError("row_ids must be a contiguous int32 device tensor with one batch row per launched row")
+        self._recommend(self.lib.als_recommend_topk_priced, "als_recommend_topk_priced",
+                        (self._bitmap(allow, n), _p(row_ids), self._keys(floor_key, n, "floor_key")), k, ld, users, n,
+                        U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val, top_idx, top_cnt)
+
+    def capacity_settle(self, *, n, top_idx, top_val, capacity, floor_key, fill, dirty, n_over):
+        """From the whole batch's lists (top_idx int32 / top_val fp32 [B, topn]) and capacity int32 [n]: fill int32 [n] =
+        min(demand, capacity), the floors (int64 [n], in / out) of the over-demanded items raised to their
+        capacity-th largest item-side key, dirty int32 [B] = the row holds an item it no longer passes, n_over int32 [1]
+        = the over-demanded items: als_capacity_settle.  No host synchronisation; the workspace is owned here."""
+        B, topn = top_idx.shape
+        for t, dt, num in ((top_idx, torch.int32, B * topn), (top_val, torch.float32, B * topn),
+                           (capacity, torch.int32, n), (fill, torch.int32, n), (dirty, torch.int32, B),
+                           (n_over, torch.int32, 1)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() != num:
+                raise ValueError("capacity_settle: the lists, capacity, fill, dirty and n_over must be contiguous device "
+                                 "tensors of their documented dtypes and sizes")
+        need = int(self.lib.als_capacity_settle_workspace_bytes(B, n, topn))
+        if need == 0:
+            raise ValueError("capacity_settle: B * topn and n must be below 2^31")
+        self._check(self.lib.als_capacity_settle(B, topn, n, _p(top_idx), _p(top_val), _p(capacity),
+                                                 self._keys(floor_key, n, "floor_key"), _p(fill), _p(dirty), _p(n_over),
+                                                 self._workspace("capacity_settle", need), need, self._stream()),
+                    "als_capacity_settle")
+
     def _rank(self, fn, what, allow, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items,
               t_score, above, n_cand):
         if seen_idx is not None and seen_idx.numel() == 0:

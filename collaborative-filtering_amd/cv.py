@@ -279,6 +279,46 @@ def calibration_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, categori
     return {"users": int(users.size), "profiled_users": int(known.sum()), "calibrations": out, **extra}
 
 
+def capacity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, capacity, min_rating: Optional[float] = None,
+                  features: Optional[Dict[str, np.ndarray]] = None, items=None, filter_items=None) -> Dict[str, Any]:
+    """What exposure caps cost and buy: `model.recommend_capacity(users, K, capacity=capacity)` over the users of the
+    held-out (user, item) pairs - one batch, every user one row - next to the uncapped `model.recommend`:
+    {"users", "recall@K", "ndcg@K", "recall@K_uncapped", "ndcg@K_uncapped", "coverage@K", "coverage@K_uncapped",
+    "max_exposure", "gini_exposure", "max_exposure_uncapped", "gini_exposure_uncapped", "rounds", "walked_rows"} (plus
+    "filtered_out" with `items` / `filter_items`).
+
+    users, rel(u), recall@K and NDCG@K are `ranking_at_k`'s (same arguments, same pairs left out); the uncapped values
+    equal `ranking_at_k`'s.  The exposure of an item is the number of lists that hold it: coverage@K is the share of
+    the allowed catalogue with exposure > 0, max_exposure the largest exposure (<= the item's cap under caps), and
+    gini_exposure the Gini coefficient of the exposures over the allowed catalogue (0: every item shown equally
+    often; towards 1: a few items take all the slots; NaN when nothing is shown).  `rounds` and `walked_rows` are the
+    call's `CapacityInfo` values."""
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
+    validate.fitted(model)
+    n = model.V.shape[0]
+    cap = validate.item_capacity(capacity, n)
+    nan = float("nan")
+    names = ("recall@K", "ndcg@K", "coverage@K", "max_exposure", "gini_exposure")
+    if users.size == 0:
+        return {"users": 0, **{f"{k}{s}": nan for k in names for s in ("", "_uncapped")}, "rounds": 0,
+                "walked_rows": 0, **extra}
+    allowed = validate.allowed_mask(validate.item_filters(items, filter_items, n), n) if kw else np.ones(n, dtype=bool)
+
+    def measures(top):
+        exposure = np.sort(np.bincount(top[top >= 0], minlength=n)[allowed].astype(np.float64))
+        na, total = exposure.size, exposure.sum()
+        gini = (2.0 * (np.arange(1, na + 1) * exposure).sum() / (na * total) - (na + 1) / na) if total > 0 else nan
+        m = _ranking_metrics(top, ub, cols, n, K)
+        return {"recall@K": m["recall@K"], "ndcg@K": m["ndcg@K"],
+                "coverage@K": float((exposure > 0).sum() / na) if na else nan,
+                "max_exposure": int(exposure[-1]) if na else 0, "gini_exposure": float(gini)}
+    top, _, info = model.recommend_capacity(users, K, capacity=cap, features=features, return_info=True, **kw)
+    capped = measures(top)
+    plain = measures(model.recommend(users, K, features=features, **kw)[0])
+    return {"users": int(users.size), **capped, **{f"{k}_uncapped": v for k, v in plain.items()},
+            "rounds": info.rounds, "walked_rows": info.walked_rows, **extra}
+
+
 def audience_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
                   features: Optional[Dict[str, np.ndarray]] = None, users=None, filter_users=None) -> Dict[str, Any]:
     """recall@K and NDCG@K of `model.recommend_users` on held-out (user, item) pairs: `ranking_at_k` per ITEM - is

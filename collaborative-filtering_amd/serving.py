@@ -1,7 +1,8 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
 `recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile`, `list_miscalibration` and
-`recommend*_deep`, and the per-user eligibility calls (`eligibility`, `recommend*_eligible`, `rank_of_eligible`).
+`recommend*_deep`, the per-user eligibility calls (`eligibility`, `recommend*_eligible`, `rank_of_eligible`) and the
+capped batch lists (`recommend*_capacity`).
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -24,6 +25,9 @@ from . import layout
 RECOMMEND_MAX_N = 128   # ALS_TOPK_MAX: longest list of ALS.recommend
 RECOMMEND_DEEP_MAX_N = 1024     # ALS_TOPK_DEEP_MAX: longest list of ALS.recommend_deep
 ELIGIBILITY_MAX_BYTES = 1 << 30     # largest eligibility table ALS.eligibility builds (4 S ceil(n / 32) bytes)
+# most list slots B N of ALS.recommend_capacity: the batch's lists stay on the device across the rounds (8 B N bytes,
+# and as much again for the key buckets of als_capacity_settle, which indexes them with 32-bit offsets)
+CAPACITY_MAX_PAIRS = 1 << 26
 
 logger = logging.getLogger(__name__)
 
@@ -60,6 +64,18 @@ class ItemEligibility:
         s = torch.from_numpy(np.asarray(segments, dtype=np.int64)).to(self.table.device)
         i = torch.from_numpy(np.asarray(items, dtype=np.int64)).to(self.table.device)
         return (((self.table[s, i >> 5].to(torch.int64) >> (i & 31)) & 1) != 0).cpu().numpy()
+
+
+@dataclass
+class CapacityInfo:
+    """What `ALS.recommend_capacity(..., return_info=True)` adds to the lists.  rounds: the settle passes that found an
+    over-demanded item (0: the uncapped lists were feasible); walked_rows: the rows scored over all rounds (B in round
+    0, then the dirty rows only); fill int64 [n_total]: how many lists hold each item (<= capacity); cutoff float64
+    [n_total]: the score of the worst holder of a full item (fill == capacity > 0), NaN where the item is not full."""
+    rounds: int
+    walked_rows: int
+    fill: np.ndarray
+    cutoff: np.ndarray
 
 
 @dataclass
@@ -645,6 +661,95 @@ class _Serving:
         user agree on it - the facade checked): grouped by user as `rank_of`, the segment of a user's row that of
         its first pair, als_rank_count_segmented in REC_BATCH chunks."""
         return self._rank_pairs(us, is_, features, exclude_seen, folded, elig=elig, pair_seg=pair_seg)
+
+    # --------------------------------------------------------- exposure caps
+    def _capacity_rounds(self, B: int, N: int, pick, items: dict, filters, capacity: np.ndarray, max_rounds):
+        """The threshold rounds of `recommend_capacity` over B batch rows.  pick(ix) -> (users
+        int32, U, b_u, seen_ptr, seen_idx) of the batch rows `ix` (int64, device, ascending): unlike the chunk sources
+        of `_topk_chunks` it serves any subset, since the rounds after the first walk the dirty rows only.  `items`,
+        `filters` as in `_topk_chunks`, the items of capacity 0 already blocked by `filters`
+        (validate.capacity_filters); `capacity` int32 [n] (host).  The lists stay on the device; the host reads one
+        int per round.  Returns host (items int64 [B, N], scores float64 [B, N],
+        CapacityInfo)."""
+        n = items["n"]
+        if B * N > CAPACITY_MAX_PAIRS:
+            raise ValueError(f"recommend_capacity keeps the batch's lists on the device: {B} rows x N = {N} is above "
+                             f"CAPACITY_MAX_PAIRS = {CAPACITY_MAX_PAIRS} slots - split the batch (and its capacities)")
+        allow = self.allow_bitmap(filters, n)
+        cap = torch.from_numpy(capacity).to(self.dev)
+        floor = torch.zeros(n, dtype=torch.int64, device=self.dev)          # the bits of the 64-bit floors
+        fill = torch.empty(n, dtype=torch.int32, device=self.dev)
+        dirty = torch.empty(B, dtype=torch.int32, device=self.dev)
+        n_over = torch.empty(1, dtype=torch.int32, device=self.dev)
+        top_val, top_idx, top_cnt = self._topn_out(B, N)
+
+        def walk(ix, tv, ti, tc):
+            users, U, b_u, seen_ptr, seen_idx = pick(ix)
+            self.be.recommend_topk_priced(users=users, row_ids=ix.to(torch.int32), U=U, b_u=b_u, seen_ptr=seen_ptr,
+                                          seen_idx=seen_idx, allow=allow, floor_key=floor, topn=N, top_val=tv,
+                                          top_idx=ti, top_cnt=tc, **items)
+
+        work, rounds, walked = None, 0, 0                                    # None: every row (round 0)
+        while True:
+            W = B if work is None else work.numel()
+            for b0, nb in self._chunks(W, self.REC_BATCH):
+                if work is None:
+                    walk(torch.arange(b0, b0 + nb, dtype=torch.int64, device=self.dev), top_val[b0: b0 + nb],
+                         top_idx[b0: b0 + nb], top_cnt[b0: b0 + nb])
+                else:
+                    ix = work[b0: b0 + nb]
+                    tv, ti, tc = self._topn_out(nb, N)
+                    walk(ix, tv, ti, tc)
+                    top_val[ix], top_idx[ix] = tv, ti
+            walked += W
+            self.be.capacity_settle(n=n, top_idx=top_idx, top_val=top_val, capacity=cap, floor_key=floor, fill=fill,
+                                    dirty=dirty, n_over=n_over)
+            if int(n_over.item()) == 0:                                      # the round's only synchronisation
+                break
+            rounds += 1
+            if max_rounds is not None and rounds > max_rounds:
+                raise RuntimeError(f"recommend_capacity: items were still over-demanded after max_rounds = "
+                                   f"{max_rounds} rounds")
+            work = torch.nonzero(dirty).flatten()
+        # the worst holder of every item, then NaN where the item is not full
+        held = top_idx >= 0
+        worst = torch.full((n,), float("inf"), dtype=torch.float32, device=self.dev)
+        worst.scatter_reduce_(0, top_idx[held].to(torch.int64), top_val[held], "amin")
+        cutoff = torch.where((fill == cap) & (cap > 0), worst.to(torch.float64), float("nan"))
+        info = CapacityInfo(rounds, walked, fill.to(torch.int64).cpu().numpy(), cutoff.cpu().numpy())
+        return top_idx.to(torch.int64).cpu().numpy(), top_val.to(torch.float64).cpu().numpy(), info
+
+    def recommend_capacity(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool, capacity: np.ndarray,
+                           folded: Optional["FoldedItems"] = None, filters=None, max_rounds=None):
+        """`recommend` (or `recommend_with_items` with `folded`) under per-item caps: `_capacity_rounds` with batch row
+        b = user users_t[b]."""
+        side = self._side(features, folded)
+        if folded is None:
+            seen_ptr = seen_idx = None
+            if exclude_seen and self.nnz > 0:
+                seen_ptr, seen_idx = self.csr.indptr, self.csr.indices
+
+            def pick(ix):
+                return users_t[ix], self.U, self.b_u, seen_ptr, seen_idx
+        else:
+            pairs = self._folded_rater_pairs(folded) if exclude_seen else None
+
+            def pick(ix):                                                    # as `_joint_rows`, for any subset
+                us = users_t[ix].to(torch.int64)
+                seen_ptr, seen_idx = self._merged_seen(us, *pairs) if exclude_seen else (None, None)
+                return (torch.arange(ix.numel(), dtype=torch.int32, device=self.dev), self.U.index_select(0, us),
+                        self.b_u.index_select(0, us), seen_ptr, seen_idx)
+        return self._capacity_rounds(users_t.numel(), N, pick, side, filters, capacity, max_rounds)
+
+    def recommend_new_capacity(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
+                               capacity: np.ndarray, filters=None, max_rounds=None):
+        """Fold in, then `_capacity_rounds` on the folded table: batch row b = table row b, the given ratings as the
+        seen CSR."""
+        Z = self._compose_for(features)
+        U, b, ptr_d, idx_d = self._fold_in_dev(indptr, indices, vals, Z, n_sweeps)
+        seen = (ptr_d, idx_d) if exclude_seen and indptr[-1] > 0 else (None, None)
+        return self._capacity_rounds(indptr.size - 1, N, lambda ix: (ix.to(torch.int32), U, b, *seen),
+                                     self._item_side(Z), filters, capacity, max_rounds)
 
     # ------------------------------------------------------------ deep lists
     def _deep_chunks(self, B: int, N: int, rows, items: dict, filters, after):

@@ -358,6 +358,43 @@ def allowed_mask(filters, n_total: int) -> np.ndarray:
     return mask
 
 
+def item_capacity(capacity, n_total: int) -> np.ndarray:
+    """`capacity=` of `recommend_capacity` over n_total items -> int32 [n_total]: an integer scalar (the same cap for
+    every item) or a 1-D integer array with one entry per item, every entry >= 0 (values above 2^31 - 1 mean the same:
+    no batch is that long).  None is refused: a call without caps is `recommend`."""
+    if capacity is None:
+        raise ValueError("capacity is required: an integer array with one entry per item, or an integer scalar "
+                         "(None is not accepted; a call without caps is recommend)")
+    a = np.asarray(capacity.detach().cpu().numpy() if torch.is_tensor(capacity) else capacity)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"capacity must hold integers, got dtype {a.dtype}")
+    if a.ndim == 0:
+        a = np.full(n_total, a.item(), dtype=np.int64)
+    if a.shape != (n_total,):
+        raise ValueError(f"capacity has shape {a.shape}. Expected number of items: {n_total}.")
+    if a.size and a.min() < 0:
+        raise ValueError("capacity must not be negative")
+    return np.minimum(a, np.iinfo(np.int32).max).astype(np.int32)
+
+
+def capacity_filters(filters, capacity: np.ndarray):
+    """The `item_filters` pair of a capped call with the items of capacity 0 blocked as well: they go into the allow
+    bitmap together with the filters.  None when there is nothing to block."""
+    stocked = capacity > 0
+    if filters is None:
+        return None if stocked.all() else (stocked, None)
+    return allowed_mask(filters, capacity.size) & stocked, None
+
+
+def max_rounds_arg(max_rounds) -> Optional[int]:
+    """`max_rounds=` of `recommend_capacity`: None (run to the fixed point) or an integer >= 0."""
+    if max_rounds is None:
+        return None
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 0:
+        raise ValueError(f"max_rounds must be None or an integer >= 0, got {max_rounds!r}")
+    return int(max_rounds)
+
+
 ELIGIBILITY_MAX_ATTRS = 256     # 32 ALS_ELIGIBILITY_MAX_TAG_WORDS
 ELIGIBILITY_RULES = ("need_all", "need_any", "forbid")
 

@@ -572,6 +572,44 @@ int als_eligibility_bitmaps(int64_t n, int tw, const uint32_t* item_tags, int64_
                             uint32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Top-N under per-item exposure caps (ALS.recommend_capacity): the two device pieces of its threshold rounds.
+ *
+ * Item-side keys: the pair (batch row b, item i) with score s has the key (enc(s) << 32) | (0xFFFFFFFF - b) - the key
+ *   of als_recommend_deep with the BATCH ROW in the index word -, so the demanders of one item are ordered by (score
+ *   descending, row ascending) and their keys are distinct.  floor_key [n]: one such key per item, 0 = no floor.
+ *
+ * als_recommend_topk_priced: als_recommend_topk_masked (allow == NULL: every item) with one more term in the candidate
+ *   test - launched row b takes item i only if key(score(users[b], i), row_ids[b]) >= floor_key[i].  row_ids [nusers]:
+ *   the batch row of every launched row (in [0, 2^31)), used in that key and nowhere else, so a compacted work list
+ *   keeps its rows' priorities.  Everything else - scores, order, ties, unused slots, top_cnt, nslices, the workspace
+ *   (als_recommend_workspace_bytes) - is that call's; with floor_key all 0 the outputs equal its outputs, element for
+ *   element, whatever row_ids holds.
+ *
+ * als_capacity_settle: from the lists of the WHOLE batch (top_idx / top_val [nrows][topn], list row = batch row; a
+ *   slot whose id is outside [0, n) is empty) and capacity [n] (negative counts as 0):
+ *     d_i        = the number of list entries naming item i (an item is named at most once per row);
+ *     fill[i]    = min(d_i, capacity[i]);
+ *     floor_key[i] for every item with d_i > capacity[i] (over-demanded) = the capacity[i]-th largest item-side key
+ *                  among its entries (capacity 0: ~0, which nothing passes); the other floors are left as they are;
+ *     dirty[b]   = 1 if row b holds an entry whose item-side key is below the (new) floor of its item, else 0;
+ *     *n_over    = the number of over-demanded items.
+ *   The results do not depend on the order in which the integer atomics inside arrive.  nrows * topn < 2^31, n < 2^31.
+ * workspace: als_capacity_settle_workspace_bytes(nrows, n, topn) bytes of device memory, always > 0 (four int32 [n]
+ *   arrays, the counters, 8 nrows topn bytes of key buckets); the call allocates nothing, enqueues its launches on
+ *   `stream` and does not synchronise with the host.
+ * ------------------------------------------------------------------------- */
+int als_recommend_topk_priced(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                              const float* Z, const float* b_u, const float* b_i, const double* mu,
+                              const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                              const int32_t* row_ids, const unsigned long long* floor_key, int topn, int nslices, float* top_val,
+                              int32_t* top_idx, int32_t* top_cnt, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t als_capacity_settle_workspace_bytes(int64_t nrows, int64_t n, int topn);
+int als_capacity_settle(int64_t nrows, int topn, int64_t n, const int32_t* top_idx, const float* top_val,
+                        const int32_t* capacity, unsigned long long* floor_key, int32_t* fill, int32_t* dirty,
+                        int32_t* n_over, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user
  * half-step (scripts/als.py:411-433) for new rows.  For every row r < nrows of the CSR (indptr [nrows+1] /
  * indices / vals: device, column indices in [0, n), unique and ascending within a row), with S its items, n_r = |S|:
