@@ -30,7 +30,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_category_profile", "als_calibrated_rerank", "als_list_miscalibration",
            "als_recommend_deep_workspace_bytes", "als_recommend_deep",
            "als_recommend_topk_segmented", "als_rank_count_segmented", "als_eligibility_bitmaps",
-           "als_recommend_topk_priced", "als_capacity_settle_workspace_bytes", "als_capacity_settle")
+           "als_recommend_topk_priced", "als_capacity_settle_workspace_bytes", "als_capacity_settle",
+           "als_recommend_topk_quota")
 
 # the workspace queries: they return size_t, everything else but the two slot-size queries an int status / value
 SIZE_QUERIES = ("als_spd_solve_workspace_bytes", "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
@@ -192,6 +193,8 @@ def load():
                                               _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_capacity_settle_workspace_bytes.argtypes = [_i64, _i64, C.c_int]
     lib.als_capacity_settle.argtypes = [_i64, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
+    lib.als_recommend_topk_quota.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]
     lib.als_recommend_deep_workspace_bytes.argtypes = [_i64, _i64, C.c_int, C.c_int]
     lib.als_recommend_deep.argtypes = [C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]

@@ -514,6 +514,58 @@ class ALS:
                                                                           exclude_seen, cap, filters, max_rounds),
                                          return_info)
 
+    # --------------------------------------------------------- group quotas
+    def recommend_quota(self, users=None, N: int = 10, *, groups, max_per_group,
+                        features: Optional[Dict[str, np.ndarray]] = None, exclude_seen: bool = True,
+                        new_items: Optional[FoldedItems] = None, items=None, filter_items=None):
+        """Top-N lists with a hard cap per group inside each list: "at most 2 items of one artist / brand / seller /
+        series".  Returns (items int64 [B, N], scores float64 [B, N]) padded with -1 / -inf.
+
+        `groups`: a 1-D integer array with one label per item (n entries, n + B with `new_items`); labels are >= 0,
+        and -1 marks an item that belongs to no group and is never capped.  `max_per_group`: a non-negative int - the
+        same cap for every group - or an int array with cap[g] for every label g used.  Everything else means what it
+        means in `recommend`.
+
+        Definition: the candidates of row b are `recommend`'s - not seen, allowed, score not NaN, scored bitwise as
+        `predict` - scanned in `recommend`'s order (score descending, item ascending); a candidate is taken iff fewer
+        than cap[g] taken items share its group g, and the scan stops after N taken items.  With every cap >= N, or
+        every label -1, it is `recommend`, element for element; a cap of 0 is a block list over the group.
+
+        One fused walk of the catalogue computes it exactly (als_recommend_topk_quota): no
+        over-fetch, no pool, no paging.  The kernel is asked for N_eff = min(N, #allowed items without a group +
+        sum_g min(cap[g], #allowed items of g)) entries - no list can hold more, so the result is unchanged and the
+        columns from N_eff on are padding - which keeps its selection threshold working under tight caps.  Local to
+        the calling rank."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        n_total = self._n_total(new_items)
+        u = validate.user_ids(users, self.U.shape[0])
+        labels, caps = validate.item_groups(groups, max_per_group, n_total)
+        allowed = validate.quota_allowed(validate.item_filters(items, filter_items, n_total), n_total)
+        if u.size == 0:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_quota(self._dev_i32(u), N, features, exclude_seen, labels, caps, new_items,
+                                             allowed)
+
+    def recommend_new_quota(self, R_new, N: int = 10, *, groups, max_per_group,
+                            features: Optional[Dict[str, np.ndarray]] = None, n_sweeps: Optional[int] = None,
+                            exclude_seen: bool = True, items=None, filter_items=None):
+        """`recommend_quota` for users outside the fit: `fold_in(R_new, ...)` as in `recommend_new`, then the
+        definition of `recommend_quota` on the folded rows; `groups` spans the n fitted items."""
+        features = self._check_predict(features)
+        N = validate.top_count(N, "N")
+        T = validate.sweeps(n_sweeps)
+        n = self.V.shape[0]
+        indptr, indices, vals = fold_in_csr(R_new, n)
+        labels, caps = validate.item_groups(groups, max_per_group, n)
+        allowed = validate.quota_allowed(validate.item_filters(items, filter_items, n), n)
+        if indptr.size == 1:
+            return np.empty((0, N), dtype=np.int64), np.empty((0, N), dtype=np.float64)
+        with _on(self._eng.dev):
+            return self._eng.recommend_new_quota(indptr, indices, vals, N, features, T, exclude_seen, labels, caps,
+                                                 allowed)
+
     # ----------------------------------------------------------- deep lists
     def recommend_deep(self, users=None, N: int = 500, *, features: Optional[Dict[str, np.ndarray]] = None,
                        exclude_seen: bool = True, new_items: Optional[FoldedItems] = None, items=None,

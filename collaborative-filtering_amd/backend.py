@@ -476,6 +476,20 @@ class HipBackend:
                                                  self._workspace("capacity_settle", need), need, self._stream()),
                     "als_capacity_settle")
 
+    def recommend_topk_quota(self, *, k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, allow, item_group,
+                             group_cap, topn, top_val, top_idx, top_cnt):
+        """`recommend_topk_masked` (allow None: every item) with at most group_cap[g] items of group g in a list:
+        als_recommend_topk_quota.  item_group int32 [n]: the label of every item (outside [0, G): no group);
+        group_cap int32 [G]."""
+        for t, num, what in ((item_group, n, "item_group"), (group_cap, group_cap.numel(), "group_cap")):
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() != num:
+                raise ValueError(f"{what} must be a contiguous int32 device tensor"
+                                 + (f" of {n} labels" if what == "item_group" else ""))
+        self._recommend(self.lib.als_recommend_topk_quota, "als_recommend_topk_quota",
+                        (self._bitmap(allow, n), _p(item_group), _p(group_cap) if group_cap.numel() else None,
+                         group_cap.numel()), k, ld, users, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, topn, top_val,
+                        top_idx, top_cnt)
+
     def _rank(self, fn, what, allow, k, ld, n, U, Z, b_u, b_i, mu, seen_ptr, seen_idx, q_users, q_ptr, q_items,
               t_score, above, n_cand):
         if seen_idx is not None and seen_idx.numel() == 0:

@@ -319,6 +319,47 @@ def capacity_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, capacity, m
             "rounds": info.rounds, "walked_rows": info.walked_rows, **extra}
 
 
+def quota_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, groups, max_per_group,
+               min_rating: Optional[float] = None, features: Optional[Dict[str, np.ndarray]] = None, items=None,
+               filter_items=None) -> Dict[str, Any]:
+    """What per-group caps cost and buy: `model.recommend_quota(users, K, groups=groups, max_per_group=max_per_group)`
+    over the users of the held-out (user, item) pairs next to the uncapped `model.recommend`: {"users", "recall@K",
+    "ndcg@K", "recall@K_uncapped", "ndcg@K_uncapped", "groups_per_list", "groups_per_list_uncapped",
+    "max_group_share", "max_group_share_uncapped"} (plus "filtered_out" with `items` / `filter_items`).
+
+    users, rel(u), recall@K and NDCG@K are `ranking_at_k`'s (same arguments, same pairs left out); the uncapped values
+    equal `ranking_at_k`'s.  groups_per_list: the mean over the non-empty lists of the number of distinct groups in a
+    list, an item without a group (label -1) counting as a group of its own.  max_group_share: the mean over the
+    non-empty lists of (the most entries one group has in the list) / (the entries of the list), 1 / entries for a list
+    without a grouped item.  Both are NaN when every list is empty."""
+    users, ub, cols, kw, extra = _users_at_k(model, rows, cols, vals, min_rating, items, filter_items)
+    validate.fitted(model)
+    n = model.V.shape[0]
+    labels, caps = validate.item_groups(groups, max_per_group, n)
+    nan = float("nan")
+    names = ("recall@K", "ndcg@K", "groups_per_list", "max_group_share")
+    if users.size == 0:
+        return {"users": 0, **{f"{k}{s}": nan for k in names for s in ("", "_uncapped")}, **extra}
+
+    def measures(top):
+        distinct, share = [], []
+        for row in top:
+            row = row[row >= 0]
+            if row.size == 0:
+                continue
+            g = labels[row]
+            counts = np.bincount(g[g >= 0]) if (g >= 0).any() else np.ones(1, np.int64)
+            distinct.append(int((counts > 0).sum() if (g >= 0).any() else 0) + int((g < 0).sum()))
+            share.append(counts.max() / row.size)
+        m = _ranking_metrics(top, ub, cols, n, K)
+        return {"recall@K": m["recall@K"], "ndcg@K": m["ndcg@K"],
+                "groups_per_list": float(np.mean(distinct)) if distinct else nan,
+                "max_group_share": float(np.mean(share)) if share else nan}
+    capped = measures(model.recommend_quota(users, K, groups=labels, max_per_group=caps, features=features, **kw)[0])
+    plain = measures(model.recommend(users, K, features=features, **kw)[0])
+    return {"users": int(users.size), **capped, **{f"{k}_uncapped": v for k, v in plain.items()}, **extra}
+
+
 def audience_at_k(model: ALS, rows, cols, vals=None, *, K: int = 10, min_rating: Optional[float] = None,
                   features: Optional[Dict[str, np.ndarray]] = None, users=None, filter_users=None) -> Dict[str, Any]:
     """recall@K and NDCG@K of `model.recommend_users` on held-out (user, item) pairs: `ranking_at_k` per ITEM - is

@@ -1,8 +1,8 @@
 """Serving a fitted model: the device side of `ALS.predict*`, `recommend*`, `rank_of*`, `explain*`, `fold_in`,
 `fold_in_items`, `recommend*_diverse`, `list_diversity`, `similar_items` / `similar_users`, `recommend_users`,
 `recommend_group`, `recommend*_explore`, `recommend*_calibrated`, `category_profile`, `list_miscalibration` and
-`recommend*_deep`, the per-user eligibility calls (`eligibility`, `recommend*_eligible`, `rank_of_eligible`) and the
-capped batch lists (`recommend*_capacity`).
+`recommend*_deep`, the per-user eligibility calls (`eligibility`, `recommend*_eligible`, `rank_of_eligible`), the
+capped batch lists (`recommend*_capacity`) and the lists under per-group caps (`recommend*_quota`).
 
 `_Serving` is the part of the engine (engine._Engine inherits it) that reads the fit's device state - `U V Z b_u b_i
 mu W64 csr` and the shapes - and never changes it.  Every call is local to the calling rank: after the all-gathers
@@ -76,6 +76,22 @@ class CapacityInfo:
     walked_rows: int
     fill: np.ndarray
     cutoff: np.ndarray
+
+
+def quota_plan(allowed: Optional[np.ndarray], labels: np.ndarray, caps: np.ndarray, N: int):
+    """What the caps of `recommend_quota` leave of a call's catalogue: (allowed, N_eff).  `allowed`: bool [n] or None
+    (every item), returned with the items of the groups of cap 0 cleared (they go into the allow bitmap; None when
+    nothing is blocked).  N_eff = min(N, #allowed items without a group + sum over the groups of min(cap, #allowed
+    items of the group)): no list can hold more, and a list that long fills, so the walk's threshold works."""
+    grouped = labels >= 0
+    closed = np.zeros(labels.size, dtype=bool)
+    closed[grouped] = caps[labels[grouped]] == 0
+    if closed.any():
+        allowed = ~closed if allowed is None else allowed & ~closed
+    open_ = grouped if allowed is None else grouped & allowed
+    sizes = np.bincount(labels[open_], minlength=caps.size).astype(np.int64)
+    free = int((~grouped).sum() if allowed is None else (allowed & ~grouped).sum())
+    return allowed, min(N, free + int(np.minimum(sizes, caps.astype(np.int64)).sum()))
 
 
 @dataclass
@@ -750,6 +766,40 @@ class _Serving:
         seen = (ptr_d, idx_d) if exclude_seen and indptr[-1] > 0 else (None, None)
         return self._capacity_rounds(indptr.size - 1, N, lambda ix: (ix.to(torch.int32), U, b, *seen),
                                      self._item_side(Z), filters, capacity, max_rounds)
+
+    # ----------------------------------------------------------- group quotas
+    def _quota_chunks(self, B: int, N: int, rows, items: dict, allowed, labels: np.ndarray, caps: np.ndarray):
+        """als_recommend_topk_quota over B batch rows in REC_BATCH chunks; `rows`, `items` as in
+        `_topk_chunks`, `allowed` the call's filters as one host mask (bool [n]) or None, `labels` int32 [n] / `caps`
+        int32 [G] from validate.item_groups, uploaded once.  The kernel is called with N_eff = `quota_plan`'s clamp - the
+        longest list the caps allow - so that every list fills and the walk's threshold works; the columns N_eff ... N
+        hold -1 / -inf, as they would anyway.  Returns host (items int64 [B, N], scores float64 [B, N])."""
+        allowed, n_eff = quota_plan(allowed, labels, caps, N)
+        out_i, out_v = np.full((B, N), -1, dtype=np.int64), np.full((B, N), -np.inf, dtype=np.float64)
+        if n_eff == 0:
+            return out_i, out_v
+        allow = self.allow_bitmap(None if allowed is None else (allowed, None), items["n"])
+        item_group, group_cap = torch.from_numpy(labels).to(self.dev), torch.from_numpy(caps).to(self.dev)
+
+        def call(b0, nb, tv, ti, tc):
+            users, U, b_u, seen_ptr, seen_idx = rows(b0, nb)
+            self.be.recommend_topk_quota(users=users, U=U, b_u=b_u, seen_ptr=seen_ptr, seen_idx=seen_idx, allow=allow,
+                                         item_group=item_group, group_cap=group_cap, topn=n_eff, top_val=tv,
+                                         top_idx=ti, top_cnt=tc, **items)
+        out_i[:, :n_eff], out_v[:, :n_eff] = self._collect_topn(B, n_eff, self.REC_BATCH, call)
+        return out_i, out_v
+
+    def recommend_quota(self, users_t: torch.Tensor, N: int, features, exclude_seen: bool, labels: np.ndarray,
+                        caps: np.ndarray, folded: Optional["FoldedItems"] = None, allowed=None):
+        """`recommend` (or `recommend_with_items` with `folded`) with at most caps[g] items of group g in a list."""
+        side, rows = self._catalogue(users_t, features, exclude_seen, folded)
+        return self._quota_chunks(users_t.numel(), N, rows, side, allowed, labels, caps)
+
+    def recommend_new_quota(self, indptr, indices, vals, N: int, features, n_sweeps: int, exclude_seen: bool,
+                            labels: np.ndarray, caps: np.ndarray, allowed=None):
+        """Fold in, then `_quota_chunks` on the folded table, as `recommend_new`."""
+        side, rows, *_ = self._new_catalogue(indptr, indices, vals, features, n_sweeps, exclude_seen)
+        return self._quota_chunks(indptr.size - 1, N, rows, side, allowed, labels, caps)
 
     # ------------------------------------------------------------ deep lists
     def _deep_chunks(self, B: int, N: int, rows, items: dict, filters, after):

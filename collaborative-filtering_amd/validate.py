@@ -395,6 +395,48 @@ def max_rounds_arg(max_rounds) -> Optional[int]:
     return int(max_rounds)
 
 
+def _int_array(a, what: str) -> np.ndarray:
+    a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what} must hold integers, got dtype {a.dtype}")
+    return a
+
+
+def item_groups(groups, max_per_group, n_total: int):
+    """`groups=` / `max_per_group=` of `recommend_quota` over n_total items -> (labels int32 [n_total], caps int32 [G]).
+    `groups`: a 1-D integer array with one label >= -1 per item (-1: the item belongs to no group and is never
+    capped).  `max_per_group`: a non-negative integer scalar - the same cap for every group - or a 1-D integer array
+    of non-negative caps that covers every label used (cap[g] for label g).  Caps above 2^31 - 1 mean the same: no
+    list is that long."""
+    if groups is None or max_per_group is None:
+        raise ValueError("groups and max_per_group are required (None is not accepted; a call without caps is "
+                         "recommend)")
+    g = _int_array(groups, "groups")
+    if g.shape != (n_total,):
+        raise ValueError(f"groups has shape {g.shape}. Expected number of items: {n_total}.")
+    if g.size and g.min() < -1:
+        raise ValueError("groups must hold labels >= 0, or -1 for an item without a group")
+    top = int(g.max()) if g.size else -1
+    if top >= np.iinfo(np.int32).max:
+        raise ValueError("group labels must be below 2^31 - 1")
+    c = _int_array(max_per_group, "max_per_group")
+    if c.ndim == 0:
+        c = np.full(top + 1, c.item(), dtype=np.int64)
+    if c.ndim != 1:
+        raise ValueError(f"max_per_group must be an integer scalar or a 1-D array, got shape {c.shape}")
+    if c.size and c.min() < 0:
+        raise ValueError("max_per_group must not be negative")
+    if c.size <= top:
+        raise ValueError(f"max_per_group has {c.size} entries: label {top} has no cap")
+    return g.astype(np.int32), np.minimum(c, np.iinfo(np.int32).max).astype(np.int32)
+
+
+def quota_allowed(filters, n_total: int) -> Optional[np.ndarray]:
+    """The `item_filters` pair of a `recommend_quota` call as one boolean mask over the catalogue (None: every item):
+    what serving.quota_plan counts the groups over."""
+    return None if filters is None else allowed_mask(filters, n_total)
+
+
 ELIGIBILITY_MAX_ATTRS = 256     # 32 ALS_ELIGIBILITY_MAX_TAG_WORDS
 ELIGIBILITY_RULES = ("need_all", "need_any", "forbid")
 

@@ -610,6 +610,28 @@ int als_capacity_settle(int64_t nrows, int topn, int64_t n, const int32_t* top_i
                         int32_t* n_over, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Top-N with per-group caps inside each list (ALS.recommend_quota): "at most group_cap[g] items of group g in a list".
+ *
+ * als_recommend_topk_quota: als_recommend_topk_masked (allow == NULL: every item) with a group label per item and a
+ *   cap per group.  item_group [n]: the label of every item, in [0, ngroups); any other value (-1 by convention) means
+ *   the item belongs to no group and is never capped.  group_cap [ngroups]: at most this many items of the group in a
+ *   list (<= 0: none; may be NULL when ngroups == 0).  Row b's list is one scan of the masked call's candidates in its
+ *   order (score descending, item ascending): a candidate is taken iff fewer than group_cap[g] taken items share its
+ *   group g, and the scan stops after topn taken items.  Scores, ties, unused slots (-1 / -inf), top_cnt, nslices and
+ *   the workspace (als_recommend_workspace_bytes) are that call's; with every label outside [0, ngroups), or every
+ *   cap >= topn, the outputs equal its outputs, element for element, and a group of cap 0 equals clearing its items
+ *   from the bitmap.  The result does not depend on nslices.  A list that the caps keep from filling (fewer than topn
+ *   takeable candidates) is exact as well but slow: its threshold never rises; callers clamp topn to the number of
+ *   takeable items first (serving._Serving._quota_chunks does).
+ * ------------------------------------------------------------------------- */
+int als_recommend_topk_quota(int k, int ld, int64_t nusers, const int32_t* users, int64_t n, const float* U,
+                             const float* Z, const float* b_u, const float* b_i, const double* mu,
+                             const int64_t* seen_ptr, const int32_t* seen_idx, const uint32_t* allow,
+                             const int32_t* item_group, const int32_t* group_cap, int64_t ngroups, int topn,
+                             int nslices, float* top_val, int32_t* top_idx, int32_t* top_cnt, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fold-in: factors and biases of users outside the fit, the item side (Z, b_i, mu) held fixed - the fit's user
  * half-step (scripts/als.py:411-433) for new rows.  For every row r < nrows of the CSR (indptr [nrows+1] /
  * indices / vals: device, column indices in [0, n), unique and ascending within a row), with S its items, n_r = |S|:
