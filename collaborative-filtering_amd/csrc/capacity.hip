@@ -7,14 +7,15 @@
 // candidate only while its item-side key is >= the floor of its item.
 //
 // k_priced (als_recommend_topk_priced): k_recommend (recommend.hip) with that one more term in the candidate test.  It
-// is a kernel of its own, written from k_recommend as k_audience was from k_similar, because a further template
-// parameter of k_recommend has to leave the instruction streams of its 60 existing instances as they are, and two more
-// kernel arguments do not promise that (catalogue_walk.hpp says why duplication is the accepted price).  What differs
-// from k_recommend<KB, NW, CAP, MASKED>: row_ids (the batch row of every launched row: a compacted work list keeps its
-// rows' priorities) and floor_key; the floors of a chunk's 32 items are per-column data like b_i and travel with the
-// chunk - lane (c, q) fetches the floors of items c and 16 + c of the next chunk behind the Z prefetch and takes them
-// over when the chunk is staged.  Slices, raw-key workspace and merge are the family's (topk_launch.hpp,
-// topk::merge_slices).  With all floors 0 the kernel is k_recommend: make_key(...) >= 0 always holds.
+// is a kernel of its own, because a further template parameter of k_recommend has to leave the instruction streams of
+// its 60 existing instances as they are, and two more kernel arguments do not promise that - but not a copy: the walk
+// and the row state are the walk_*.inc fragments k_recommend includes, and only what differs is
+// written here, around the includes.  What differs from k_recommend<KB, NW, CAP, MASKED>: row_ids (the batch row of
+// every launched row: a compacted work list keeps its rows' priorities) and floor_key; the floors of a chunk's 32 items
+// are per-column data like b_i and travel with the chunk - lane (c, q) fetches the floors of items c and 16 + c of the
+// next chunk behind the Z prefetch and takes them over when the chunk is staged.  Slices, raw-key workspace and merge
+// are the family's (topk_launch.hpp, topk::merge_slices).  With all floors 0 the kernel is k_recommend:
+// make_key(...) >= 0 always holds.
 //
 // Settle (als_capacity_settle): from the batch's lists to per-item demand, new floors, dirty rows - six launches on
 // the caller's stream, no host synchronisation, nothing allocated:
@@ -42,7 +43,6 @@ using topk::key_index;
 using topk::key_score;
 using topk::make_key;
 
-constexpr int PC_CHUNK = walk::CHUNK;
 constexpr int PC_WIDE = topk::ROWS_WIDE;
 constexpr int PC_NARROW = topk::ROWS_NARROW;
 
@@ -59,10 +59,10 @@ void k_priced(int ld, int64_t nusers, const int32_t* __restrict__ users, const i
               const uint32_t* __restrict__ allow, const unsigned long long* __restrict__ floor_key) {
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
-    constexpr int NT = NW * 64, NV = PC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
+    constexpr int NT = NW * 64, NV = walk::CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     static_assert(L >= 32 && BUF >= 64, "a chunk appends up to 32 keys per row");
     __shared__ unsigned long long keys[NW * 16][CAP];
-    __shared__ __attribute__((aligned(16))) float zs[PC_CHUNK][ZS];
+    __shared__ __attribute__((aligned(16))) float zs[walk::CHUNK][ZS];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -85,82 +85,15 @@ void k_priced(int ld, int64_t nusers, const int32_t* __restrict__ users, const i
         const int u = users[min(rb, nusers - 1)];
         bu[r] = b_u[u];
         rid[r] = (unsigned)row_ids[min(rb, nusers - 1)];
-        cur[r] = end[r] = 0;
-        if (seen_ptr && valid[r]) {
-            int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
-            end[r] = e;
-            while (a < e) {                                              // first seen item >= lo
-                const int64_t mid = a + ((e - a) >> 1);
-                if (seen_idx[mid] < lo) a = mid + 1; else e = mid;
-            }
-            cur[r] = a;
-        }
-        nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+#include "walk_seen_cursor.inc"
     }
-    unsigned long long thr[4] = {0ull, 0ull, 0ull, 0ull};    // key of the current topn-th entry (0: list not full)
-    int cnt[4] = {0, 0, 0, 0};                                // buffered survivors (same in the 16 lanes of a q group)
-    int nlist[4] = {0, 0, 0, 0};                              // valid entries of the sorted list
-
-    auto compact = [&](int r) {        // wave-uniform r: list + buffer of row r -> sorted list, new threshold
-        const int rq = r >> 2, re = r & 3;
-        int rc = 0, rn = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { rc = (re == e) ? cnt[e] : rc; rn = (re == e) ? nlist[e] : rn; }
-        rc = readlane_i(rc, 16 * rq);
-        rn = readlane_i(rn, 16 * rq);
-        unsigned long long k[CAP / 64];
-#pragma unroll
-        for (int v = 0; v < CAP / 64; ++v) {
-            const int i = lane + 64 * v;
-            const bool live = (i < rn) || (i >= L && i < L + rc);
-            k[v] = live ? kw[r][i] : 0ull;
-        }
-        topk::sort_desc<CAP / 64>(k, lane);
-#pragma unroll
-        for (int v = 0; v < CAP / 64; ++v)
-            if (lane + 64 * v < L) kw[r][lane + 64 * v] = k[v];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const int nn = min(topn, rn + rc);
-        const unsigned long long t = (nn == topn) ? kw[r][topn - 1] : 0ull;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (q == rq && e == re) { thr[e] = t; cnt[e] = 0; nlist[e] = nn; }
-    };
+#include "walk_row_lists.inc"
 
     unsigned deny = 0u;     // MASKED: bit c set = item cb + c of the block `select` is called for is not allowed
     // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold and floor test, append;
     // fl: the floor of item cb + c
     auto select = [&](const f32x4& acc, int64_t cb, unsigned long long fl) {
-        unsigned msk[4] = {0u, 0u, 0u, 0u};
-        bool near = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) near = near || nxt[r] < cb + 16;
-        if (__ballot(near)) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bool more = nxt[r] < cb + 16;                            // same in the 16 lanes of the q group
-                const bool touched = more;
-                while (__ballot(more)) {
-                    int s = INT32_MAX;
-                    if (more) {
-                        const int64_t p = cur[r] + c;
-                        s = p < end[r] ? seen_idx[p] : INT32_MAX;
-                    }
-                    const bool below = more && s < cb + 16;
-                    unsigned bit = (below && s >= cb) ? 1u << (int)(s - cb) : 0u;
-                    bit |= __shfl_xor(bit, 1, 64);
-                    bit |= __shfl_xor(bit, 2, 64);
-                    bit |= __shfl_xor(bit, 4, 64);
-                    bit |= __shfl_xor(bit, 8, 64);
-                    msk[r] |= bit;
-                    const int adv = __popc((unsigned)(__ballot(below) >> (16 * q)) & 0xFFFFu);
-                    cur[r] += adv;
-                    more = more && adv == 16;                            // 16 consumed: there may be more in the block
-                }
-                if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
-            }
-        }
+#include "walk_seen_masks.inc"
         if constexpr (MASKED) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) msk[r] |= deny;
@@ -183,58 +116,26 @@ void k_priced(int ld, int64_t nusers, const int32_t* __restrict__ users, const i
     f32x4 pf[PF];
     unsigned long long pfl[2] = {0ull, 0ull}, fl[2] = {0ull, 0ull};      // floors of items c and 16 + c: prefetched, current
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
         pfl[0] = floor_key[min(it0 + c, n - 1)];
         pfl[1] = floor_key[min(it0 + 16 + c, n - 1)];
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
         fl[0] = pfl[0];
         fl[1] = pfl[1];
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + PC_CHUNK - 1) / PC_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / PC_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
-    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);
-        if (nx < nch) { fetch(lo + nx * PC_CHUNK); window(nx + 1); }
+        if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }
     } else if (nch > 0) {
         fetch(lo);
     }
     for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
-        const int64_t it0 = lo + ch * PC_CHUNK;
+        const int64_t it0 = lo + ch * walk::CHUNK;
         unsigned word = 0u;
         if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
         __syncthreads();                                 // every wave is done with the previous chunk
@@ -242,65 +143,19 @@ void k_priced(int ld, int64_t nusers, const int32_t* __restrict__ users, const i
         __syncthreads();
         if constexpr (MASKED) {
             nx = after(ch);
-            if (nx < nch) { fetch(lo + nx * PC_CHUNK); window(nx + 1); }      // however far ahead
+            if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }      // however far ahead
         } else if (ch + 1 < nch) {
-            fetch(it0 + PC_CHUNK);
+            fetch(it0 + walk::CHUNK);
         }
-        float z0[E], z1[E];
-        load_frow<E>(&zs[c][E * q], z0);
-        load_frow<E>(&zs[16 + c][E * q], z1);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
-        }
+#include "walk_score_tiles.inc"
         const unsigned long long f0 = fl[0], f1 = fl[1];  // this chunk's floors, before the prefetch's are taken over
         if constexpr (MASKED) deny = ~word & 0xFFFFu;
         select(acc0, it0, f0);
         if constexpr (MASKED) deny = ~word >> 16;
         select(acc1, it0 + 16, f1);
-        bool full = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) full = full || cnt[r] > BUF - PC_CHUNK;
-        if (__ballot(full)) {                            // some row's buffer could overflow in the next chunk
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            for (int r = 0; r < 16; ++r) {
-                int rc = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
-                rc = readlane_i(rc, 16 * (r >> 2));
-                if (rc > BUF - PC_CHUNK) compact(r);
-            }
-        }
+#include "walk_row_overflow.inc"
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    for (int r = 0; r < 16; ++r) {
-        int rc = 0, rn = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
-        rc = readlane_i(rc, 16 * (r >> 2));
-        if (rc > 0) compact(r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) rn = ((r & 3) == e) ? nlist[e] : rn;
-        rn = readlane_i(rn, 16 * (r >> 2));
-        const int64_t rb = b0 + r;
-        if (rb >= nusers) continue;
-        if (part) {                                      // sliced: raw keys of (slice, user), 0 = empty
-            unsigned long long* dst = part + ((int64_t)blockIdx.y * nusers + rb) * topn;
-            for (int t = lane; t < topn; t += 64) dst[t] = t < rn ? kw[r][t] : 0ull;
-        } else {
-            for (int t = lane; t < topn; t += 64) {
-                const bool ok = t < rn;
-                const unsigned long long key = ok ? kw[r][t] : 0ull;
-                top_val[rb * topn + t] = ok ? key_score(key) : -INFINITY;
-                top_idx[rb * topn + t] = ok ? key_index(key) : -1;
-            }
-            if (lane == 0) top_cnt[rb] = rn;
-        }
-    }
+#include "walk_row_write.inc"
 }
 
 template <int KB>

@@ -5,11 +5,14 @@
 //
 // Only what compiles to the same instructions as before lives here.  The rest of the walk - Z prefetch / staging,
 // allow-bitmap scan, seen-cursor set-up, 16-entry exclusion walk, score tiles, candidate test, chunk loop - was moved
-// here as well, measured and put back: shared, in every form tried, it changed the register allocation of all 60
-// kernel instances, and on the MI355X the sliced k_recommend calls (64 ... 4096 users, N = 10) came out 6 % slower
-// while everything else ran 1 ... 5 % faster (profiles/catalogue_walk_ab.json).  Those pieces are
-// therefore still written twice, character for character apart from the RC_ / RK_ prefix: change them in both files,
-// and let the GPU suite (test_gpu_rank_eval.py, test_gpu_recommend_filter.py) confirm that they still agree bitwise.
+// here as well, measured and put back: as functions, member functions, lambda factories or a loop template it changed
+// the register allocation of all 60 kernel instances, and on the MI355X the sliced k_recommend calls (64 ... 4096
+// users, N = 10) came out 6 % slower while everything else ran 1 ... 5 % faster (DESIGN section 19,
+// profiles/catalogue_walk_ab.json).  Those pieces have one text all the same: the walk_*.inc fragments next to this
+// header, plain statements that a kernel #includes at the point of use, inside its body, so that the compiler reads the
+// token sequence it read when they were written out and every stream stays the parent's (which lists
+// the fragments and their includers; profiles/walk_text_streams.txt).  The candidate test and the chunk loop differ from
+// kernel to kernel and stay in the kernels; tests/test_walk_single_text_cpu.py keeps the copies from growing back.
 #pragma once
 #include "als_device.hpp"
 
@@ -44,8 +47,8 @@ constexpr int lds_row_stride(int KB) { return 16 * KB + 4; }    // floats per st
 __device__ __forceinline__ float score(float dot, float mu, float bu, float bi) { return dot + mu + bu + bi; }
 
 // ---- first position in [a, e) of the ascending list whose entry is >= bound: where a seen cursor starts in a slice,
-// and where it jumps to after chunks that were not scored (k_audience, k_group, k_explore; k_recommend and
-// k_rank_count keep the search written out in their cursor set-up)
+// and where it jumps to after chunks that were not scored (k_audience, k_group, k_explore; the kernels that include
+// walk_seen_cursor.inc have the search written out there: section 19)
 __device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ idx, int64_t a, int64_t e, int64_t bound) {
     while (a < e) {
         const int64_t mid = a + ((e - a) >> 1);

@@ -26,8 +26,9 @@
 //             folded by two xor shuffles (16, 32) - every lane of column c then holds |W z_c|^2.
 //   key:      three correctly rounded fp32 operations, no contraction (explore_key).
 // A leverage depends on (W, z_i) alone: an MFMA column does not see its neighbours, the additions have one order.
-// Selection (one candidate per item and one list per wave), seen cursor, allow-bitmap scan, slices and their merge
-// (topk::k_merge_slices) are k_group's, character for character.
+// Selection (one candidate per item and one list per wave), seen cursor, slices and their merge (topk::k_merge_slices)
+// are k_group's, character for character; Z fetch / stage, the allow-bitmap scan and the base-score tiles are the
+// walk_*.inc fragments of k_recommend's walk.
 //
 // k_explore_lev: top_lev.  After the lists are final (merged), one wave per batch row recomputes the leverages of
 // the returned items with the same tiles_lev - so sqrt / multiply / add of top_lev in fp32 gives top_val back
@@ -301,43 +302,13 @@ void k_explore(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_
 
     f32x4 pf[PF];
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + EX_CHUNK - 1) / EX_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / EX_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);
@@ -359,15 +330,7 @@ void k_explore(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_
         // base scores: lane (c, 0) gets item it0 + c (tile 0) and it0 + 16 + c (tile 1)
         float sc0, sc1;
         {
-            float z0[E], z1[E];
-            load_frow<E>(&zs[c][E * q], z0);
-            load_frow<E>(&zs[16 + c][E * q], z1);
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
-            }
+#include "walk_score_tiles.inc"
             const float bi0 = b_i[min(it0 + c, n - 1)], bi1 = b_i[min(it0 + 16 + c, n - 1)];
             sc0 = walk::score(acc0[0], mu, bu, bi0);
             sc1 = walk::score(acc1[0], mu, bu, bi1);

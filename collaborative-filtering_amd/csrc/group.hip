@@ -36,7 +36,9 @@
 // and OR-reduces a 32-bit mask.  When all 64 lie below the chunk - the cursor is behind because chunks with an
 // all-zero bitmap word were skipped - the cursor jumps by a lower-bound search (as k_audience).  Allow bitmap (the
 // MASKED instantiations): k_recommend's scan - a chunk whose word is 0 is never fetched, staged or scored, every wave
-// finds the next chunk with a set bit by the same ballot, so the workgroup's barriers stay matched.
+// finds the next chunk with a set bit by the same ballot, so the workgroup's barriers stay matched.  The scan and the
+// Z fetch / stage are k_recommend's text, not copies of it: walk_allow_scan.inc, walk_z_fetch.inc, walk_z_stage.inc
+// (DESIGN section 31).
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
@@ -187,45 +189,13 @@ void k_group(int ld, int64_t ngroups, const int64_t* __restrict__ g_ptr, const i
 
     f32x4 pf[PF];
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + GR_CHUNK - 1) / GR_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / GR_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
-    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);

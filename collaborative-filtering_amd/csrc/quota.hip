@@ -11,8 +11,9 @@
 // of the walk is k_recommend's, unchanged.
 //
 // k_quota<KB, NW, CAP, MASKED>: the walk of k_recommend (recommend.hip) - staging, prefetch, score tiles, seen cursors,
-// bitmap skip, candidate test - with the per-row state of topk_rows.hpp and the capped compaction below in place of
-// topk::compact.  A kernel of its own, as k_priced (capacity.hip) is, so that no existing kernel's text changes.
+// bitmap skip: the walk_*.inc fragments that kernel includes, and its candidate test - with the
+// per-row state of topk_rows.hpp and the capped compaction below in place of topk::compact.  A kernel of its own, as
+// k_priced (capacity.hip) is, so that no existing kernel's stream changes; the text they have in common is one.
 // k_quota_merge: topk::k_merge_slices with the capped filter after every fold, the last one included.
 //
 // The capped filter (capped_keep): the sorted keys are in registers, element i = lane + 64 v.  Each lane fetches the
@@ -34,7 +35,6 @@ using topk::key_index;
 using topk::key_score;
 using topk::make_key;
 
-constexpr int QC_CHUNK = walk::CHUNK;
 constexpr int QC_WIDE = topk::ROWS_WIDE;
 constexpr int QC_NARROW = topk::ROWS_NARROW;
 
@@ -168,9 +168,9 @@ void k_quota(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t 
              const int32_t* __restrict__ group_cap, int ngroups) {
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int BUF = topk::Rows<CAP>::BUF;
-    constexpr int NT = NW * 64, NV = QC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
+    constexpr int NT = NW * 64, NV = walk::CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     __shared__ unsigned long long keys[NW * 16][CAP];
-    __shared__ __attribute__((aligned(16))) float zs[QC_CHUNK][ZS];
+    __shared__ __attribute__((aligned(16))) float zs[walk::CHUNK][ZS];
     __shared__ __attribute__((aligned(16))) int groups[NW][CAP];       // the labels of the keys a wave is compacting
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -193,52 +193,14 @@ void k_quota(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t 
         valid[r] = rb < nusers;
         const int u = users[min(rb, nusers - 1)];
         bu[r] = b_u[u];
-        cur[r] = end[r] = 0;
-        if (seen_ptr && valid[r]) {
-            int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
-            end[r] = e;
-            while (a < e) {                                              // first seen item >= lo
-                const int64_t mid = a + ((e - a) >> 1);
-                if (seen_idx[mid] < lo) a = mid + 1; else e = mid;
-            }
-            cur[r] = a;
-        }
-        nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+#include "walk_seen_cursor.inc"
     }
     topk::Rows<CAP> st;
 
     unsigned deny = 0u;     // MASKED: bit c set = item cb + c of the block `select` is called for is not allowed
     // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold test, append
     auto select = [&](const f32x4& acc, int64_t cb) {
-        unsigned msk[4] = {0u, 0u, 0u, 0u};
-        bool near = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) near = near || nxt[r] < cb + 16;
-        if (__ballot(near)) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bool more = nxt[r] < cb + 16;                            // same in the 16 lanes of the q group
-                const bool touched = more;
-                while (__ballot(more)) {
-                    int s = INT32_MAX;
-                    if (more) {
-                        const int64_t p = cur[r] + c;
-                        s = p < end[r] ? seen_idx[p] : INT32_MAX;
-                    }
-                    const bool below = more && s < cb + 16;
-                    unsigned bit = (below && s >= cb) ? 1u << (int)(s - cb) : 0u;
-                    bit |= __shfl_xor(bit, 1, 64);
-                    bit |= __shfl_xor(bit, 2, 64);
-                    bit |= __shfl_xor(bit, 4, 64);
-                    bit |= __shfl_xor(bit, 8, 64);
-                    msk[r] |= bit;
-                    const int adv = __popc((unsigned)(__ballot(below) >> (16 * q)) & 0xFFFFu);
-                    cur[r] += adv;
-                    more = more && adv == 16;                            // 16 consumed: there may be more in the block
-                }
-                if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
-            }
-        }
+#include "walk_seen_masks.inc"
         if constexpr (MASKED) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) msk[r] |= deny;
@@ -256,54 +218,22 @@ void k_quota(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t 
 
     f32x4 pf[PF];
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + QC_CHUNK - 1) / QC_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / QC_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
-    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);
-        if (nx < nch) { fetch(lo + nx * QC_CHUNK); window(nx + 1); }
+        if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }
     } else if (nch > 0) {
         fetch(lo);
     }
     for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
-        const int64_t it0 = lo + ch * QC_CHUNK;
+        const int64_t it0 = lo + ch * walk::CHUNK;
         unsigned word = 0u;
         if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
         __syncthreads();                                 // every wave is done with the previous chunk
@@ -311,30 +241,22 @@ void k_quota(int ld, int64_t nusers, const int32_t* __restrict__ users, int64_t 
         __syncthreads();
         if constexpr (MASKED) {
             nx = after(ch);
-            if (nx < nch) { fetch(lo + nx * QC_CHUNK); window(nx + 1); }      // however far ahead
+            if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }      // however far ahead
         } else if (ch + 1 < nch) {
-            fetch(it0 + QC_CHUNK);
+            fetch(it0 + walk::CHUNK);
         }
-        float z0[E], z1[E];
-        load_frow<E>(&zs[c][E * q], z0);
-        load_frow<E>(&zs[16 + c][E * q], z1);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
-        }
+#include "walk_score_tiles.inc"
         if constexpr (MASKED) deny = ~word & 0xFFFFu;
         select(acc0, it0);
         if constexpr (MASKED) deny = ~word >> 16;
         select(acc1, it0 + 16);
         bool full = false;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) full = full || st.cnt[r] > BUF - QC_CHUNK;
+        for (int r = 0; r < 4; ++r) full = full || st.cnt[r] > BUF - walk::CHUNK;
         if (__ballot(full)) {                            // some row's buffer could overflow in the next chunk
             wave_lds_sync();
             for (int R = 0; R < 16; ++R)
-                if (topk::row_cnt(st, R) > BUF - QC_CHUNK)
+                if (topk::row_cnt(st, R) > BUF - walk::CHUNK)
                     compact_capped<CAP>(kw, st, R, topn, lane, gw, item_group, group_cap, ngroups);
         }
     }

@@ -29,9 +29,10 @@
 // chunk, prefetched behind the Z loads, ANDed into the candidate test; a wave none of whose rows has a set bit in the
 // chunk counts nothing but still stages and passes both barriers.  Not combined with MASKED.
 //
-// "k_recommend's" above means a second copy of that code in this file, not a shared implementation: only the chunk and
-// slice arithmetic and the score epilogue are shared (catalogue_walk.hpp, which says why the rest is not).  An edit
-// to the walk in recommend.hip belongs here too.
+// "k_recommend's" above means the same text, not a copy of it: Z fetch / stage, the bitmap scan, the
+// cursor set-up (with `u` naming su[r]), the exclusion walk and the score tiles are the walk_*.inc fragments that
+// recommend.hip includes too, next to the chunk and slice arithmetic and the score epilogue of catalogue_walk.hpp, which
+// says why the fragments are included text and not functions.  The candidate test and the chunk loop are this kernel's.
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
@@ -42,7 +43,6 @@ namespace {
 
 using topk::make_key;
 
-constexpr int RK_CHUNK = walk::CHUNK;
 constexpr int RK_TP = 16;           // targets per row and pass (4 * RK_TP counters per lane)
 constexpr int RK_TG = 8;            // targets per skip group
 constexpr unsigned long long RK_NONE = ~0ull;   // target key of a NaN score / an unused slot: nothing is above it
@@ -58,9 +58,9 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
                   int64_t seg_stride, const int32_t* __restrict__ row_seg) {
     static_assert(!SEG || !MASKED, "the eligibility table replaces the bitmap");
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
-    constexpr int NT = NW * 64, NV = RK_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
+    constexpr int NT = NW * 64, NV = walk::CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     __shared__ unsigned long long tks[NW * 16][RK_TP];
-    __shared__ __attribute__((aligned(16))) float zs[RK_CHUNK][ZS];
+    __shared__ __attribute__((aligned(16))) float zs[walk::CHUNK][ZS];
     __shared__ int wg_tmax;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -86,7 +86,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         if constexpr (SEG) {
             const int64_t sg = row_seg[min(rb, nq - 1)];
             sv[r] = valid[r] && sg >= 0 && sg < nseg;
-            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / RK_CHUNK;       // lo is a multiple of 32
+            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / walk::CHUNK;       // lo is a multiple of 32
         }
     }
     // target range of row c (the row whose targets this lane gathers) and the largest count of the wave's rows
@@ -108,45 +108,13 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
 
     f32x4 pf[PF];
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + RK_CHUNK - 1) / RK_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / RK_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
-    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     // SEG: the words of chunk `ch` in the segment rows of this lane's rows 4q + r, 0 for a row that takes no part;
     // ch < nch keeps the word inside the table row (lo / 32 + ch < ceil(n / 32) <= seg_stride)
     unsigned sp[4] = {0u, 0u, 0u, 0u};
@@ -195,52 +163,15 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         int nxt[4];                                                      // next seen item of rows 4q + r
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            cur[r] = end[r] = 0;
-            if (seen_ptr && valid[r]) {
-                int64_t a = seen_ptr[su[r]], e = seen_ptr[su[r] + 1];
-                end[r] = e;
-                while (a < e) {                                          // first seen item >= lo
-                    const int64_t mid = a + ((e - a) >> 1);
-                    if (seen_idx[mid] < lo) a = mid + 1; else e = mid;
-                }
-                cur[r] = a;
-            }
-            nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+            const int u = su[r];                                         // the name the fragment reads
+#include "walk_seen_cursor.inc"
         }
 
         unsigned deny = 0u; // MASKED: bit c set = item cb + c of the block `keys_of` is called for is not allowed
         unsigned dn[4] = {0u, 0u, 0u, 0u};                               // SEG: the same, one word per row 4q + r
         // one 16-item block [cb, cb + 16): keys of the lane's four scores, 0 where the score is no candidate
         auto keys_of = [&](const f32x4& acc, int64_t cb, unsigned long long (&key)[4]) {
-            unsigned msk[4] = {0u, 0u, 0u, 0u};
-            bool near = false;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) near = near || nxt[r] < cb + 16;
-            if (__ballot(near)) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bool more = nxt[r] < cb + 16;                        // same in the 16 lanes of the q group
-                    const bool touched = more;
-                    while (__ballot(more)) {
-                        int s = INT32_MAX;
-                        if (more) {
-                            const int64_t p = cur[r] + c;
-                            s = p < end[r] ? seen_idx[p] : INT32_MAX;
-                        }
-                        const bool below = more && s < cb + 16;
-                        unsigned bit = (below && s >= cb) ? 1u << (int)(s - cb) : 0u;
-                        bit |= __shfl_xor(bit, 1, 64);
-                        bit |= __shfl_xor(bit, 2, 64);
-                        bit |= __shfl_xor(bit, 4, 64);
-                        bit |= __shfl_xor(bit, 8, 64);
-                        msk[r] |= bit;
-                        const int adv = __popc((unsigned)(__ballot(below) >> (16 * q)) & 0xFFFFu);
-                        cur[r] += adv;
-                        more = more && adv == 16;                        // 16 consumed: there may be more in the block
-                    }
-                    if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
-                }
-            }
+#include "walk_seen_masks.inc"
             if constexpr (MASKED) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) msk[r] |= deny;
@@ -263,13 +194,13 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
         int64_t nx = 0;                                  // MASKED: the chunk after ch that is counted
         if constexpr (MASKED) {
             nx = next_chunk(0);
-            if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }
+            if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }
         } else if (nch > 0) {
             fetch(lo);
             if constexpr (SEG) seg_fetch(0);
         }
         for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
-            const int64_t it0 = lo + ch * RK_CHUNK;
+            const int64_t it0 = lo + ch * walk::CHUNK;
             unsigned word = 0u;
             if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
             unsigned sw[4] = {0u, 0u, 0u, 0u};           // SEG: this chunk's words, before the prefetch reuses sp
@@ -282,9 +213,9 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
             __syncthreads();
             if constexpr (MASKED) {
                 nx = after(ch);
-                if (nx < nch) { fetch(lo + nx * RK_CHUNK); window(nx + 1); }      // however far ahead
+                if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }      // however far ahead
             } else if (ch + 1 < nch) {
-                fetch(it0 + RK_CHUNK);
+                fetch(it0 + walk::CHUNK);
                 if constexpr (SEG) seg_fetch(ch + 1);
             }
             if (!active) continue;                       // wave-uniform: this wave's rows have no targets left
@@ -293,15 +224,7 @@ void k_rank_count(int ld, int64_t nq, const int32_t* __restrict__ users, const i
                 // has staged its share and passed both barriers; its counters are as the last chunk left them
                 if (!__ballot((sw[0] | sw[1] | sw[2] | sw[3]) != 0u)) continue;
             }
-            float z0[E], z1[E];
-            load_frow<E>(&zs[c][E * q], z0);
-            load_frow<E>(&zs[16 + c][E * q], z1);
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
-            }
+#include "walk_score_tiles.inc"
             unsigned long long k0[4], k1[4];
             if constexpr (MASKED) deny = ~word & 0xFFFFu;
             if constexpr (SEG) {

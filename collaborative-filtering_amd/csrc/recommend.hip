@@ -34,7 +34,7 @@
 // is no ceiling, 0 closes the slice for the user.  A workgroup none of whose 64 users is open for its slice returns
 // before the first barrier (every wave reads the same 64 ceilings, one per lane, so the decision is the workgroup's),
 // as does every workgroup of a round whose predecessor raised no flag (*go == 0).  The lists always go to the workspace
-// as raw keys, 128 per (slice, user).  The walk itself is untouched, and so is rank_eval.hip's copy: the ceiling is one
+// as raw keys, 128 per (slice, user).  The walk itself is untouched, and so is k_rank_count's: the ceiling is one
 // more term of the candidate test, which k_rank_count does not have.  The instantiations without DEEP contain none of
 // this: their instruction streams are those of the kernel without the parameter.
 //
@@ -47,10 +47,11 @@
 // it stages its share and passes both barriers, so they stay matched.  The seen cursors catch up as under MASKED.
 // SEG is combined with neither MASKED nor DEEP, and the other instantiations contain none of it.
 //
-// The walk is written a second time in rank_eval.hip (k_rank_count), character for character apart from the RC_ / RK_
-// prefix: fetch / stage, next_chunk / window / after, the cursor set-up, the exclusion walk, the score tiles, the
-// candidate test, the chunk loop.  Only the chunk and slice arithmetic and the score epilogue are one copy
-// (catalogue_walk.hpp, which says why the rest is not): an edit to the walk here belongs there too.
+// The walk has one text: the walk_*.inc fragments included below at their points of use - cursor
+// set-up, exclusion walk, Z fetch / stage, bitmap scan, score tiles, and the row state with its compaction and
+// write-out - are the same files k_rank_count (rank_eval.hip), k_priced (capacity.hip) and k_quota (quota.hip) include,
+// so an edit to a fragment is an edit to all of them.  What is this kernel's own stays here: the DEEP / SEG lines, the
+// candidate test, the chunk loop.  catalogue_walk.hpp says why the pieces are included text and not functions.
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "catalogue_walk.hpp"
@@ -65,7 +66,6 @@ using topk::key_index;
 using topk::key_score;
 using topk::make_key;
 
-constexpr int RC_CHUNK = walk::CHUNK;
 constexpr int RC_WIDE = topk::ROWS_WIDE;         // users per workgroup, topn > 32: 4 waves, 256 keys per user
 constexpr int RC_NARROW = topk::ROWS_NARROW;     // users per workgroup, topn <= 32: 8 waves, 128 keys per user
 
@@ -85,10 +85,10 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     static_assert(!SEG || (!MASKED && !DEEP), "the eligibility table replaces the bitmap; deep lists do not take one");
     constexpr int E = 4 * KB, LD = 16 * KB, ZS = walk::lds_row_stride(KB);
     constexpr int L = CAP == 256 ? 128 : 32, BUF = CAP - L;
-    constexpr int NT = NW * 64, NV = RC_CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
+    constexpr int NT = NW * 64, NV = walk::CHUNK * LD / 4, PF = (NV + NT - 1) / NT;
     static_assert(L >= 32 && BUF >= 64, "a chunk appends up to 32 keys per row");
     __shared__ unsigned long long keys[NW * 16][CAP];
-    __shared__ __attribute__((aligned(16))) float zs[RC_CHUNK][ZS];
+    __shared__ __attribute__((aligned(16))) float zs[walk::CHUNK][ZS];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -123,84 +123,17 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         if constexpr (SEG) {
             const int64_t sg = row_seg[min(rb, nusers - 1)];
             sv[r] = valid[r] && sg >= 0 && sg < nseg;
-            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / RC_CHUNK;       // lo is a multiple of 32
+            so[r] = (sv[r] ? sg : 0) * seg_stride + lo / walk::CHUNK;    // lo is a multiple of 32
         }
-        cur[r] = end[r] = 0;
-        if (seen_ptr && valid[r]) {
-            int64_t a = seen_ptr[u], e = seen_ptr[u + 1];
-            end[r] = e;
-            while (a < e) {                                              // first seen item >= lo
-                const int64_t mid = a + ((e - a) >> 1);
-                if (seen_idx[mid] < lo) a = mid + 1; else e = mid;
-            }
-            cur[r] = a;
-        }
-        nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
+#include "walk_seen_cursor.inc"
     }
-    unsigned long long thr[4] = {0ull, 0ull, 0ull, 0ull};    // key of the current topn-th entry (0: list not full)
-    int cnt[4] = {0, 0, 0, 0};                                // buffered survivors (same in the 16 lanes of a q group)
-    int nlist[4] = {0, 0, 0, 0};                              // valid entries of the sorted list
-
-    auto compact = [&](int r) {        // wave-uniform r: list + buffer of row r -> sorted list, new threshold
-        const int rq = r >> 2, re = r & 3;
-        int rc = 0, rn = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { rc = (re == e) ? cnt[e] : rc; rn = (re == e) ? nlist[e] : rn; }
-        rc = readlane_i(rc, 16 * rq);
-        rn = readlane_i(rn, 16 * rq);
-        unsigned long long k[CAP / 64];
-#pragma unroll
-        for (int v = 0; v < CAP / 64; ++v) {
-            const int i = lane + 64 * v;
-            const bool live = (i < rn) || (i >= L && i < L + rc);
-            k[v] = live ? kw[r][i] : 0ull;
-        }
-        topk::sort_desc<CAP / 64>(k, lane);
-#pragma unroll
-        for (int v = 0; v < CAP / 64; ++v)
-            if (lane + 64 * v < L) kw[r][lane + 64 * v] = k[v];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        const int nn = min(topn, rn + rc);
-        const unsigned long long t = (nn == topn) ? kw[r][topn - 1] : 0ull;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (q == rq && e == re) { thr[e] = t; cnt[e] = 0; nlist[e] = nn; }
-    };
+#include "walk_row_lists.inc"
 
     unsigned deny = 0u;     // MASKED: bit c set = item cb + c of the block `select` is called for is not allowed
     unsigned dn[4] = {0u, 0u, 0u, 0u};                                   // SEG: the same, one word per row 4q + r
     // one 16-item block [cb, cb + 16): scores from the accumulator, seen mask, threshold test, append
     auto select = [&](const f32x4& acc, int64_t cb) {
-        unsigned msk[4] = {0u, 0u, 0u, 0u};
-        bool near = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) near = near || nxt[r] < cb + 16;
-        if (__ballot(near)) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bool more = nxt[r] < cb + 16;                            // same in the 16 lanes of the q group
-                const bool touched = more;
-                while (__ballot(more)) {
-                    int s = INT32_MAX;
-                    if (more) {
-                        const int64_t p = cur[r] + c;
-                        s = p < end[r] ? seen_idx[p] : INT32_MAX;
-                    }
-                    const bool below = more && s < cb + 16;
-                    unsigned bit = (below && s >= cb) ? 1u << (int)(s - cb) : 0u;
-                    bit |= __shfl_xor(bit, 1, 64);
-                    bit |= __shfl_xor(bit, 2, 64);
-                    bit |= __shfl_xor(bit, 4, 64);
-                    bit |= __shfl_xor(bit, 8, 64);
-                    msk[r] |= bit;
-                    const int adv = __popc((unsigned)(__ballot(below) >> (16 * q)) & 0xFFFFu);
-                    cur[r] += adv;
-                    more = more && adv == 16;                            // 16 consumed: there may be more in the block
-                }
-                if (touched) nxt[r] = cur[r] < end[r] ? seen_idx[cur[r]] : INT32_MAX;
-            }
-        }
+#include "walk_seen_masks.inc"
         if constexpr (MASKED) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) msk[r] |= deny;
@@ -226,45 +159,13 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
 
     f32x4 pf[PF];
     auto fetch = [&](int64_t it0) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                pf[p] = *reinterpret_cast<const f32x4*>(Z + (size_t)min(it0 + i, n - 1) * ld + 4 * d);
-            }
-        }
+#include "walk_z_fetch.inc"
     };
     auto stage = [&]() {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const int v = tid + p * NT;
-            if (v < NV) {
-                const int i = v / (LD / 4), d = v - i * (LD / 4);
-                *reinterpret_cast<f32x4*>(&zs[i][4 * d]) = pf[p];
-            }
-        }
+#include "walk_z_stage.inc"
     };
 
-    const int64_t nch = hi > lo ? (hi - lo + RC_CHUNK - 1) / RC_CHUNK : 0;
-    const uint32_t* aw = MASKED ? allow + lo / RC_CHUNK : nullptr;      // word of chunk 0 (lo is a multiple of 32)
-    // first chunk >= ch with an allowed item, nch if there is none: the same value in every wave of the workgroup
-    auto next_chunk = [&](int64_t ch) -> int64_t {
-        for (; ch < nch; ch += 64) {
-            const unsigned w = ch + lane < nch ? aw[ch + lane] : 0u;
-            const unsigned long long m = __ballot(w != 0u);
-            if (m) return ch + __builtin_ctzll(m);
-        }
-        return nch;
-    };
-    // the scan is kept off the prefetch's path: while chunk ch is scored, this lane's word of the window
-    // [ch + 1, ch + 65) is in flight behind the Z loads, and the chunk after ch is read off it by one ballot
-    unsigned pw = 0u;
-    auto window = [&](int64_t from) { pw = from + lane < nch ? aw[from + lane] : 0u; };
-    auto after = [&](int64_t ch) -> int64_t {
-        const unsigned long long m = __ballot(pw != 0u);
-        return m ? ch + 1 + __builtin_ctzll(m) : next_chunk(ch + 65);
-    };
+#include "walk_allow_scan.inc"
     // SEG: the words of chunk `ch` in the segment rows of this lane's rows 4q + r, 0 for a row that takes no part;
     // ch < nch keeps the word inside the table row (lo / 32 + ch < ceil(n / 32) <= seg_stride)
     unsigned sp[4] = {0u, 0u, 0u, 0u};
@@ -275,13 +176,13 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
     int64_t nx = 0;                                      // MASKED: the chunk after ch that is scored
     if constexpr (MASKED) {
         nx = next_chunk(0);
-        if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }
+        if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }
     } else if (nch > 0) {
         fetch(lo);
         if constexpr (SEG) seg_fetch(0);
     }
     for (int64_t ch = nx; ch < nch; ch = MASKED ? nx : ch + 1) {
-        const int64_t it0 = lo + ch * RC_CHUNK;
+        const int64_t it0 = lo + ch * walk::CHUNK;
         unsigned word = 0u;
         if constexpr (MASKED) word = __builtin_amdgcn_readfirstlane(aw[ch]);
         unsigned sw[4] = {0u, 0u, 0u, 0u};               // SEG: this chunk's words, before the prefetch reuses sp
@@ -294,9 +195,9 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
         __syncthreads();
         if constexpr (MASKED) {
             nx = after(ch);
-            if (nx < nch) { fetch(lo + nx * RC_CHUNK); window(nx + 1); }      // however far ahead
+            if (nx < nch) { fetch(lo + nx * walk::CHUNK); window(nx + 1); }      // however far ahead
         } else if (ch + 1 < nch) {
-            fetch(it0 + RC_CHUNK);
+            fetch(it0 + walk::CHUNK);
             if constexpr (SEG) seg_fetch(ch + 1);
         }
         if constexpr (SEG) {
@@ -304,15 +205,7 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
             // staged its share and passed both barriers; its buffers are as the last chunk left them
             if (!__ballot((sw[0] | sw[1] | sw[2] | sw[3]) != 0u)) continue;
         }
-        float z0[E], z1[E];
-        load_frow<E>(&zs[c][E * q], z0);
-        load_frow<E>(&zs[16 + c][E * q], z1);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z0[e], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[e], z1[e], acc1, 0, 0, 0);
-        }
+#include "walk_score_tiles.inc"
         if constexpr (MASKED) deny = ~word & 0xFFFFu;
         if constexpr (SEG) {
 #pragma unroll
@@ -325,47 +218,9 @@ void k_recommend(int ld, int64_t nusers, const int32_t* __restrict__ users, int6
             for (int r = 0; r < 4; ++r) dn[r] = ~sw[r] >> 16;
         }
         select(acc1, it0 + 16);
-        bool full = false;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) full = full || cnt[r] > BUF - RC_CHUNK;
-        if (__ballot(full)) {                            // some row's buffer could overflow in the next chunk
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            for (int r = 0; r < 16; ++r) {
-                int rc = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
-                rc = readlane_i(rc, 16 * (r >> 2));
-                if (rc > BUF - RC_CHUNK) compact(r);
-            }
-        }
+#include "walk_row_overflow.inc"
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    for (int r = 0; r < 16; ++r) {
-        int rc = 0, rn = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) rc = ((r & 3) == e) ? cnt[e] : rc;
-        rc = readlane_i(rc, 16 * (r >> 2));
-        if (rc > 0) compact(r);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) rn = ((r & 3) == e) ? nlist[e] : rn;
-        rn = readlane_i(rn, 16 * (r >> 2));
-        const int64_t rb = b0 + r;
-        if (rb >= nusers) continue;
-        if (part) {                                      // sliced: raw keys of (slice, user), 0 = empty
-            unsigned long long* dst = part + ((int64_t)blockIdx.y * nusers + rb) * topn;
-            for (int t = lane; t < topn; t += 64) dst[t] = t < rn ? kw[r][t] : 0ull;
-        } else {
-            for (int t = lane; t < topn; t += 64) {
-                const bool ok = t < rn;
-                const unsigned long long key = ok ? kw[r][t] : 0ull;
-                top_val[rb * topn + t] = ok ? key_score(key) : -INFINITY;
-                top_idx[rb * topn + t] = ok ? key_index(key) : -1;
-            }
-            if (lane == 0) top_cnt[rb] = rn;
-        }
-    }
+#include "walk_row_write.inc"
 }
 
 // seg: the SEG instantiations (`allow` is then the eligibility table); otherwise MASKED when there is a bitmap

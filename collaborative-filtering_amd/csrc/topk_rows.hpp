@@ -1,8 +1,9 @@
 // Per-row selection state of a wave that serves 16 batch rows of a catalogue walk, and the merge of per-slice lists:
-// what k_recommend (recommend.hip) keeps in lambdas, in shared form.  k_similar and k_audience use the per-row state;
-// k_group and k_explore keep one list per wave and use the merge alone, as does recommend.hip, whose kernel keeps its
-// own text of the state (catalogue_walk.hpp says why: sharing it moved the register allocation).  The merge is
-// launched by topk::merge_slices below, with the slice plan of topk_launch.hpp.
+// what k_recommend (recommend.hip) keeps in lambdas, in function form.  k_similar, k_audience and k_quota use the
+// per-row state; k_group and k_explore keep one list per wave and use the merge alone, as do recommend.hip and
+// capacity.hip, whose kernels keep the lambda form of the state - one text as well, the fragments walk_row_lists.inc,
+// walk_row_overflow.inc and walk_row_write.inc (catalogue_walk.hpp says why: the function form moved their register
+// allocation).  The merge is launched by topk::merge_slices below, with the slice plan of topk_launch.hpp.
 //
 // Layout: lane (c, q) = (lane & 15, lane >> 4) holds the state of the rows 4q + r, r = 0 ... 3, the same value in the 16
 // lanes of a q group; row R of the wave owns kw[R][0 .. CAP): the sorted list [0, L) and the survivor buffer

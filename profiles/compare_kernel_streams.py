@@ -11,7 +11,7 @@ list left out: a flag that did not exist is a flag that is off.  Two kernels are
 encodings are, line by line (addresses dropped, branch offsets kept).  A kernel only the new build has is counted, one
 only the old build has is reported under its object's line.  Prints one line per object and a total; exit status 1
 when a kernel that both builds have differs, when an object of the old directory has no namesake in the new one, or
-when nothing was compared.  (DESIGN.md sections 19, 26, 27 and 28 record outcomes.)"""
+when nothing was compared.  (DESIGN.md sections 19, 26, 27, 28 and 31 record outcomes.)"""
 import os
 import re
 import shutil
