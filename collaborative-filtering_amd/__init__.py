@@ -8,6 +8,7 @@ The directory is named `collaborative-filtering_amd`; the importable alias
 """
 from .als_config import ALSConfig, BiasesConfig, CoreConfig, GraphConfig, GraphSimConfig
 from .als import ALS, CapacityInfo, Explanation, FoldedItems, ItemEligibility
+from .implicit import ImplicitALS, ImplicitConfig
 from .helpers import (ES_MIN_ITERS, ES_TOL, DEFAULT_RANDOM_STATE, cholesky_solve, make_config,
                       normalize_params, rmse_on_indices)
 
@@ -15,6 +16,6 @@ from . import cv                     # sparse CV / ablation harness (SURVEY 8(f)
 from . import features               # feature normaliser
 from . import sweep                  # resident-data hyper-parameter sweep driver
 
-__all__ = ["ALS", "CapacityInfo", "Explanation", "FoldedItems", "ItemEligibility", "cv", "features", "sweep", "ALSConfig", "BiasesConfig", "CoreConfig", "GraphConfig", "GraphSimConfig",
+__all__ = ["ALS", "ImplicitALS", "ImplicitConfig", "CapacityInfo", "Explanation", "FoldedItems", "ItemEligibility", "cv", "features", "sweep", "ALSConfig", "BiasesConfig", "CoreConfig", "GraphConfig", "GraphSimConfig",
            "cholesky_solve", "make_config", "normalize_params", "rmse_on_indices",
            "ES_TOL", "ES_MIN_ITERS", "DEFAULT_RANDOM_STATE"]

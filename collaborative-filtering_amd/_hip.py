@@ -31,7 +31,8 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_recommend_deep_workspace_bytes", "als_recommend_deep",
            "als_recommend_topk_segmented", "als_rank_count_segmented", "als_eligibility_bitmaps",
            "als_recommend_topk_priced", "als_capacity_settle_workspace_bytes", "als_capacity_settle",
-           "als_recommend_topk_quota")
+           "als_recommend_topk_quota",
+           "als_table_gram_partials", "als_table_gram_f64", "als_implicit_row_solve")
 
 # the workspace queries: they return size_t, everything else but the two slot-size queries an int status / value
 SIZE_QUERIES = ("als_spd_solve_workspace_bytes", "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
@@ -127,6 +128,17 @@ class ExplainParams(C.Structure):
         ("score", _vp), ("latent", _vp), ("leverage", _vp),
         ("top_item", _vp), ("top_contrib", _vp), ("top_weight", _vp), ("top_cnt", _vp),
         ("b_u_out", _vp), ("status", _vp),
+    ]
+
+
+class ImplicitParams(C.Structure):
+    """struct als_implicit_params (include/als_hip.h)."""
+    _fields_ = [
+        ("k", _i32), ("ld", _i32), ("nrows", _i64), ("ncols", _i64), ("F_zero_row", _i32), ("reserved", _i32),
+        ("indptr", _vp), ("indices", _vp), ("gram_w", _vp), ("rhs_w", _vp), ("F", _vp), ("G", _vp),
+        ("G_scale", C.c_double), ("lambda_scalar", _f32), ("lambda_row", _vp),
+        ("X_out", _vp), ("xb_out", _vp), ("status", _vp),
+        ("tasks", _vp), ("ntasks", _i64), ("long_rows", _vp), ("nlong", _i64), ("workspace", _vp),
     ]
 
 
@@ -227,6 +239,8 @@ def load():
     lib.als_calibrated_rerank.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _vp, _f32, _f32,
                                           C.c_int, _vp, _vp, _vp, _vp, _vp]
     lib.als_list_miscalibration.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _f32, _vp, _vp]
+    lib.als_table_gram_f64.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]
+    lib.als_implicit_row_solve.argtypes = [C.POINTER(ImplicitParams), _vp]
     lib.als_graph_classify.argtypes =[_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]
     lib.als_impute_col_median.argtypes = [_i64, C.c_int, _vp, _vp, _vp]

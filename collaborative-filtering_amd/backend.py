@@ -533,6 +533,40 @@ class HipBackend:
         p.V_out, p.b_i_out, p.status = _p(V_out), _p(b_i_out), _p(status)
         self._check(self.lib.als_fold_in_items(C.byref(p), self._stream()), "als_fold_in_items")
 
+    # -- K18 -------------------------------------------------------------------
+    def table_gram_doubles(self, ld: int) -> int:
+        """Doubles of one Gram image of als_table_gram_f64: the lower 16 x 16 blocks of an ld x ld matrix."""
+        kb = ld // 16
+        return kb * (kb + 1) // 2 * 256
+
+    def table_gram(self, k, ld, F, out):
+        """out fp64 [table_gram_doubles(ld)] = F^T F over all rows of the fp32 table F [rows, ld], the perm-space
+        lower-block image als_implicit_row_solve takes: als_table_gram_f64.  The partials are owned here."""
+        assert F.dtype == torch.float32 and F.is_contiguous() and F.shape[1] == ld
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= self.table_gram_doubles(ld)
+        need = 8 * int(self.lib.als_table_gram_partials()) * self.table_gram_doubles(ld)
+        self._check(self.lib.als_table_gram_f64(k, ld, F.shape[0], _p(F), self._workspace("table_gram", need), _p(out),
+                                                self._stream()), "als_table_gram_f64")
+
+    def implicit_row_solve(self, *, k, ld, side, F, zero_row, G, g_scale, lam, lam_row, X_out, xb_out, status, tasks,
+                           rhs_w=None):
+        """x = (g_scale G + sum a f f^T + (lam + 1e-10) I)^-1 sum t f for the rows of `tasks` (side.vals holds the
+        weights a; rhs_w the t, None: t = 1 + a); rows of `side` without entries get x = 0: als_implicit_row_solve.
+        zero_row: the row of F that lanes past a row's end gather, or -1.  The slot workspace is owned here."""
+        p = _hip.ImplicitParams()
+        p.k, p.ld, p.nrows, p.ncols, p.F_zero_row = k, ld, side.nrows, F.shape[0], int(zero_row)
+        assert F.dtype == torch.float32 and F.is_contiguous() and F.shape[1] == ld and -1 <= int(zero_row) < F.shape[0]
+        assert X_out.is_contiguous() and X_out.shape[0] >= side.nrows and X_out.shape[1] == ld
+        assert G.dtype == torch.float64 and G.numel() >= self.table_gram_doubles(ld)
+        p.indptr, p.indices, p.gram_w, p.rhs_w = _p(side.indptr), _p(side.indices), _p(side.vals), _p(rhs_w)
+        p.F, p.G, p.G_scale = _p(F), _p(G), float(g_scale)
+        p.lambda_scalar, p.lambda_row = float(lam), _p(lam_row)
+        p.X_out, p.xb_out, p.status = _p(X_out), _p(xb_out), _p(status)
+        p.tasks, p.ntasks = _p(tasks.tasks), tasks.ntasks
+        p.long_rows, p.nlong = _p(tasks.long_rows), tasks.nlong
+        p.workspace = self._workspace("implicit_slots", tasks.nslots * self.slot_bytes(k, True))
+        self._check(self.lib.als_implicit_row_solve(C.byref(p), self._stream()), "als_implicit_row_solve")
+
     # -- K11 -------------------------------------------------------------------
     def explain(self, *, k, ld, indptr, indices, vals, rows, n, Z, b_i, mu, lam_u, lam_bu, n_sweeps, t_ptr, t_items,
                 topm, largest, score, latent, leverage, top_item, top_contrib, top_weight, top_cnt, b_u_out, status):

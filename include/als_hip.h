@@ -965,6 +965,60 @@ int als_list_miscalibration(int ncat, int ldc, int64_t nrows, int64_t n, const f
                             const int32_t* idx, float alpha, float* kl, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Implicit feedback: the confidence-weighted fit of Hu, Koren and Volinsky (ICDM 2008), the model behind
+ * ImplicitALS.  A half-step solves, for every row with entries t (rows f_t of the other side's table F):
+ *     A = G + sum_t a_t f_t f_t^T + (lambda(row) + 1e-10) I,   b = sum_t t_t f_t,   x = A^-1 b,
+ * where G = a0 F^T F over ALL rows of F stands for the unobserved entries and is the same for every row.
+ *
+ * als_table_gram_f64: G_out = F^T F over the nrows rows of the fp32 table F [nrows][ld] (16-byte aligned), accumulated
+ *   in fp64 on the fp64 matrix cores.  A fixed grid of als_table_gram_partials() workgroups, each summing a contiguous
+ *   row range into its partial, and a second launch that adds the partials in index order: the result is bitwise
+ *   reproducible and a function of (F, nrows, k) alone.  Columns k .. ld-1 of F contribute zero whatever they hold;
+ *   nrows == 0 gives G = 0.
+ *   G_out: the LOWER-BLOCK PERM-SPACE IMAGE the fp64 row kernels factorise - (ld/16)(ld/16 + 1)/2 blocks of 16 x 16
+ *   doubles, block (I, K), K <= I, at offset 256 (I (I + 1) / 2 + K), row-major inside a block, element (r, c) of it
+ *   being G[col(16 I + r)][col(16 K + c)] with col(p) the factor column at perm position p (als_perm_index) - chosen
+ *   over natural order because als_implicit_row_solve then adds G to a row's image with one linear pass.  Diagonal
+ *   blocks are full and symmetric; positions of padding columns are exactly zero.
+ *   partials: scratch of als_table_gram_partials() images (256 (ld/16)(ld/16 + 1)/2 doubles each).
+ *
+ * als_implicit_row_solve: the per-row solve above, one wave per task, fp64 throughout on the fp32-stored F; only x
+ *   is rounded to fp32.  tasks / long_rows / workspace as als_row_solve takes them (als_host_row_tasks; slots are
+ *   als_partial_slot_bytes_f64(k) bytes, summed in slot order; no wave takes more than ALS_SPLIT_CHUNK entries).
+ *   A row's result depends on its own entries, F and G alone.  Rows with entries that no task names are left
+ *   untouched; rows WITHOUT entries (of all nrows) get x = 0, x.b = 0.  nrows == 0 is a no-op.
+ * ------------------------------------------------------------------------- */
+typedef struct als_implicit_params {
+    int32_t k, ld;                  /* ld = als_padded_k(k) */
+    int64_t nrows;                  /* rows of this orientation, < 2^31 - 1 */
+    int64_t ncols;                  /* rows of F, >= 1; ncols * ld < 2^31 */
+    int32_t F_zero_row;             /* the row of F that lanes past the end of a row gather: any row in [0, ncols), or
+                                       -1 = F has no spare row (row 0 is read).  Those lanes carry a = t = 0, which
+                                       removes them exactly, so the row need not be zero - only finite */
+    int32_t reserved;
+    const int64_t* indptr;          /* [nrows + 1] */
+    const int32_t* indices;         /* [nnz], in [0, ncols) */
+    const float*   gram_w;          /* [nnz] a_t; >= 0 by contract (A is then positive definite for lambda >= 0) */
+    const float*   rhs_w;           /* nullable [nnz] t_t; NULL: t_t = 1 + a_t (preference 1 with confidence 1 + a) */
+    const float*   F;               /* [ncols][ld], padding columns zero, 16-byte aligned */
+    const double*  G;               /* als_table_gram_f64 image of F (or any symmetric image in that layout) */
+    double         G_scale;         /* a0, the weight of the unobserved entries: A = G_scale G + ... */
+    float          lambda_scalar;   /* >= 0 */
+    const float*   lambda_row;      /* nullable [nrows] */
+    float*         X_out;           /* [nrows][ld], padding columns written as zero */
+    double*        xb_out;          /* nullable [nrows]: x.b with the unrounded x (the closed-form loss) */
+    int32_t*       status;          /* as als_row_solve: 0 on entry; a non-positive (or NaN) pivot stores row + 1 by
+                                       atomicMax */
+    const als_task*     tasks;      int64_t ntasks;
+    const als_long_row* long_rows;  int64_t nlong;
+    void*          workspace;       /* 16-byte aligned; may be NULL when nlong == 0 */
+} als_implicit_params;
+
+int als_table_gram_partials(void);
+int als_table_gram_f64(int k, int ld, int64_t nrows, const float* F, double* partials, double* G_out, void* stream);
+int als_implicit_row_solve(const als_implicit_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Item-feature normalisation (scripts/prepare_features.py:95-124, 131-201) of a float64 [n][d] matrix X (device):
  * method 0 none (cast), 1 row_l1, 2 row_l2, 3 col_zscore, 4 col_minmax; out: float32 [n][d].  Sums run in numpy's
  * order, so out is bitwise the reference's result.  colwork: 2*d doubles (methods 3, 4).  status (device int32,
