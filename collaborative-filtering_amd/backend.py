@@ -9,6 +9,7 @@ can be exercised on CPU under gloo with a stand-in solver living in tests/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -129,12 +130,28 @@ class HipBackend:
         return int(self.lib.als_partial_slot_bytes(k))
 
     # -- K1 ------------------------------------------------------------------
+    @staticmethod
+    def residual_scale(max_abs_val: float) -> float:
+        """als_row_solve_params::R_scale for ratings of magnitude up to `max_abs_val`: the power of two that puts
+        max_abs_val in [2^9, 2^10), clamped to 2^-126 ... 2^126 so that the scale and its inverse are normal fp32
+        numbers; 1.0 for a side without ratings (0, or not finite).  The pre-split path of the row solve rounds
+        (residual * scale) to two fp16 terms: 2^6 of headroom for mu and the biases below the fp16 overflow, a normal
+        low term down to 2^-13 of the largest rating.  A per-fit constant: the ratings do not change between
+        iterations, so it needs no device read and is the same under graph replay as in the eager fit."""
+        v = float(max_abs_val)
+        if not (0.0 < v < float("inf")):
+            return 1.0
+        e = math.frexp(v)[1] - 1                     # v in [2^e, 2^(e+1))
+        return math.ldexp(1.0, max(-126, min(126, 9 - e)))
+
     def row_solve(self, *, k, ld, side, F, zero_row, bias_self, bias_other, mu, lam, lam_row, lam_b,
                   lam_b_row, rhs_extra, diag_extra, X_out, bias_out, gram_out, factor_out,
                   rhs_out, colsum_out, sumr_out, status, tasks, workspace, sumr2_out=None, stat_out=None,
-                  f64=False):
+                  f64=False, residual_scale=0.0):
         """`f64`: this call in fp64 whatever the backend's mode, by-product arrays (gram_out, factor_out, rhs_out,
-        colsum_out, sumr_out, sumr2_out) being DOUBLE tensors (the engine's fp64 V-step)."""
+        colsum_out, sumr_out, sumr2_out) being DOUBLE tensors (the engine's fp64 V-step).
+        `residual_scale`: als_row_solve_params::R_scale, `residual_scale(max |side.vals|)` - read by the pre-split
+        path alone; 0 leaves its residual pair unscaled (ratings of order 1 ... 10^3)."""
         p = _hip.RowSolveParams()
         p.k, p.ld, p.nrows, p.F_zero_row = k, ld, side.nrows, int(zero_row)
         p.reserved0 = self.ablate          # 0 in production; profiling builds of bench.py set it
@@ -169,6 +186,7 @@ class HipBackend:
             if buf is None:
                 buf = self._planes[nwords] = torch.empty(nwords, dtype=torch.int32, device=self.device)
             p.F_planes = _p(buf)
+            p.R_scale = float(residual_scale)
         if self.cond_limit > 0.0 and not self.ablate and not f64:
             if side.nrows not in self._redo_rows:
                 self._redo_rows[side.nrows] = torch.empty(max(side.nrows, 1), dtype=torch.int32, device=self.device)

@@ -224,7 +224,8 @@ __device__ __forceinline__ void process_chunk_planes(RowAcc<KB>& A, f32x4 (&E)[K
     }
 }
 
-// E (rows 0, 1, 2 of the lanes q = 0) -> the lane's partial right-hand side / column sums, unscaled; E restarts at zero
+// E (rows 0, 1, 2 of the lanes q = 0) -> the lane's partial right-hand side / column sums, unscaled by 1 / S (the
+// right-hand side still carries the residual scale: gram_accumulate takes it off once per task); E restarts at zero
 template <int KB>
 __device__ __forceinline__ void fold_planes_rhs(RowAcc<KB>& A, f32x4 (&E)[KB], int q, float inv_s) {
 #pragma unroll
@@ -275,7 +276,7 @@ __device__ __forceinline__ void gram_accumulate(RowAcc<KB>& A, const int32_t* __
                                                 const float* __restrict__ F, int ld, int zero_row,
                                                 const float* __restrict__ bias_other, float mu,
                                                 float bself, int lane, float* __restrict__ Ls, float S,
-                                                const uint32_t* __restrict__ planes = nullptr) {
+                                                const uint32_t* __restrict__ planes = nullptr, float Rs = 1.f) {
     const int c = lane & 15, q = lane >> 4;
     const float* Fc = F + KB * c;
     int nflush = 0;
@@ -285,6 +286,13 @@ __device__ __forceinline__ void gram_accumulate(RowAcc<KB>& A, const int32_t* __
     const int sel_c = (c == 0) ? 0x05040100 : (c == 2) ? 0x07060302 : 0x0c0c0c0c;
     const int ones_c = (c == 1) ? 0x3C003C00 : 0;
     const float inv_s = __int_as_float((254 - ((__float_as_int(S) >> 23) & 0xff)) << 23);      // S is a power of two
+    // MODE 2: the residuals reach the matrix cores as fp16 pairs and get a scale of their own, Rs - a power of two
+    // from the caller (als_row_solve_params::R_scale) that puts the call's largest rating in [2^9, 2^10): a residual
+    // of up to 64 times that rating stays below the fp16 overflow (65520), one down to 2^-13 of it keeps a normal low
+    // term, and the pair is the same whatever power of two the ratings were multiplied by.  The right-hand side is
+    // accumulated with the scale on (the chunk loop is the unscaled one's) and multiplied by 1 / Rs once per task.
+    const float inv_r = __int_as_float((254 - ((__float_as_int(Rs) >> 23) & 0xff)) << 23);      // Rs: a power of two too
+    const float bself_rs = bself * Rs;
     if constexpr (MODE == 2) {
 #pragma unroll
         for (int b = 0; b < KB; ++b) E[b] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -311,7 +319,13 @@ __device__ __forceinline__ void gram_accumulate(RowAcc<KB>& A, const int32_t* __
         const float rb = val0 - mu - bo0;
         A.sumr += ok ? rb : 0.f;
         A.sumr2 = ok ? fmaf(rb, rb, A.sumr2) : A.sumr2;
-        const float r0 = ok ? (rb - bself) : 0.f;
+        // (MODE 2: (rb - bself) Rs in the one rounding of the subtraction - the products with a power of two are exact)
+        const float r0 = ok ? (MODE == 2 ? fmaf(rb, Rs, -bself_rs) : rb - bself) : 0.f;
+        float r0err = 0.f;              // MODE 2: what the rounding of that subtraction dropped (TwoSum; rb Rs is exact)
+        if constexpr (MODE == 2) {
+            const float a = rb * Rs, bb = r0 - a;
+            r0err = ok ? ((a - (r0 - bb)) + (-bself_rs - bb)) : 0.f;
+        }
         const int off0 = idx0 * ld;                       // < 2^31 elements (checked by the launcher)
         if constexpr (MODE == 0) {
             if (nvalid == 64) process_chunk<KB, true>(A, off0, r0, 64, Fc, q);
@@ -320,7 +334,7 @@ __device__ __forceinline__ void gram_accumulate(RowAcc<KB>& A, const int32_t* __
             if constexpr (MODE == 2) {
                 // the residual of the lane's rating in two fp16 terms, one dword: (r_hi, r_lo)
                 const _Float16 rh = (_Float16)r0;
-                const _Float16 rl = (_Float16)(r0 - (float)rh);
+                const _Float16 rl = (_Float16)((r0 - (float)rh) + r0err);
                 const int rp = (int)__builtin_bit_cast(unsigned short, rh) | ((int)__builtin_bit_cast(unsigned short, rl) << 16);
                 if (nvalid == 64) process_chunk_planes<KB, true>(A, E, off0, rp, 64, Pc, q, sel_c, ones_c);
                 else              process_chunk_planes<KB, false>(A, E, off0, rp, nvalid, Pc, q, sel_c, ones_c);
@@ -337,7 +351,11 @@ __device__ __forceinline__ void gram_accumulate(RowAcc<KB>& A, const int32_t* __
         }
     }
     if (MODE != 0) mfma_results_settle();         // whoever reads the accumulators next (totals, partial slot, finish_row)
-    if constexpr (MODE == 2) fold_planes_rhs<KB>(A, E, q, inv_s);
+    if constexpr (MODE == 2) {
+        fold_planes_rhs<KB>(A, E, q, inv_s);
+#pragma unroll
+        for (int b = 0; b < KB; ++b) A.rhs[b] *= inv_r;
+    }
     if (MODE != 0 && nflush > 0) {
         unflush_acc<KB>(A, Ls, lane);
         wave_lds_sync();
@@ -731,6 +749,10 @@ __device__ __forceinline__ void finish_row(RowAcc<KB>& A, const als_row_solve_pa
         if (lane + 64 * rr < KP) P.X_out[r64 * P.ld + colrow[rr]] = x[rr];
     __builtin_amdgcn_sched_barrier(0);
     if (lane == 0) {
+        // never a silent inf / NaN: the new bias holds (F^T 1).x, so it is finite only if every x is - what a residual
+        // past the fp16 range of the pre-split path's scaled pair (|r| R_scale >= 65520) does to the row's sums is
+        // reported like a failed factorisation
+        if (!(fabsf(bnew) < __builtin_inff())) atomicMax(P.status, row + 1);
         P.bias_out[row] = bnew;
         if (P.stat_out) { P.stat_out[2 * r64] = st1; P.stat_out[2 * r64 + 1] = st2; }
     }
@@ -765,7 +787,7 @@ void k_row_tasks(const als_row_solve_params P) {
     if (!(P.reserved0 & 1))        // reserved0: ablation flags for profiling builds, 0 in production
         gram_accumulate<KB, MODE>(A, P.indices + beg, P.vals + beg, len, P.F, P.ld, P.F_zero_row,
                                   P.bias_other, mu, bself, lane, lds_all + wave * C::LDS_FLOATS, S,
-                                  (const uint32_t*)P.F_planes);
+                                  (const uint32_t*)P.F_planes, P.R_scale);
     if (slot >= 0) {
         store_partial<KB>(A, (float*)P.workspace + (size_t)slot * C::SLOT_ITEMS * 64, lane);
         return;
@@ -1117,6 +1139,7 @@ int launch_row_solve(const als_row_solve_params* p, hipStream_t st) {
     if (nprimal > 0) {
         als_row_solve_params q = *p;
         q.ntasks = nprimal;
+        if (!(q.R_scale > 0.f)) q.R_scale = 1.f;            // 0 = not given: the residual pair unscaled
         const unsigned grid = (unsigned)((nprimal + C::WPW - 1) / C::WPW);
         bool planes = false;
         if constexpr (KB == 4 || KB == 8)
@@ -1439,7 +1462,9 @@ static int row_solve_checked(const als_row_solve_params* p, void* stream, bool w
     if (p->ld != ld || !p->indptr || !p->indices || !p->vals || !p->F || !p->bias_self ||
         !p->bias_other || !p->mu || !p->status || p->ntasks < 0 || p->nlong < 0 || p->F_zero_row < 0 ||
         (p->gram_mode != ALS_GRAM_F32 && p->gram_mode != ALS_GRAM_F16X2 && p->gram_mode != ALS_GRAM_F64) ||
-        (int64_t)p->F_zero_row * ld >= ((int64_t)1 << 31))
+        (int64_t)p->F_zero_row * ld >= ((int64_t)1 << 31) ||
+        !(p->R_scale == 0.f || (p->R_scale >= 1.1754944e-38f && p->R_scale < __builtin_inff() &&
+                                (__builtin_bit_cast(uint32_t, p->R_scale) & 0x7FFFFFu) == 0)))     // 0 or a normal power of two
         return ALS_E_BADARG;
     if (p->ntasks > 0 && !p->tasks) return ALS_E_BADARG;
     if (p->nlong > 0 && (!p->long_rows || !p->workspace)) return ALS_E_BADARG;

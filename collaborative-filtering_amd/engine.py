@@ -172,6 +172,15 @@ class _Engine(_Serving):
         # --- ratings in HBM
         self.csr = cache.get(("side_dev", ku), lambda: _side_to_dev(csr, self.dev))
         self.csc = cache.get(("side_dev", ki), lambda: _side_to_dev(csc, self.dev))
+        # scale of the fp16 residual pair of the row solve's pre-split path (als_row_solve_params::R_scale): from the
+        # largest |rating|, once per fit, here where the ratings are staged - they do not change between iterations,
+        # so the replayed graph carries the same constant as the eager fit.  Both half steps pass it: the U-step takes
+        # that path at k = 49 ... 64, the V-step whenever its gathered table (U) is small enough.
+        self.rs_kw = {}
+        if hasattr(self.be, "residual_scale"):
+            vmax = cache.get(("max_abs_val", ku), lambda: float(torch.as_tensor(csr.vals).abs().max().item())
+                             if csr.vals.shape[0] else 0.0)
+            self.rs_kw = {"residual_scale": self.be.residual_scale(vmax)}
         uptr_h = cache.get(("indptr_h", ku), lambda: self.csr.indptr.cpu().numpy())
         iptr_h = cache.get(("indptr_h", ki), lambda: self.csc.indptr.cpu().numpy())
         # --- shards: contiguous row ranges balanced by predicted cost = ratings + c(k) * rows (about
@@ -476,7 +485,7 @@ class _Engine(_Serving):
                   bias_other=self.b_i, mu=self.mu, lam=md.lambda_u, lam_row=None, lam_b=md.lambda_bu,
                   lam_b_row=None, rhs_extra=None, diag_extra=None, X_out=self.U, bias_out=self.b_u,
                   gram_out=None, factor_out=None, rhs_out=None, colsum_out=None, sumr_out=None,
-                  status=self.status, workspace=self.workspace)
+                  status=self.status, workspace=self.workspace, **self.rs_kw)
         if self.u_chunks == 1:
             with self._tick("row_solve_user"):
                 self.be.row_solve(tasks=self.utasks, **kw)
@@ -506,7 +515,7 @@ class _Engine(_Serving):
                       bias_other=self.b_u, mu=self.mu, lam=0.0, lam_row=self.lam_v_row,
                       lam_b=md.lambda_bi, lam_b_row=None, rhs_extra=None,
                       gram_out=self.gram if want_gram else None, status=self.status,
-                      tasks=self.itasks, workspace=self.workspace, **self.f64kw)
+                      tasks=self.itasks, workspace=self.workspace, **self.f64kw, **self.rs_kw)
         if not self.use_graph:
             with self._tick("row_solve_item"):
                 self.be.row_solve(diag_extra=None, X_out=self.V, bias_out=self.b_i, factor_out=None,

@@ -108,7 +108,9 @@ int64_t als_partial_slot_bytes_f64(int k);     /* slot size when gram_mode == AL
  *                               L (perm space) with 1/L_ii on the diagonal
  *   is written for als_gs_sweep, which also needs rhs_out/colsum_out/sumr_out.
  * status: int32[1], must be 0 on entry (host zeroes it); on a non-SPD pivot
- *   the kernel stores (row + 1) with atomicMax.
+ *   - or a row whose new bias is not finite, which is what a residual beyond
+ *   the range of R_scale on the F_planes path leads to - the kernel stores
+ *   (row + 1) with atomicMax.
  * workspace: als_partial_slot_bytes(k) * (number of slots referenced by
  *   tasks) bytes; may be NULL when no task has slot >= 0.
  * ------------------------------------------------------------------------- */
@@ -197,6 +199,18 @@ typedef struct als_row_solve_params {
                                            vector instructions per rating.  Pays where F is small and the launch is
                                            bound by vector issue (the U-step); costs one pass over F.  Must not be
                                            shared by concurrent calls */
+    float          R_scale;             /* F_planes path only: scale of the residuals vals - mu - bias_other - bias_self,
+                                           which that path hands to the matrix cores as two fp16 terms each.  The
+                                           CALLER supplies it: the power of two that puts the largest |vals| of the
+                                           call in [2^9, 2^10) (a per-fit constant; the bindings' residual_scale()).
+                                           A residual of up to 64 times the largest rating then stays inside the fp16
+                                           range and one down to 2^-13 of it keeps full precision (2^-21 relative);
+                                           the results are the same bits, times 2^p, when vals, mu and the biases are
+                                           multiplied by 2^p and R_scale by 2^-p.  A residual beyond the range
+                                           (|r| R_scale >= 65520) makes the row's sums inf / NaN: status receives
+                                           (row + 1) as for a non-SPD pivot.  0 = 1.0 (no scale: accurate for ratings
+                                           of order 1 ... 10^3 only); anything else that is not a normal power of
+                                           two: ALS_E_BADARG */
 } als_row_solve_params;
 
 int als_row_solve(const als_row_solve_params* p, void* stream);
