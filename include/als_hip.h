@@ -357,10 +357,16 @@ int als_w_normal_equations(const als_w_params* p, void* stream);
  * als_spd_solve_f64: x = (A + diag_add I)^-1 b by a dense fp64 Cholesky factorisation -
  * the reference's `cholesky_solve(A, b)` on the W-step's (d k) x (d k) normal equations
  * (scripts/als.py:497-500; scripts/helpers.py cholesky_solve).
- * A: [N][lda] row-major fp64, symmetric (both triangles valid), not modified.  b, x: [N] (may alias).
- * workspace: als_spd_solve_workspace_bytes(N) bytes of device memory (0 = N out of range).
- * status (device int32): 0 ok; p > 0: pivot p-1 was not positive (not SPD, x is then meaningless).
- * Enqueues 2 ceil(N/64) + 2 small kernels on `stream`.
+ * A: [N][lda] row-major fp64, lda >= N (columns N .. lda-1 are never read), symmetric (both triangles
+ * valid), not modified.  b, x: [N] (may alias).  1 <= N <= ALS_SPD_MAX_N.
+ * workspace: als_spd_solve_workspace_bytes(N) bytes of device memory (0 = N out of range); its contents
+ * on entry do not matter, a call writes everything it reads.
+ * status (device int32): any value on entry, every call resets it.  0 ok; p > 0: pivot p-1 is the first
+ * that was not positive; a NaN pivot counts, so a NaN entry A[r][c], r >= c, reports r + 1.  x is then
+ * meaningless (the pivot is replaced by 1 and the call runs to its end).
+ * Backward stable at LAPACK's level for cond_2 up to 1e12 and under A 2^p, |p| <= 400 (tests/test_gpu_spd_solve.py).
+ * Enqueues at most 2 ceil(N/64) + 2 small kernels on `stream`; the last one takes (ceil(N/64) + 1) 512 bytes
+ * of dynamic LDS, 64 KB at ALS_SPD_MAX_N.
  * ------------------------------------------------------------------------- */
 #define ALS_SPD_MAX_N 8128
 size_t als_spd_solve_workspace_bytes(int64_t N);
