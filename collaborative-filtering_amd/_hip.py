@@ -32,7 +32,7 @@ EXPORTS = ("als_version", "als_padded_k", "als_perm_index", "als_partial_slot_by
            "als_recommend_topk_segmented", "als_rank_count_segmented", "als_eligibility_bitmaps",
            "als_recommend_topk_priced", "als_capacity_settle_workspace_bytes", "als_capacity_settle",
            "als_recommend_topk_quota",
-           "als_table_gram_partials", "als_table_gram_f64", "als_implicit_row_solve")
+           "als_table_gram_partials", "als_table_gram_f64", "als_table_gram_weighted_f64", "als_implicit_row_solve")
 
 # the workspace queries: they return size_t, everything else but the two slot-size queries an int status / value
 SIZE_QUERIES = ("als_spd_solve_workspace_bytes", "als_recommend_workspace_bytes", "als_rank_count_workspace_bytes",
@@ -139,6 +139,7 @@ class ImplicitParams(C.Structure):
         ("G_scale", C.c_double), ("lambda_scalar", _f32), ("lambda_row", _vp),
         ("X_out", _vp), ("xb_out", _vp), ("status", _vp),
         ("tasks", _vp), ("ntasks", _i64), ("long_rows", _vp), ("nlong", _i64), ("workspace", _vp),
+        ("g_scale_row", _vp),
     ]
 
 
@@ -240,6 +241,7 @@ def load():
                                           C.c_int, _vp, _vp, _vp, _vp, _vp]
     lib.als_list_miscalibration.argtypes = [C.c_int, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _f32, _vp, _vp]
     lib.als_table_gram_f64.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]
+    lib.als_table_gram_weighted_f64.argtypes = [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp]
     lib.als_implicit_row_solve.argtypes = [C.POINTER(ImplicitParams), _vp]
     lib.als_graph_classify.argtypes =[_i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.als_normalize_features.argtypes = [_i64, C.c_int, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp]

@@ -557,20 +557,31 @@ class HipBackend:
         kb = ld // 16
         return kb * (kb + 1) // 2 * 256
 
-    def table_gram(self, k, ld, F, out):
+    def table_gram(self, k, ld, F, out, w=None):
         """out fp64 [table_gram_doubles(ld)] = F^T F over all rows of the fp32 table F [rows, ld], the perm-space
-        lower-block image als_implicit_row_solve takes: als_table_gram_f64.  The partials are owned here."""
+        lower-block image als_implicit_row_solve takes: als_table_gram_f64.  With the row weights w (fp32 [rows]):
+        F^T diag(w) F, als_table_gram_weighted_f64.  The partials are owned here."""
         assert F.dtype == torch.float32 and F.is_contiguous() and F.shape[1] == ld
         assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= self.table_gram_doubles(ld)
         need = 8 * int(self.lib.als_table_gram_partials()) * self.table_gram_doubles(ld)
-        self._check(self.lib.als_table_gram_f64(k, ld, F.shape[0], _p(F), self._workspace("table_gram", need), _p(out),
-                                                self._stream()), "als_table_gram_f64")
+        if w is None:
+            self._check(self.lib.als_table_gram_f64(k, ld, F.shape[0], _p(F), self._workspace("table_gram", need),
+                                                    _p(out), self._stream()), "als_table_gram_f64")
+            return
+        assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() >= F.shape[0] and w.device == F.device
+        self._check(self.lib.als_table_gram_weighted_f64(k, ld, F.shape[0], _p(F), _p(w),
+                                                         self._workspace("table_gram", need), _p(out),
+                                                         self._stream()), "als_table_gram_weighted_f64")
 
     def implicit_row_solve(self, *, k, ld, side, F, zero_row, G, g_scale, lam, lam_row, X_out, xb_out, status, tasks,
-                           rhs_w=None):
+                           rhs_w=None, g_scale_row=None):
         """x = (g_scale G + sum a f f^T + (lam + 1e-10) I)^-1 sum t f for the rows of `tasks` (side.vals holds the
         weights a; rhs_w the t, None: t = 1 + a); rows of `side` without entries get x = 0: als_implicit_row_solve.
+        g_scale_row (fp32 [side.nrows]): row r takes g_scale g_scale_row[r] in place of g_scale.
         zero_row: the row of F that lanes past a row's end gather, or -1.  The slot workspace is owned here."""
+        if g_scale_row is not None:
+            assert (g_scale_row.dtype == torch.float32 and g_scale_row.is_contiguous()
+                    and g_scale_row.numel() >= side.nrows and g_scale_row.device == F.device)
         p = _hip.ImplicitParams()
         p.k, p.ld, p.nrows, p.ncols, p.F_zero_row = k, ld, side.nrows, F.shape[0], int(zero_row)
         assert F.dtype == torch.float32 and F.is_contiguous() and F.shape[1] == ld and -1 <= int(zero_row) < F.shape[0]
@@ -583,6 +594,7 @@ class HipBackend:
         p.tasks, p.ntasks = _p(tasks.tasks), tasks.ntasks
         p.long_rows, p.nlong = _p(tasks.long_rows), tasks.nlong
         p.workspace = self._workspace("implicit_slots", tasks.nslots * self.slot_bytes(k, True))
+        p.g_scale_row = _p(g_scale_row)
         self._check(self.lib.als_implicit_row_solve(C.byref(p), self._stream()), "als_implicit_row_solve")
 
     # -- K11 -------------------------------------------------------------------

@@ -11,13 +11,16 @@
 //   order.  Nothing depends on timing: the result is a function of (F, nrows, k) alone, bit for bit.  The output is
 //   the lower-block perm-space image of row_f64_common.hpp, the form the row kernel adds to its own image with one
 //   pass of "img[e] += G[e]" (natural order would cost it a permuted read per element).
+//   als_table_gram_weighted_f64 is the same grid, ranges and fold with G = F^T diag(w) F: the
+//   second instantiation of table_gram_pass, whose A operand is f w_r; als_table_gram_f64 launches the first one.
 //
 // als_implicit_row_solve: one wave per task as k_row_tasks_f64 (same als_task / als_long_row lists, same fp64 slot
 //   layout, slots folded in slot order by slot_fold.hpp), the Gram pass being gram_pass_f64 with the A operand scaled
 //   by a_t and rhs += t_t f_t.  Lanes past the end of a row gather a valid row of F with a = t = 0, which removes
 //   them exactly (F is finite), so F needs no zero row.  After the image is complete: + G, the regulariser on the
 //   real diagonal and 1 on the padded one, cholesky_f64<KB, 1>, solve_lt_f64; only x is rounded to fp32.
-//   A row's result depends on its entries, F and G alone (fixed reduction orders, no cross-row state).
+//   G enters as G_scale G, or as (G_scale g_scale_row[row]) G where a per-row scale is given (section 33).
+//   A row's result depends on its entries, F, G and its scale alone (fixed reduction orders, no cross-row state).
 #include "als_device.hpp"
 #include "als_hip.h"
 #include "row_f64_common.hpp"
@@ -32,11 +35,14 @@ constexpr int TABLE_GRAM_PARTIALS = 512;
 // ---------------------------------------------------------------------------------------------------------
 // table Gram: block rows [I0, I1) of the lower triangle over the table rows [beg, end).  Lane (c, q) holds the KB
 // contiguous floats F[row 4 s + q][KB c ...] = position c of every block (perm space), as in gram_pass_f64; columns
-// >= k and rows >= end are zeroed after the load.
+// >= k and rows >= end are zeroed after the load.  WEIGHTED: G = sum_r w_r f_r f_r^T - the A operand of every MFMA
+// is (double)f * (double)w_r, exact in fp64 (24 + 24 significand bits), the B operand is unscaled; rows >= end take
+// weight 0 and read w at `beg`, so nothing past nrows is read.  With every w_r = 1 the operands, and so the bits, are
+// the unweighted pass's.
 // ---------------------------------------------------------------------------------------------------------
-template <int KB, int I0, int I1>
-__device__ __forceinline__ void table_gram_pass(const float* __restrict__ F, int k, int64_t beg, int64_t end,
-                                                double* __restrict__ out, int lane) {
+template <int KB, int I0, int I1, bool WEIGHTED>
+__device__ __forceinline__ void table_gram_pass(const float* __restrict__ F, const float* __restrict__ w, int k,
+                                                int64_t beg, int64_t end, double* __restrict__ out, int lane) {
     constexpr int NB = blk64(I1, 0) - blk64(I0, 0);
     constexpr int GS = 4;                                    // 4-row steps whose loads are in flight together
     constexpr int LD = 16 * KB;
@@ -47,24 +53,39 @@ __device__ __forceinline__ void table_gram_pass(const float* __restrict__ F, int
     for (int a = 0; a < NB; ++a) acc[a] = f64x4{0.0, 0.0, 0.0, 0.0};
     for (int64_t r0 = beg; r0 < end; r0 += 4 * GS) {
         float f[GS][KB];
+        float wr[GS];
         bool live[GS];
 #pragma unroll
         for (int s = 0; s < GS; ++s) {
             const int64_t r = r0 + 4 * s + q;
             live[s] = r < end;
             load_frow<KB>(Fc + (live[s] ? r : beg) * LD, f[s]);
+            if constexpr (WEIGHTED) wr[s] = w[live[s] ? r : beg];
         }
 #pragma unroll
         for (int s = 0; s < GS; ++s) {
             double fd[KB];
 #pragma unroll
             for (int b = 0; b < KB; ++b) fd[b] = (live[s] && KB * c + b < k) ? (double)f[s][b] : 0.0;
+            if constexpr (WEIGHTED) {
+                const double wd = live[s] ? (double)wr[s] : 0.0;
+                double fw[KB];
 #pragma unroll
-            for (int I = I0; I < I1; ++I)
+                for (int b = 0; b < KB; ++b) fw[b] = fd[b] * wd;
 #pragma unroll
-                for (int K = 0; K <= I; ++K)
-                    acc[blk64(I, K) - blk64(I0, 0)] = __builtin_amdgcn_mfma_f64_16x16x4f64(
-                        fd[I], fd[K], acc[blk64(I, K) - blk64(I0, 0)], 0, 0, 0);
+                for (int I = I0; I < I1; ++I)
+#pragma unroll
+                    for (int K = 0; K <= I; ++K)
+                        acc[blk64(I, K) - blk64(I0, 0)] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                            fw[I], fd[K], acc[blk64(I, K) - blk64(I0, 0)], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int I = I0; I < I1; ++I)
+#pragma unroll
+                    for (int K = 0; K <= I; ++K)
+                        acc[blk64(I, K) - blk64(I0, 0)] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+                            fd[I], fd[K], acc[blk64(I, K) - blk64(I0, 0)], 0, 0, 0);
+            }
         }
     }
     // accumulator register i of lane (c, q) is element (row q + 4 i, col c) of its block
@@ -77,13 +98,13 @@ __device__ __forceinline__ void table_gram_pass(const float* __restrict__ F, int
                 out[blk64(I, K) * 256 + (q + 4 * i) * 16 + c] = acc[blk64(I, K) - blk64(I0, 0)][i];
 }
 
-template <int KB, int I0>
-__device__ __forceinline__ void table_gram_passes(const float* __restrict__ F, int k, int64_t beg, int64_t end,
-                                                  double* __restrict__ out, int lane) {
+template <int KB, int I0, bool WEIGHTED>
+__device__ __forceinline__ void table_gram_passes(const float* __restrict__ F, const float* __restrict__ w, int k,
+                                                  int64_t beg, int64_t end, double* __restrict__ out, int lane) {
     if constexpr (I0 < KB) {
         constexpr int I1 = F64Cfg<KB>::pass_end(I0);
-        table_gram_pass<KB, I0, I1>(F, k, beg, end, out, lane);
-        table_gram_passes<KB, I1>(F, k, beg, end, out, lane);
+        table_gram_pass<KB, I0, I1, WEIGHTED>(F, w, k, beg, end, out, lane);
+        table_gram_passes<KB, I1, WEIGHTED>(F, w, k, beg, end, out, lane);
     }
 }
 
@@ -92,7 +113,19 @@ __global__ __launch_bounds__(64)
 void k_table_gram(const float* __restrict__ F, int k, int64_t nrows, double* __restrict__ partials) {
     const int64_t chunk = (nrows + TABLE_GRAM_PARTIALS - 1) / TABLE_GRAM_PARTIALS;
     const int64_t beg = min(nrows, (int64_t)blockIdx.x * chunk), end = min(nrows, beg + chunk);
-    table_gram_passes<KB, 0>(F, k, beg, end, partials + (size_t)blockIdx.x * F64Cfg<KB>::IMG, threadIdx.x);
+    table_gram_passes<KB, 0, false>(F, nullptr, k, beg, end, partials + (size_t)blockIdx.x * F64Cfg<KB>::IMG,
+                                    threadIdx.x);
+}
+
+// the same grid and row ranges with the row weights w [nrows]
+template <int KB>
+__global__ __launch_bounds__(64)
+void k_table_gram_weighted(const float* __restrict__ F, const float* __restrict__ w, int k, int64_t nrows,
+                           double* __restrict__ partials) {
+    const int64_t chunk = (nrows + TABLE_GRAM_PARTIALS - 1) / TABLE_GRAM_PARTIALS;
+    const int64_t beg = min(nrows, (int64_t)blockIdx.x * chunk), end = min(nrows, beg + chunk);
+    // (a workgroup with an empty range runs no step: it reads neither F nor w)
+    table_gram_passes<KB, 0, true>(F, w, k, beg, end, partials + (size_t)blockIdx.x * F64Cfg<KB>::IMG, threadIdx.x);
 }
 
 // G[e] = partial 0 + partial 1 + ... in index order, one thread per element
@@ -194,14 +227,16 @@ __device__ __forceinline__ void rhs_to_rows(double (&rhs)[KB], double (&rhs_p)[F
     }
 }
 
-// img: lower blocks of sum a f f^T; rhs_p: lane = perm row.  + a0 G, regularise, factorise, solve, store.
+// img: lower blocks of sum a f f^T; rhs_p: lane = perm row.  + a0 G (times the row's own scale, when one is given),
+// regularise, factorise, solve, store.
 template <int KB>
 __device__ __forceinline__ void finish_implicit(const als_implicit_params& P, int row, double* __restrict__ img,
                                                 double (&rhs_p)[F64Cfg<KB>::NR], int lane) {
     using C = F64Cfg<KB>;
     constexpr int KP = C::KP, NR = C::NR;
     const int c = lane & 15, q = lane >> 4;
-    for (int e = lane; e < C::IMG; e += 64) img[e] += P.G_scale * P.G[e];
+    const double g_scale = P.g_scale_row ? P.G_scale * (double)P.g_scale_row[row] : P.G_scale;
+    for (int e = lane; e < C::IMG; e += 64) img[e] += g_scale * P.G[e];
     wave_lds_sync();
     // regulariser on the real diagonal, 1 on the padded one (as finish_row_f64)
     const double lam = (double)(P.lambda_row ? P.lambda_row[row] : P.lambda_scalar) + 1e-10;
@@ -317,9 +352,14 @@ void k_implicit_empty_rows(const als_implicit_params P) {
 }
 
 template <int KB>
-int launch_table_gram(int k, int64_t nrows, const float* F, double* partials, double* G, hipStream_t st) {
+int launch_table_gram(int k, int64_t nrows, const float* F, const float* w, double* partials, double* G,
+                      hipStream_t st) {
     constexpr int IMG = F64Cfg<KB>::IMG;
-    hipLaunchKernelGGL(k_table_gram<KB>, dim3(TABLE_GRAM_PARTIALS), dim3(64), 0, st, F, k, nrows, partials);
+    if (w)
+        hipLaunchKernelGGL(k_table_gram_weighted<KB>, dim3(TABLE_GRAM_PARTIALS), dim3(64), 0, st, F, w, k, nrows,
+                           partials);
+    else
+        hipLaunchKernelGGL(k_table_gram<KB>, dim3(TABLE_GRAM_PARTIALS), dim3(64), 0, st, F, k, nrows, partials);
     hipLaunchKernelGGL(k_table_gram_fold, dim3((IMG + 255) / 256), dim3(256), 0, st, partials, IMG, G);
     return hipGetLastError() == hipSuccess ? 0 : ALS_E_LAUNCH;
 }
@@ -341,15 +381,20 @@ int launch_implicit(const als_implicit_params* p, hipStream_t st) {
 
 extern "C" int als_table_gram_partials(void) { return TABLE_GRAM_PARTIALS; }
 
-extern "C" int als_table_gram_f64(int k, int ld, int64_t nrows, const float* F, double* partials, double* G_out,
-                                  void* stream) {
+extern "C" int als_table_gram_weighted_f64(int k, int ld, int64_t nrows, const float* F, const float* w,
+                                           double* partials, double* G_out, void* stream) {
     const int kp = als_padded_k(k);
     if (kp < 0) return ALS_E_BADK;
     if (ld != kp || nrows < 0 || (nrows > 0 && !F) || !partials || !G_out || ((uintptr_t)F & 15) != 0)
         return ALS_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    ALS_DISPATCH_KB(kp / 16, return launch_table_gram<KB>(k, nrows, F, partials, G_out, st));
+    ALS_DISPATCH_KB(kp / 16, return launch_table_gram<KB>(k, nrows, F, w, partials, G_out, st));
     return 0;
+}
+
+extern "C" int als_table_gram_f64(int k, int ld, int64_t nrows, const float* F, double* partials, double* G_out,
+                                  void* stream) {
+    return als_table_gram_weighted_f64(k, ld, nrows, F, nullptr, partials, G_out, stream);
 }
 
 extern "C" int als_implicit_row_solve(const als_implicit_params* p, void* stream) {

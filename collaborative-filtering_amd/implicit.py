@@ -14,7 +14,10 @@ pairs, p = 0 and c = 1 elsewhere.  A half-step solves per row (F the other side'
 
     (a0 F^T F + sum_t a_t f_t f_t^T + (lambda + 1e-10) I) x = sum_t t_t f_t
 
-in fp64 (als_table_gram_f64 once per half-step, als_implicit_row_solve per row).  There are no biases, no mu, no
+in fp64 (als_table_gram_f64 once per half-step, als_implicit_row_solve per row).  `item_weight` / `user_weight` put
+rank-one weights p_u q_i on the all-entries term, a0 sum_all p_u q_i (u.v)^2 (section 33): a user row then takes
+(a0 p_u) sum_i q_i v_i v_i^T, an item row (a0 q_i) sum_u p_u u_u u_u^T - still one Gram per half-step.
+There are no biases, no mu, no
 features and no graph: predict is U V^T, and everything `serving._Serving` offers on `U V Z b_u b_i mu csr` works
 on the fitted tables with b_u = b_i = 0, mu = 0, Z = V.
 
@@ -41,6 +44,7 @@ from .serving import _Serving, _raise_unless_solved
 logger = logging.getLogger(__name__)
 
 CONFIDENCES = ("linear", "log")
+ITEM_WEIGHTS = ("popularity",)
 DIAG_EPS = 1e-10        # what als_implicit_row_solve adds to lambda on the diagonal (as every row solve here does)
 
 
@@ -50,6 +54,34 @@ class ImplicitConfig:
     confidence: str = "linear"
     eps: float = 1.0                    # scale of the counts under "log"
     unobserved_weight: float = 1.0      # a0, the weight of (u.v)^2 on every entry of the matrix
+    # rank-one weights p_u q_i on that all-entries term; None: 1 for every user / item
+    item_weight: object = None          # "popularity", or an array [n], finite and >= 0
+    popularity_exponent: float = 0.5    # eta of "popularity": q_i proportional to (entries of item i) ** eta
+    user_weight: object = None          # an array [m], finite and >= 0
+
+
+def popularity_weights(counts, exponent: float) -> np.ndarray:
+    """q (float32 [n]) of `item_weight="popularity"`: q_i = n f_i^eta / sum_j f_j^eta for the entry counts f, evaluated
+    in float64 and rounded once, so that the mean is 1 and a0 keeps its meaning.  0^0 = 1 (eta = 0 is uniform); without
+    any entry q = 1."""
+    f = np.asarray(counts, dtype=np.float64)
+    w = f ** float(exponent)
+    total = w.sum()
+    if not total > 0:
+        return np.ones(f.size, dtype=np.float32)
+    return ((f.size * w) / total).astype(np.float32)
+
+
+def _weight_array(x, length: int, name: str) -> np.ndarray:
+    """A user's `user_weight` / `item_weight` array as the device stores it (float32 [length]), or ValueError."""
+    w = np.asarray(x, dtype=np.float64)
+    if w.ndim != 1 or w.size != length:
+        raise ValueError(f"ImplicitConfig.{name} must have one value per row ({length}), got shape {w.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        w32 = w.astype(np.float32)
+    if w.size and not bool((np.isfinite(w32) & (w32 >= 0)).all()):
+        raise ValueError(f"ImplicitConfig.{name} must be finite and >= 0")
+    return w32
 
 
 def confidence_weights(vals, cfg: ImplicitConfig):
@@ -81,6 +113,7 @@ class _ImplicitEngine(_Serving):
         self.world, self.rank = 1, 0
         self.native = getattr(backend, "lib", None) is not None
         self._init_shapes(model, csr, csc)
+        self._init_missing_weights(model, csc)
         self._init_sides(model, csr, csc)
         self._init_tasks()
         self._init_params(model)
@@ -94,6 +127,20 @@ class _ImplicitEngine(_Serving):
         self.nnz = int(csr.vals.shape[0])
         self.a0 = float(model.implicit.unobserved_weight)
         self.feat_names, self.feat_dims = [], []
+
+    def _init_missing_weights(self, model, csc):
+        """p (fp32 [m]) and q (fp32 [n]) of the all-entries term a0 sum_all p_u q_i (u.v)^2 on the device, or None
+        where the model has none (every value 1).  The same rounded values feed the Gram and the per-row scale."""
+        ic = model.implicit
+        self.p = self.q = None
+        if ic.user_weight is not None:
+            self.p = torch.from_numpy(_weight_array(ic.user_weight, self.m, "user_weight")).to(self.dev)
+        if isinstance(ic.item_weight, str):
+            ptr = csc.indptr.cpu().numpy() if torch.is_tensor(csc.indptr) else np.asarray(csc.indptr)
+            counts = np.diff(ptr.astype(np.int64))
+            self.q = torch.from_numpy(popularity_weights(counts, ic.popularity_exponent)).to(self.dev)
+        elif ic.item_weight is not None:
+            self.q = torch.from_numpy(_weight_array(ic.item_weight, self.n, "item_weight")).to(self.dev)
 
     def _init_sides(self, model, csr, csc):
         """The ratings in HBM with the confidence weights a IN PLACE of the values: the kernels read nothing else per
@@ -150,21 +197,25 @@ class _ImplicitEngine(_Serving):
     # ---------------------------------------------------------- half steps
     _tick = _Engine._tick           # (name, start, end) events per phase when self.timers is a list
 
-    def _half_step(self, name, side, tasks, F_store, nF, lam, X_out, xb_out):
+    def _half_step(self, name, side, tasks, F_store, nF, lam, X_out, xb_out, w_table=None, w_rows=None):
+        """w_table: the weights of the rows of F in the Gram; w_rows: the per-row scale of that Gram.  Either keyword
+        reaches the backend only when its weights are set: an unweighted model makes the calls it always made."""
+        gram_kw = {} if w_table is None else {"w": w_table}
+        solve_kw = {} if w_rows is None else {"g_scale_row": w_rows}
         with self._tick("table_gram"):
-            self.be.table_gram(self.k, self.ld, F_store[:nF], self.G)
+            self.be.table_gram(self.k, self.ld, F_store[:nF], self.G, **gram_kw)
         with self._tick(name):
             self.be.implicit_row_solve(k=self.k, ld=self.ld, side=side, F=F_store, zero_row=nF, G=self.G,
                                        g_scale=self.a0, lam=lam, lam_row=None, X_out=X_out, xb_out=xb_out,
-                                       status=self.status, tasks=tasks)
+                                       status=self.status, tasks=tasks, **solve_kw)
 
     def user_step(self):
         self._half_step("row_solve_user", self.csr, self.utasks, self.V_store, self.n, self.model.lambda_u, self.U,
-                        None)
+                        None, self.q, self.p)
 
     def item_step(self):
         self._half_step("row_solve_item", self.csc, self.itasks, self.U_store, self.m, self.model.lambda_v, self.V,
-                        self.xb)
+                        self.xb, self.p, self.q)
 
     def loss_step(self, it):
         """Because A x = b for every item row after the V-step, the G, weighted and lambda_v terms of the loss add up to
@@ -217,14 +268,15 @@ class _ImplicitEngine(_Serving):
     def _fold_in_dev(self, indptr: np.ndarray, indices: np.ndarray, vals: np.ndarray, Z, n_sweeps: int):
         """A new user's row is one implicit row solve against the fitted item table: folded factors (fp32 [B, ld]) and
         zero biases on the device, with the device CSR they were computed from.  `n_sweeps` is accepted and ignored:
-        there is no bias recurrence."""
+        there is no bias recurrence.  A new user has p = 1; the Gram is G_q = sum_i q_i z_i z_i^T of the fit's item
+        weights (the cached image is that weighted Gram)."""
         md = self.model
         check_ratings(vals)
         B = indptr.size - 1
         ptr_d, idx_d, a_d = self._csr_dev(indptr, indices, confidence_weights(vals, md.implicit))
         if self.G_fold is None or self.G_fold[0] != Z.data_ptr():
             G = torch.zeros_like(self.G)
-            self.be.table_gram(self.k, self.ld, Z, G)
+            self.be.table_gram(self.k, self.ld, Z, G, **({} if self.q is None else {"w": self.q}))
             self.G_fold = (Z.data_ptr(), G)
         U = torch.empty(B, self.ld, dtype=torch.float32, device=self.dev)
         b = torch.zeros(B, dtype=torch.float32, device=self.dev)
@@ -266,7 +318,21 @@ class ImplicitALS(ALS):
             raise ValueError("ImplicitConfig.eps must be > 0")
         if not (np.isfinite(ic.unobserved_weight) and ic.unobserved_weight >= 0):
             raise ValueError("ImplicitConfig.unobserved_weight must be >= 0")
+        if isinstance(ic.item_weight, str) and ic.item_weight not in ITEM_WEIGHTS:
+            raise ValueError(f"unknown item_weight '{ic.item_weight}': one of {ITEM_WEIGHTS}, or an array")
+        if not (np.isfinite(ic.popularity_exponent) and ic.popularity_exponent >= 0):
+            raise ValueError("ImplicitConfig.popularity_exponent must be finite and >= 0")
         self.history["loss"] = []
+
+    def missing_weights(self):
+        """(p [m], q [n]) as float32 numpy arrays: the weights p_u q_i the last fit put on the all-entries term, ones
+        where `user_weight` / `item_weight` is unset."""
+        eng = self._eng
+        if eng is None:
+            raise RuntimeError("missing_weights() needs a fitted model")
+        p = np.ones(eng.m, dtype=np.float32) if eng.p is None else eng.p.cpu().numpy().copy()
+        q = np.ones(eng.n, dtype=np.float32) if eng.q is None else eng.q.cpu().numpy().copy()
+        return p, q
 
     def _fit_sides(self, csr, csc, features, tol, min_iters, verbose, S, run: bool = True,
                    S_trusted: bool = False) -> "ImplicitALS":

@@ -1022,7 +1022,7 @@ typedef struct als_implicit_params {
     const float*   rhs_w;           /* nullable [nnz] t_t; NULL: t_t = 1 + a_t (preference 1 with confidence 1 + a) */
     const float*   F;               /* [ncols][ld], padding columns zero, 16-byte aligned */
     const double*  G;               /* als_table_gram_f64 image of F (or any symmetric image in that layout) */
-    double         G_scale;         /* a0, the weight of the unobserved entries: A = G_scale G + ... */
+    double         G_scale;         /* a0, the weight of the unobserved entries: A = G_scale G + ... (see g_scale_row) */
     float          lambda_scalar;   /* >= 0 */
     const float*   lambda_row;      /* nullable [nrows] */
     float*         X_out;           /* [nrows][ld], padding columns written as zero */
@@ -1032,10 +1032,21 @@ typedef struct als_implicit_params {
     const als_task*     tasks;      int64_t ntasks;
     const als_long_row* long_rows;  int64_t nlong;
     void*          workspace;       /* 16-byte aligned; may be NULL when nlong == 0 */
+    const float*   g_scale_row;     /* nullable [nrows], >= 0 by contract: A = (G_scale g_scale_row[row]) G + ..., the
+                                       product formed in fp64.  NULL: G_scale for every row (the same bits as a
+                                       g_scale_row of ones).  Appended last: every earlier offset stands */
 } als_implicit_params;
 
 int als_table_gram_partials(void);
 int als_table_gram_f64(int k, int ld, int64_t nrows, const float* F, double* partials, double* G_out, void* stream);
+/* G_out = sum_r w[r] f_r f_r^T = F^T diag(w) F: als_table_gram_f64 (same grid, partials, fold order, output image and
+ * argument checks) with the row weights w [nrows] (device, fp32, >= 0 by contract; nothing past nrows is read).  The
+ * A operand of every matrix-core step is (double)f * (double)w[r] - exact in fp64 - and the B operand is unscaled, so
+ * with every w[r] = 1.0f, or w = NULL, the result is bitwise als_table_gram_f64's; it is a function of
+ * (F, w, nrows, k) alone.  For general w a diagonal block is symmetric to rounding, not bitwise; the row kernels read
+ * its lower triangle. */
+int als_table_gram_weighted_f64(int k, int ld, int64_t nrows, const float* F, const float* w, double* partials,
+                                double* G_out, void* stream);
 int als_implicit_row_solve(const als_implicit_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------
